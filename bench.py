@@ -20,10 +20,17 @@ strong-scales the SAME job over N GPUs (parity mode: bit-identical to one GPU):
     process per GPU; every rank runs the host logic and evaluates its share of
     every batch, one shared-memory all-gather per batch (fscl_amd_set_ranks_shm)
     completes the results on every rank.  --gpus must equal WORLD_SIZE.
-Every timed job's final scan points (every field, floats as hex) are hashed and
+A plain run sets up, warms up, times the steps and prints the line.
+--dump-outputs DIR also writes the last timed job's scan points (what the
+caller of the timed path receives), one float64 array per field, DIR/<field>.npy;
+the inputs are seeded, so two builds can be compared output for output.
+--full adds what the headline figure does not need.  Every timed job's final
+scan points (every field, floats as hex) are hashed and
 compared with the oracle's digest of the same job (tests/golden/fullsize.json,
 made by tests/golden/make_fullsize.py) where one exists: parity over the whole
-job, the initial scan and all permutation trials with their pruning.
+job, the initial scan and all permutation trials with their pruning.  On one
+GPU the CPU baseline (the reference's compiled hot path, oracle/_ref) is timed
+and the north-star ratio reported.
 --config C2 gives BASELINE configs[1].
 
 value = (grid points + sum of permute_n) / wall seconds (max over ranks).
@@ -64,7 +71,13 @@ def parse():
     ap.add_argument("--n-permute", type=int, default=None)
     ap.add_argument("--seed", type=int, default=None,
                     help="synthetic genome seed (default 55 for C5 -- the seed of its oracle fixtures -- else 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the parity check of every timed job against the oracle's "
+                         "fixtures, the CPU baseline (the reference's compiled hot path) and the north-star ratio")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed job's scan points, one float64 array per "
+                         "field, as DIR/<field>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="CPU baseline threads (default: every CPU this process may run on)")
     ap.add_argument("--cpu-sample", type=int, default=None, help="CPU baseline: cells in the sample")
@@ -86,7 +99,10 @@ def parse():
     ap.add_argument("--profile-summary", default=None,
                     help="rocprofv3 summary (tools/prof_summary.py) for roofline.traffic and the issue roofline; "
                          "default: the newest profiles/r*_<config>_*summary.json")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.cpu_full_job and not args.full:
+        ap.error("--cpu-full-job is part of the CPU baseline: give --full too")
+    return args
 
 
 def cpu_info() -> dict:
@@ -200,6 +216,27 @@ def points_digest(pts) -> tuple[str, list[str]]:
     return h.hexdigest(), rows
 
 
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(dirpath, pts) -> None:
+    """--dump-outputs: what the timed path's caller receives -- the scan points of the last timed job
+    (fscl_amd.points: every field of every point) -- as one float64 array per field, <field>.npy
+    (the integer fields are below 2^31, exact in float64).  Past DUMP_MAX_BYTES in all, a fixed
+    seeded sample of the points, their indices in point_index.npy."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    names = pts.dtype.names
+    cap = DUMP_MAX_BYTES // (8 * (len(names) + 1))
+    (d / "point_index.npy").unlink(missing_ok=True)  # a reused DIR: no index beside a whole dump
+    if len(pts) > cap:
+        idx = np.sort(np.random.default_rng(0).choice(len(pts), size=cap, replace=False))
+        np.save(d / "point_index.npy", idx.astype(np.float64))
+        pts = pts[idx]
+    for k in names:
+        np.save(d / f"{k}.npy", np.ascontiguousarray(pts[k], dtype=np.float64))
+
+
 def heartbeat(period: float = 30.0) -> None:
     """A line on stderr every `period` seconds (long jobs, e.g. C5, print nothing else for minutes)."""
     import threading
@@ -295,10 +332,13 @@ def main() -> int:
     job_opts = ([f"--n-permute={n_permute}"] if n_permute > 0 else []) + (
         [f"--asc-depth={cfg['asc_depth']}", f"--asc-minimum-freq={cfg.get('asc_min_freq', 1)}"]
         if cfg.get("asc_depth", 0) else [])
-    fx_name, fx = full_job_fixture(snp, job_opts) if rank == 0 and args.permute_mode == "parity" else (None, None)
+    # --full: the oracle's digest of exactly this job, where one exists
+    fx_name, fx = (full_job_fixture(snp, job_opts) if args.full and rank == 0 and args.permute_mode == "parity"
+                   else (None, None))
     # else the oracle's digest of this genome's initial scan alone, where one exists (C5: its 50k-cell
     # initial scan takes the oracle minutes, too long to run live beside the bench)
-    sfx_name, sfx = full_job_fixture(snp, []) if rank == 0 and fx is None and job_opts else (None, None)
+    sfx_name, sfx = (full_job_fixture(snp, []) if args.full and rank == 0 and fx is None and job_opts
+                     else (None, None))
 
     fscl_amd.set_permute_mode(args.permute_mode)
 
@@ -317,7 +357,7 @@ def main() -> int:
     barrier()
     t0 = time.perf_counter()
     units, gp, n_perm_units = 0, 0, 0
-    timed_pts = []
+    timed_pts, pts = [], None
     for _ in range(args.steps):
         n_gp, n_perm, pts = job()
         units += n_gp + n_perm
@@ -332,8 +372,12 @@ def main() -> int:
         elapsed = float(t.item())
     st = fscl_amd.get_stats()
 
+    if args.dump_outputs and rank == 0 and pts is not None:  # every rank holds the whole job's points
+        dump_outputs(args.dump_outputs, pts)
+
     out = bench_line(args, cfg, st, units, elapsed, n_gpus, world, n_local, n_permute, gp, setup_s)
 
+    # ---- everything below the line's assembly runs with --full alone
     # ---- parity of every timed job, whole job: initial scan + all permutation trials, their
     # hits, prune draws and saved null CLRs, against the oracle's digest of the same job
     if fx is not None:
@@ -371,7 +415,7 @@ def main() -> int:
         out["parity"]["max_abs_dclr_initial_scan"] = 0.0 if ok else None
         out["max_abs_dclr"] = None
         out["max_abs_dclr_note"] = "initial scan only (parity.scope): no oracle fixture of the whole job"
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["parity"] = {"scope": "initial scan" if world == 1 and n_local == 1 and not args.no_cpu_baseline else
                          "none in this run", "note": "no oracle fixture of this exact job (tests/golden/fullsize.json)"}
 
@@ -384,18 +428,19 @@ def main() -> int:
     # times and the job's own counts.  Then the GPU's initial scan is checked against the
     # reference code's on a spread sample of cells... and against the oracle on all cells.
     # Test infrastructure: timed and compared here, never called by the product.
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         info = cpu_info()
         out["cpu_baseline"], scan_dclr, out["position_mismatches"] = cpu_baseline(
             args, cfg, snp, wd, info, fscl_amd, scan, tab, gp, n_perm_units, st["trials"] // max(1, args.steps),
             units / args.steps, elapsed / args.steps, live_parity=fx is None and sfx is None)
         if fx is None and sfx is None:
             out["max_abs_dclr"] = scan_dclr
-    if rank == 0:
+    if args.full and rank == 0:
         live = (out.get("cpu_baseline") or {}).get("node_linear", {}).get("job_s")
         out["north_star_ratio"] = north_star_ratio(args, n_permute, elapsed / args.steps, n_gpus, live)
         if out.get("cpu_baseline"):
             out["cpu_baseline"]["north_star_ratio"] = (out["north_star_ratio"] or {}).get("value")
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -1028,7 +1028,7 @@ def test_throughput_mode_two_ranks(built, tmp, tp_case):
 
 def test_bench_under_torchrun_is_the_drivers_scale_shape(built, tmp):
     """The driver's SCALE command, at two ranks: `python -m torch.distributed.run --nproc-per-node 2
-    bench.py --gpus 2`, one process per rank.  Both ranks sit on GPU 0 here (FSCL_AMD_DEVICE=0) and
+    bench.py --gpus 2`, one process per rank, here with --full for its parity check.  Both ranks sit on GPU 0 here (FSCL_AMD_DEVICE=0) and
     torch's own collectives (the segment-name broadcast, the elapsed-time max) run on gloo
     (FSCL_BENCH_BACKEND); on the driver's 8-GPU node the same path inits nccl with device_id.  C2 at
     its full size: rc 0, exactly one JSON line (rank 0's), n_gpus 2, and the timed job identical to
@@ -1038,7 +1038,7 @@ def test_bench_under_torchrun_is_the_drivers_scale_shape(built, tmp):
                FSCL_AMD_RANK_TIMEOUT="300")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr=127.0.0.1",
            f"--master-port={29900 + os.getpid() % 1000}", str(ROOT / "bench.py"), "--gpus", "2", "--config", "C2",
-           "--steps", "1", "--warmup", "0", "--workdir", str(tmp)]
+           "--steps", "1", "--warmup", "0", "--workdir", str(tmp), "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

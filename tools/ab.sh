@@ -12,7 +12,7 @@ for r in $(seq $ROUNDS); do
   for leg in "$@"; do
     name=${leg%%=*}; rest=${leg#*=}
     lib=${rest%%,*}; envs=""; [ "$rest" != "$lib" ] && envs=$(echo ${rest#*,} | tr ',' ' ')
-    env $envs FSCL_AMD_LIBDIR=$R/$lib timeout -k 10 ${AB_LIMIT:-400} python3 -u $R/bench.py $ARGS --no-cpu-baseline \
+    env $envs FSCL_AMD_LIBDIR=$R/$lib timeout -k 10 ${AB_LIMIT:-400} python3 -u $R/bench.py $ARGS --full --no-cpu-baseline \
       > $OUT/${name}_$r.json 2> $OUT/${name}_$r.err
     rc=$?
     if [ $rc -ne 0 ] && ! { [ $rc -eq 1 ] && [ -n "$ABLATION" ]; }; then echo "leg $name round $r: exit $rc"; exit $rc; fi

@@ -14,5 +14,5 @@ REDUCE=1 bash $R/tools/profile.sh ${TAG}_$c --config $CFG $EXTRA --steps 1 --war
 cp $R/gpurun_out/prof_${TAG}_$c/partial_all_summary.json $R/profiles/${TAG}_${c}_summary.json
 cp $R/gpurun_out/prof_${TAG}_$c/partial_all_kernel_stats.csv $R/profiles/${TAG}_${c}_kernel_stats.csv
 cd $R
-timeout -k 10 900 python -u bench.py --config $CFG $EXTRA > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -20 $OUT/bench_$c.err; exit 1; }
+timeout -k 10 900 python -u bench.py --full --config $CFG $EXTRA > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -20 $OUT/bench_$c.err; exit 1; }
 cat $OUT/bench_$c.json

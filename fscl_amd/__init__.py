@@ -25,7 +25,8 @@ __all__ = [
     "load_snp_input", "load_ms_input", "background_fsp", "compute_sweep_model_tables", "compute_snp_null_model",
     "init_log_table", "scan_chromosome", "scan_permute", "scan_output", "output_background_fs", "points",
     "get_stats", "reset_stats", "set_device", "set_devices", "set_ranks", "set_ranks_shm", "srand", "shutdown", "run",
-    "device_count", "set_dump_output",
+    "device_count", "set_dump_output", "ProfileT", "RunT", "PointT", "scan_profile", "profile_cell_max", "profile_grid",
+    "profile_runs", "profile_output", "profile_last_ms", "profile_chunk",
 ]
 
 ROOT = Path(__file__).resolve().parent
@@ -92,6 +93,21 @@ class Stats(C.Structure):  # fscl_amd_stats_t
         return {k: (list(v) if isinstance(v, C.Array) else v) for k, v in ((k, getattr(self, k)) for k, _ in self._fields_)}
 
 
+class ProfileT(C.Structure):  # fscl_amd_profile_t
+    _fields_ = [("n_pts", C.c_int), ("pts", C.POINTER(ScanPtT)), ("grid_pos", C.POINTER(C.c_int)),
+                ("cell", C.POINTER(C.c_int))]
+
+
+class RunT(C.Structure):  # fsclg_run_t
+    _fields_ = [("chr", C.c_int32), ("start_pos", C.c_int32), ("step", C.c_int32), ("count", C.c_int32)]
+
+
+class PointT(C.Structure):  # fsclg_point_t
+    _fields_ = [("chr", C.c_int32), ("nearest_snp", C.c_int32), ("sweep_pos", C.c_int32), ("n_snps", C.c_int32),
+                ("window_start", C.c_int32), ("window_end", C.c_int32), ("flags", C.c_int32), ("cost", C.c_uint32),
+                ("lalpha", C.c_double), ("null_logl", C.c_double), ("sm_logl", C.c_double), ("clr", C.c_double)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_void_p)
 
 # exported symbols of include/fscl_amd.h and include/fsclg.h (checked by tests)
@@ -110,6 +126,9 @@ EXPORTS = [
     "fsclg_row_buffer", "fsclg_slot_row_buffer", "fsclg_slot_set_rows", "fsclg_search_submit", "fsclg_search_wait",
     "fsclg_slot_windows", "ms_openfile", "ms_background", "ms_next_block",
     "fscl_amd_set_permute_mode",
+    "fsclg_profile", "fsclg_profile_submit", "fsclg_profile_wait", "fsclg_profile_chunk", "fsclg_profile_last_ms",
+    "fscl_amd_scan_profile", "fscl_amd_profile_cell_max", "fscl_amd_profile_output", "fscl_amd_profile_free",
+    "fscl_amd_profile_grid", "fscl_amd_profile_runs", "fscl_amd_profile_last_ms",
 ]
 
 
@@ -157,6 +176,14 @@ def _load() -> C.CDLL:
         "fsclg_device_count": (C.c_int, []),
         "fsclg_last_error": (C.c_char_p, []),
         "fsclg_interval_thresholds": (C.c_int, [C.c_double, C.c_int, P(C.c_double)]),
+        "fsclg_profile_chunk": (C.c_int, []),
+        "fscl_amd_scan_profile": (P(ProfileT), [P(ScanT), P(SmPtableT), C.c_int, C.c_int, C.c_int]),
+        "fscl_amd_profile_cell_max": (C.c_int, [P(ProfileT), P(ScanT), P(ScanPtT), P(C.c_int)]),
+        "fscl_amd_profile_output": (None, [C.c_char_p, P(ScanT), P(ProfileT), C.c_char_p]),
+        "fscl_amd_profile_free": (None, [P(ProfileT)]),
+        "fscl_amd_profile_grid": (C.c_int, [P(ScanT), C.c_int, C.c_int, P(P(C.c_int)), P(P(C.c_int)), P(P(C.c_int))]),
+        "fscl_amd_profile_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(RunT), C.c_int, C.c_int, P(PointT)]),
+        "fscl_amd_profile_last_ms": (C.c_double, []),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -276,6 +303,123 @@ def points(scan) -> np.ndarray:
     return out
 
 
+PROFILE_DTYPE = np.dtype(POINT_DTYPE.descr + [("grid_pos", "i4"), ("cell", "i4")])
+
+
+# the C layouts of scan_pt_t and fsclg_point_t (the pointer as an integer)
+_SCANPT_RAW = np.dtype([("chr", "i4"), ("nearest_snp", "i4"), ("sweep_pos", "i4"), ("n_snps", "i4"),
+                        ("window_start", "i4"), ("window_end", "i4"), ("lalpha", "f8"), ("null_logl", "f8"),
+                        ("sm_logl", "f8"), ("clr", "f8"), ("permute_n", "i4"), ("permute_p", "i4"),
+                        ("permute_finished", "i4"), ("scan_running", "i4"), ("permute_clr", "u8")])
+_POINT_RAW = np.dtype([("chr", "i4"), ("nearest_snp", "i4"), ("sweep_pos", "i4"), ("n_snps", "i4"),
+                       ("window_start", "i4"), ("window_end", "i4"), ("flags", "i4"), ("cost", "u4"),
+                       ("lalpha", "f8"), ("null_logl", "f8"), ("sm_logl", "f8"), ("clr", "f8")])
+assert _SCANPT_RAW.itemsize == C.sizeof(ScanPtT) and _POINT_RAW.itemsize == C.sizeof(PointT)
+
+
+def _pts_array(pts, n, dtype=POINT_DTYPE) -> np.ndarray:
+    """n structs (ScanPtT or PointT) at `pts` as a structured array of `dtype`'s point fields."""
+    out = np.zeros(n, dtype=dtype)
+    if n:
+        ct = pts._type_
+        raw = np.frombuffer((ct * n).from_address(C.addressof(pts.contents) if hasattr(pts, "contents")
+                                                  else C.addressof(pts)),
+                            dtype=_SCANPT_RAW if ct is ScanPtT else _POINT_RAW)
+        have = set(raw.dtype.names)
+        for k in POINT_DTYPE.names:
+            if k in have:
+                out[k] = raw[k]
+    return out
+
+
+def _libc_free(*ptrs) -> None:
+    free = C.CDLL(None).free
+    free.argtypes = [C.c_void_p]
+    for p in ptrs:
+        free(C.cast(p, C.c_void_p))
+
+
+def profile_chunk() -> int:
+    """Positions per workgroup of the profile kernel ($FSCLG_PROFILE_CHUNK, read per call)."""
+    return int(get_lib().fsclg_profile_chunk())
+
+
+def profile_last_ms() -> float:
+    return float(get_lib().fscl_amd_profile_last_ms())
+
+
+def profile_grid(scan, small_grid_sp: int = 1000, large_grid_sp: int = 100000):
+    """The fine grid alone (no GPU): (chr, grid_pos, cell) int32 arrays."""
+    pc, pp, pe = C.POINTER(C.c_int)(), C.POINTER(C.c_int)(), C.POINTER(C.c_int)()
+    n = get_lib().fscl_amd_profile_grid(scan, int(small_grid_sp), int(large_grid_sp), C.byref(pc), C.byref(pp),
+                                        C.byref(pe))
+    if n < 0:
+        raise ValueError("small_grid_sp must be positive and divide large_grid_sp")
+    out = tuple(np.array(a[:n], dtype=np.int32) for a in (pc, pp, pe))
+    _libc_free(pc, pp, pe)
+    return out
+
+
+def profile_runs(scan, tables, runs, eval_range: int = 81920) -> np.ndarray:
+    """init_scan_result + search_maxalpha at start + k * step, k < count, for each
+    (chr, start, step, count) of ``runs``: a POINT_DTYPE array in run order."""
+    arr = (RunT * max(len(runs), 1))(*[RunT(*[int(v) for v in r]) for r in runs])
+    n = sum(max(int(r[3]), 0) for r in runs)
+    out = (PointT * max(n, 1))()
+    r = get_lib().fscl_amd_profile_runs(scan, tables, arr, len(runs), int(eval_range), out)
+    if r != 0:
+        raise RuntimeError(f"fscl_amd_profile_runs: code {r}: {get_lib().fsclg_last_error().decode()}")
+    return _pts_array(out, n)
+
+
+def scan_profile(scan, tables, eval_range: int = 81920, small_grid_sp: int = 1000,
+                 large_grid_sp: int = 100000) -> np.ndarray:
+    """CLR and alpha at every small_grid_sp-spaced position (include/fscl_amd.h): points()'s
+    fields plus grid_pos (the requested position) and cell (its coarse cell)."""
+    pf = get_lib().fscl_amd_scan_profile(scan, tables, int(eval_range), int(small_grid_sp), int(large_grid_sp))
+    if not pf:
+        return np.zeros(0, dtype=PROFILE_DTYPE)
+    n = pf.contents.n_pts
+    out = _pts_array(pf.contents.pts, n, PROFILE_DTYPE)
+    out["grid_pos"] = np.array(pf.contents.grid_pos[:n], dtype=np.int32)
+    out["cell"] = np.array(pf.contents.cell[:n], dtype=np.int32)
+    get_lib().fscl_amd_profile_free(pf)
+    return out
+
+
+def _profile_struct(profile: np.ndarray):
+    n = len(profile)
+    pts = np.zeros(max(n, 1), dtype=_SCANPT_RAW)
+    for k in POINT_DTYPE.names:
+        pts[k][:n] = profile[k]
+    gp = np.ascontiguousarray(np.resize(profile["grid_pos"], max(n, 1)) if n else np.zeros(1), dtype=np.int32)
+    ce = np.ascontiguousarray(np.resize(profile["cell"], max(n, 1)) if n else np.zeros(1), dtype=np.int32)
+    pf = ProfileT(n, pts.ctypes.data_as(C.POINTER(ScanPtT)), gp.ctypes.data_as(C.POINTER(C.c_int)),
+                  ce.ctypes.data_as(C.POINTER(C.c_int)))
+    return pf, (pts, gp, ce)
+
+
+def profile_cell_max(profile: np.ndarray, scan):
+    """Per coarse cell the first grid point of strictly greatest CLR, and the number of cells
+    whose grid maximum exceeds the scan's (bisection's) point: (POINT_DTYPE array, n_missed).
+    Needs scan_chromosome to have run (ValueError otherwise)."""
+    pf, keep = _profile_struct(profile)
+    n_cells = scan.contents.n_scan_pts
+    out = (ScanPtT * max(n_cells, 1))()
+    missed = C.c_int(0)
+    r = get_lib().fscl_amd_profile_cell_max(C.byref(pf), scan, out, C.byref(missed))
+    del keep
+    if r < 0:
+        raise ValueError("profile_cell_max needs scan_chromosome's points")
+    return _pts_array(out, r), missed.value
+
+
+def profile_output(path, scan, profile: np.ndarray, label=None) -> None:
+    pf, keep = _profile_struct(profile)
+    get_lib().fscl_amd_profile_output(_b(path), scan, C.byref(pf), _b(label))
+    del keep
+
+
 def get_stats() -> dict:
     st = Stats()
     get_lib().fscl_amd_get_stats(C.byref(st))
@@ -359,7 +503,8 @@ def shutdown() -> None:
 def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_folded=False, n_permute=0,
         permute_nbp=0.1, asc_depth=0, asc_min_freq=1, ascbias_background_only=False, include_invariant=False,
         force_neutral=False, minimum_depth=5, large_grid_sp=100000, scan_width_mb=1.0, max_only=False,
-        label=None, eval_range=81920, bp_resl=128, verbosity=1, permute_mode="parity", permute_seed=0xFD821A6):
+        label=None, eval_range=81920, bp_resl=128, verbosity=1, permute_mode="parity", permute_seed=0xFD821A6,
+        profile_file=None, small_grid_sp=1000):
     """The fscl main() pipeline (fscl.c:316-337) in-process; returns the scan_t
     pointer (points(scan) reads the results).  permute_mode "throughput": the
     counter-based permutation test (set_permute_mode)."""
@@ -375,6 +520,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
                                      include_invariant)
     compute_snp_null_model(scan, fsp)
     scan_chromosome(scan, tab, eval_range, bp_resl, large_grid_sp)
+    if profile_file is not None:  # the CLI's --profile-file: the -g spaced likelihood profile
+        profile_output(profile_file, scan, scan_profile(scan, tab, eval_range, small_grid_sp, large_grid_sp), label)
     if n_permute > 0:
         scan_permute(scan, tab, n_permute, permute_nbp, 1.0, 1, eval_range, bp_resl, large_grid_sp, scan_width_mb)
     if output is not None:

@@ -2346,6 +2346,74 @@ search_maxpos_split_kernel(Params P) {
   maxpos_body<LDS, true>(S, P);
 }
 
+// ------------------------------------------------------------ likelihood profile
+// A dense run of positions (fsclg_profile): one workgroup takes a chunk of consecutive positions
+// of one run, pays the LDS prologue (thresholds, null rows, coefficient window, log-table slice)
+// once, and evaluates the chunk two positions per alpha search -- init_scan_result by waves 0
+// and 1, then the search of both points together, as a cell's two end points.  The exact-sum
+// machinery (eval_walks, resolve_walk, the slow-path settle) is search_maxalpha_pts's, unchanged.
+struct ProfChunk {
+  int32_t chr, start_pos, step, count;  // positions start_pos + k * step, k < count
+  int32_t out0, pad[3];                 // the chunk's first point in Params::out
+};
+
+template <bool LDS, class SM>
+__device__ __forceinline__ void profile_body(SM& S, const Params& P, const ProfChunk* __restrict__ chunks) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int k = (int)blockIdx.x;
+  if (k >= P.n_cells) return;
+  if (tid < 8) S.cnt[tid] = 0;
+  if (tid < 5) S.tph[tid] = 0;
+  if (tid == 0) { S.cell = k; S.member = 0; S.inst = 0; S.xfail = 0; S.iev = 0; }
+  if constexpr (LDS) {
+    double* thr = reinterpret_cast<double*>(fsclg_dyn + P.off_thr);
+    double* nul = reinterpret_cast<double*>(fsclg_dyn + P.off_nul);
+    for (int j = tid; j <= P.n_iv; j += WG) thr[j] = P.thr[j];
+    for (int j = tid; j <= P.n_rows; j += WG) nul[j] = P.nullrow[j];  // + sentinel
+    load_window(S, P, P.ivc0);
+    double* lt2 = reinterpret_cast<double*>(fsclg_dyn + P.off_lt);
+    for (int j = 256 + tid; j < P.lt_hi; j += WG) lt2[j] = P.logt3[2 * 0x10000 + j];
+#if FSCLG_LOG_CALC
+    if (lx_kernel<SM>() && P.lx_on) {
+      double* lx = reinterpret_cast<double*>(fsclg_dyn + P.off_lx);
+      for (int j = tid; j < LX_BYTES / 8; j += WG) lx[j] = P.lx[j];
+    }
+#endif
+  } else if (tid == 0) S.ivc0 = 0;
+  __syncthreads();
+  const ProfChunk c = chunks[k];
+  for (int i = 0; i < c.count; i += 2) {
+    const int np = min(2, c.count - i);  // an odd chunk's last search takes one position
+    if (wave < np) init_point_wave(S.pt[wave], c.chr, c.start_pos + (i + wave) * c.step, P, lane);
+    __syncthreads();
+    if (tid == 0) for (int q = 0; q < np; q++) S.cnt[1] += (unsigned long long)S.pt[q].n_snps;
+    search_maxalpha_pts<LDS>(S, P, 0, np);  // (ends with a barrier: the points are final)
+    if (tid < np) {  // one store per point (P.out is host memory: no read-modify-write)
+      fsclg_point_t o;
+      write_point(o, S.pt[tid]);
+      o.cost = (uint32_t)min(S.cnt[0] >> 10, 0xFFFFFFFFull);  // the chunk's terms up to this search
+      P.out[c.out0 + i + tid] = o;
+    }
+    __syncthreads();  // the next pair's init_scan_result rewrites S.pt[0..1]
+  }
+  if (tid < 8 && S.cnt[tid]) atomicAdd(&P.stats[tid], S.cnt[tid]);
+}
+
+// waves_per_eu 3: one 768-thread workgroup per CU (3 waves per SIMD), so that the compiler may
+// take up to 168 VGPRs and the kernel keeps everything in registers (no spill, no scratch:
+// profiles/profile_kernel_resources.txt).  At 6 (two workgroups per CU, 80 VGPRs, as the throughput
+// kernel) the shared search code spills 27 VGPRs; the two were measured against each other
+// (HISTORY.md, "profile kernel"; -DFSCLG_WPE_PROFILE=6 builds the other one)
+#ifndef FSCLG_WPE_PROFILE
+#define FSCLG_WPE_PROFILE 3
+#endif
+template <bool LDS>
+__global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(FSCLG_WPE_PROFILE, FSCLG_WPE_PROFILE)))
+profile_kernel(Params P, const ProfChunk* __restrict__ chunks) {
+  __shared__ Smem S;
+  profile_body<LDS>(S, P, chunks);
+}
+
 // ------------------------------------------------------------ window null sums
 // init_scan_result's window sum (scan-chromosome.c:92-94) for every window start of the
 // chromosomes longer than the window: acc = 0.0; acc += null_logl[i] for i = ws..ws+W-1,
@@ -3005,6 +3073,11 @@ struct fsclg_ctx {
   int ci_guess = 5;                       // of split cells' speculative refine walks (Params::ci_guess)
   double kernel_ms = 0.0;
   unsigned long long launches = 0;
+  ProfChunk* p_pchunks = nullptr;  // fsclg_profile: the launch's chunks (pinned, read by the kernel)
+  int pchunk_cap = 0;
+  int prof_n = 0;                  // points of the submitted profile (batch 0 pending)
+  bool prof_pending = false;
+  double prof_ms = 0.0;            // kernel time of the last profile (fsclg_profile_last_ms)
   std::vector<std::pair<double, double>> busy;  // [start, end) ms of each batch's kernels since ev_ref
 };
 
@@ -3122,6 +3195,7 @@ int fsclg_close(fsclg_ctx* c) {
                   c->d_chr_start, c->d_chr_n, c->d_wtasks, c->d_la_coarse, c->d_la_refine, c->d_n_refine,
                   c->d_stats, c->d_dfail, c->d_dband, c->d_tpos, c->d_plan_tmp, c->d_lx};
   for (void* p : ptrs) if (p) hipFree(p);
+  if (c->p_pchunks) hipHostFree(c->p_pchunks);
   for (Slot& S : c->slot) {
     for (void* p : {(void*)S.d_pr, (void*)S.d_chr_null, (void*)S.d_win_null, (void*)S.d_ctab, (void*)S.d_ctree})
       if (p) hipFree(p);
@@ -4608,6 +4682,134 @@ int fsclg_search_points(fsclg_ctx* c, fsclg_point_t* pts, int n_pts) {
   c->busy.emplace_back((double)t0, (double)t1);
   return FSCLG_OK;
 }
+
+// Chunk length of the profile kernel: positions per workgroup, i.e. per LDS prologue
+// ($FSCLG_PROFILE_CHUNK, read per call).  Default 16: 8, 16 and 32 measured within 1.3 % of each
+// other at C4 and C2 (HISTORY.md, "profile kernel"), so the prologue is already amortised at 8;
+// 16 halves the workgroups of 8 and leaves a C2 profile 12 500 of them to balance
+#ifndef FSCLG_PROFILE_CHUNK
+#define FSCLG_PROFILE_CHUNK 16
+#endif
+int fsclg_profile_chunk(void) {
+  const char* e = getenv("FSCLG_PROFILE_CHUNK");
+  const int v = e ? atoi(e) : FSCLG_PROFILE_CHUNK;
+  return v < 1 ? 1 : (v > 4096 ? 4096 : v);
+}
+
+int fsclg_profile_submit(fsclg_ctx* c, const fsclg_run_t* runs, int n_runs, int eval_range) {
+  if (!c || (!runs && n_runs) || n_runs < 0 || eval_range < 0) return set_err(FSCLG_E_ARG, "runs");
+  if (!c->d_pr0 || !c->d_coef || !c->d_la_coarse) return set_err(FSCLG_E_STATE, "tables/snps/alpha grid not set");
+  Batch& B = c->batch[0];
+  if (B.pending) return set_err(FSCLG_E_STATE, "batch 0 not waited for");
+  const int CH = fsclg_profile_chunk();
+  long long total = 0, nchunk = 0;
+  for (int i = 0; i < n_runs; i++) {
+    const fsclg_run_t& r = runs[i];
+    if (r.step < 1 || r.count < 0) return set_err(FSCLG_E_ARG, "run step/count");
+    if (r.chr < 0 || r.chr >= c->n_chr) return set_err(FSCLG_E_ARG, "run chromosome");
+    // (the last position + 64: init_scan_result's de-collision may move a point past it)
+    if (r.count > 0 && (long long)r.start_pos + (long long)(r.count - 1) * r.step > 0x7FFFFFFFll - 64)
+      return set_err(FSCLG_E_ARG, "run position overflow");
+    const long long nwin = std::min((long long)c->h_chr_n[r.chr], 2ll * eval_range + 1);
+    if (nwin / SEG_SPLIT + 4 > (long long)MAXSEG_W) return set_err(FSCLG_E_UNSUPPORTED, "window above the segment table");
+    total += r.count;
+    nchunk += (r.count + CH - 1) / CH;
+  }
+  if (total > 0x7FFFFFFFll / (long long)sizeof(fsclg_point_t)) return set_err(FSCLG_E_ARG, "too many profile points");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  c->prof_n = (int)total; c->prof_ms = 0.0;
+  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = 0; B.ivhist = nullptr; B.traced = false;
+  int r;
+  if (total > 0) {
+    // the profile is of the data as uploaded: the unpermuted rows into slot 0 (its whole-chromosome
+    // null sums are the caller's, fsclg_set_chr_null, as for fsclg_search_maxpos)
+    if ((r = fsclg_slot_set_rows(c, 0, nullptr, nullptr))) return r;
+    {  // the window null sums of every window the runs' positions touch: one covering cell per run
+      std::vector<fsclg_cell_t> cover;
+      for (int i = 0; i < n_runs; i++)
+        if (runs[i].count > 0)
+          cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos,
+                                       runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
+      if ((r = fsclg_slot_windows(c, 0, cover.data(), (int)cover.size(), eval_range))) return r;
+    }
+    if ((r = ensure_io(B, (int)total))) return r;
+    if ((r = ensure_pinned(&c->p_pchunks, &c->pchunk_cap, (int)nchunk))) return r;
+    int nc = 0, o = 0;
+    for (int i = 0; i < n_runs; i++)
+      for (int k = 0; k < runs[i].count; k += CH) {
+        const int cnt = std::min(CH, runs[i].count - k);
+        c->p_pchunks[nc++] = ProfChunk{runs[i].chr, runs[i].start_pos + k * runs[i].step, runs[i].step, cnt, o, {0, 0, 0}};
+        o += cnt;
+      }
+    HIPCHK(hipStreamWaitEvent(B.stream, c->slot[0].ready, 0), "hipStreamWaitEvent");
+    Params P = make_params(c, B, 0, nc, 3, eval_range, 0);
+    P.band_th = -1; P.ivc0 = c->c_ivc0; P.n_civ = c->c_civ;  // the walk-window path (band mode has its own kernel)
+    P.civ_max = std::max(P.n_civ - 1, 0); P.n_cache = P.n_civ * P.stride;
+    P.off_thr = P.n_cache * 32; P.off_nul = P.off_thr + (c->n_iv + 1) * 8;
+    P.off_lt = P.off_nul + (c->n_rows + 1) * 8 - 256 * 8;
+    P.off_lx = (P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0) + 15) & ~15;
+    P.ctrace = nullptr;
+    const int dyn = P.lx_on ? P.off_lx + LX_BYTES : P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0);
+    const int stat_m = (int)((sizeof(Smem) + 15) / 16 * 16);
+    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
+    if (stat_m + dyn <= LDS_WG) {
+      static unsigned long long attr_set = 0;  // per device (bit = device id)
+      if (c->device >= 64 || !(attr_set >> c->device & 1ull)) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&profile_kernel<true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WG - stat_m), "hipFuncSetAttribute");
+        if (c->device < 64) attr_set |= 1ull << c->device;
+      }
+      hipLaunchKernelGGL((profile_kernel<true>), dim3(nc), dim3(WG), dyn, B.stream, P, (const ProfChunk*)c->p_pchunks);
+    } else {  // tables too large for the LDS copies: every coefficient from the global table, as the cell path
+      hipLaunchKernelGGL((profile_kernel<false>), dim3(nc), dim3(WG), 0, B.stream, P, (const ProfChunk*)c->p_pchunks);
+    }
+    HIPCHK(hipGetLastError(), "launch profile_kernel");
+    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+  }
+  B.pending = true; c->prof_pending = true;
+  c->slot[0].users++;
+  return FSCLG_OK;
+}
+
+int fsclg_profile_wait(fsclg_ctx* c, fsclg_point_t* out) {
+  if (!c) return set_err(FSCLG_E_ARG, "context");
+  Batch& B = c->batch[0];
+  if (!B.pending || !c->prof_pending) return set_err(FSCLG_E_STATE, "no profile submitted");
+  if (!out && c->prof_n) return set_err(FSCLG_E_ARG, "out");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  B.pending = false; c->prof_pending = false;
+  c->slot[0].users--;
+  const int n = c->prof_n;
+  if (n == 0) return FSCLG_OK;
+  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  memcpy(out, B.p_out, sizeof(fsclg_point_t) * (size_t)n);
+  float ms = 0.f, t0 = 0.f, t1 = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
+  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
+  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
+  c->prof_ms = ms;
+  c->kernel_ms += ms;
+  c->launches++;
+  c->busy.emplace_back((double)t0, (double)t1);
+  note_alphas(c, out, n);
+  for (int i = 0; i < n; i++)
+    if (out[i].flags)
+      return set_err(out[i].flags & PF_UNSUPPORTED ? FSCLG_E_UNSUPPORTED : FSCLG_E_KERNEL, "device flag");
+  return FSCLG_OK;
+}
+
+int fsclg_profile(fsclg_ctx* c, const fsclg_run_t* runs, int n_runs, int eval_range, fsclg_point_t* out) {
+  if (!out && n_runs > 0) {
+    long long total = 0;
+    for (int i = 0; runs && i < n_runs; i++) total += runs[i].count > 0 ? runs[i].count : 0;
+    if (total > 0) return set_err(FSCLG_E_ARG, "out");
+  }
+  const int r = fsclg_profile_submit(c, runs, n_runs, eval_range);
+  if (r) return r;
+  return fsclg_profile_wait(c, out);
+}
+
+double fsclg_profile_last_ms(fsclg_ctx* c) { return c ? c->prof_ms : 0.0; }
 
 int fsclg_interval_thresholds(double log_ad_step, int n_iv, double* thr) {
   if (!thr || n_iv <= 0 || !(log_ad_step > 0)) return set_err(FSCLG_E_ARG, "thresholds");

@@ -55,7 +55,7 @@ int main(int argc, char **argv) {
   int small_grid_sp = 1000, large_grid_sp = 100000, dont_scan = 0, minimum_obs_depth = 5, n_threads = 1;
   int verbosity = MSG_STATUS, eval_range = 81920, bp_resl = 128, stop = 0, i, n_gpus = 0;
   double permute_nbp = 0.1, alpha_factor = 1.0, scan_width_mb = 1.0;
-  char *permute_mode = NULL, *permute_seed = NULL;
+  char *permute_mode = NULL, *permute_seed = NULL, *profile_fname = NULL;
   scan_t *s;
   double **fsp;
   opt_t opts[] = {
@@ -66,7 +66,7 @@ int main(int argc, char **argv) {
       {0, "permute-nbp", &permute_nbp, T_DBL, "probability for switching to a new snp block for permutations"},
       {0, "n-threads", &n_threads, T_INT, "accepted for compatibility (the GPU evaluates all points at once)"},
       {'a', "alpha-factor", &alpha_factor, T_DBL, "multiply 1/alpha by this factor to determine single sweep window size"},
-      {'g', "fine-grid-spacing", &small_grid_sp, T_INT, "Spacing of candidate sweep points along the chromosome (in bp)"},
+      {'g', "fine-grid-spacing", &small_grid_sp, T_INT, "Spacing in bp of the CLR profile's positions (--profile-file); must divide -G"},
       {'G', "coarse-grid-spacing", &large_grid_sp, T_INT, "Size of coarse grid in which CLR maxima will be selected"},
       {'w', "sweep-width", &scan_width_mb, T_DBL, "maximum width of sweep effect in scanning, in Mb"},
       {0, "minimum-depth", &minimum_obs_depth, T_INT, "minimum depth of sample (lower depth SNPs ignored)"},
@@ -89,6 +89,7 @@ int main(int argc, char **argv) {
       {0, "n-gpus", &n_gpus, T_INT, "GPUs to use (default: every visible GPU, or $FSCL_AMD_DEVICE alone when set)"},
       {0, "permute-mode", &permute_mode, T_STR, "parity (default: the reference's rand() stream, identical results) or "
                                                 "throughput (counter-based random numbers, trials independent; not identical)"},
+      {0, "profile-file", &profile_fname, T_STR, "write CLR and alpha at every -g spaced position (the likelihood profile) to this file"},
       {0, "permute-seed", &permute_seed, T_STR, "seed of the throughput mode's random numbers (default 0xFD821A6)"},
       {0, NULL, NULL, 0, NULL}};
 
@@ -164,10 +165,12 @@ int main(int argc, char **argv) {
     logmsg(MSG_ERROR, "Error: specify sweep position grid spacing with -g option (in bp).\n");
     stop = 1;
   }
-  if (!output_bs_fname && small_grid_sp > 0 && large_grid_sp % small_grid_sp != 0) {
+  if ((profile_fname || !output_bs_fname) && small_grid_sp > 0 && large_grid_sp > 0 && large_grid_sp % small_grid_sp != 0) {
     logmsg(MSG_ERROR, "Error: fine grid spacing must evenly divide coarse grid spacing.\n");
     stop = 1;
   }
+  if (profile_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --profile-file needs the scan (not with --no-scan).\n"); stop = 1; }
+  if (profile_fname && small_grid_sp < 1) { logmsg(MSG_ERROR, "Error: --profile-file needs a positive -g spacing.\n"); stop = 1; }
   if (large_grid_sp < 1) { logmsg(MSG_ERROR, "Error: coarse grid spacing must be positive.\n"); stop = 1; }
   if (n_gpus < 0) { logmsg(MSG_ERROR, "Error: --n-gpus must be >= 0.\n"); stop = 1; }
   if (permute_mode && strcmp(permute_mode, "parity") && strcmp(permute_mode, "throughput")) {
@@ -217,6 +220,17 @@ int main(int argc, char **argv) {
     sm = compute_sweep_model_tables(s, fsp, asc_depth, asc_min_freq, bg_only, include_invariant);
     compute_snp_null_model(s, fsp);
     scan_chromosome(s, sm, eval_range, bp_resl, large_grid_sp, n_threads);
+    if (profile_fname) { /* the likelihood profile at -g spacing, of the data as loaded (rank 0 alone) */
+      fscl_amd_profile_t *pf = fscl_amd_scan_profile(s, sm, eval_range, small_grid_sp, large_grid_sp);
+      if (pf) {
+        int n_missed = 0;
+        fscl_amd_profile_cell_max(pf, s, NULL, &n_missed);
+        fscl_amd_profile_output(profile_fname, s, pf, prepend_label);
+        logmsg(MSG_STATUS, "Profile: %d grid points at %d bp, kernel %.3f ms, %d of %d cells have a grid point above the bisection's maximum\n",
+               pf->n_pts, small_grid_sp, fscl_amd_profile_last_ms(), n_missed, s->n_scan_pts);
+        fscl_amd_profile_free(pf);
+      }
+    }
     if (n_permute > 0)
       scan_permute(s, sm, n_permute, permute_nbp, alpha_factor, n_threads, eval_range, bp_resl, large_grid_sp,
                    scan_width_mb);

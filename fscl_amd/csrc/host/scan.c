@@ -695,17 +695,10 @@ static void set_original_rows(void) {
   free(nul);
 }
 
-/* scan-chromosome.c:228-265 */
-void scan_chromosome(scan_t *s, sm_ptable_t *sm, int eval_range, int bp_resl, int large_grid_sp, int n_threads) {
-  fsclg_cell_t *cells;
-  fsclg_point_t *out;
-  keyed_pt_t *kp;
-  int n = 0, cap = 1024, chm = 0, pos, i;
-  double t0 = fh_now();
-  (void)n_threads; /* the GPUs evaluate every cell concurrently */
-  prepare(s, sm);
-  /* the cell sequence one scan_thread walks (scan-chromosome.c:176-212) */
-  cells = fh_malloc(sizeof(fsclg_cell_t) * cap, "cells");
+/* the cell sequence one scan_thread walks (scan-chromosome.c:176-212) */
+static fsclg_cell_t *scan_cells(const scan_t *s, int large_grid_sp, int *n_out) {
+  int n = 0, cap = 1024, chm = 0, pos;
+  fsclg_cell_t *cells = fh_malloc(sizeof(fsclg_cell_t) * cap, "cells");
   if (s->n_chromosomes > 0) {
     pos = s->chr_limits[0].start_pos;
     for (;;) {
@@ -723,6 +716,20 @@ void scan_chromosome(scan_t *s, sm_ptable_t *sm, int eval_range, int bp_resl, in
       pos += large_grid_sp;
     }
   }
+  *n_out = n;
+  return cells;
+}
+
+/* scan-chromosome.c:228-265 */
+void scan_chromosome(scan_t *s, sm_ptable_t *sm, int eval_range, int bp_resl, int large_grid_sp, int n_threads) {
+  fsclg_cell_t *cells;
+  fsclg_point_t *out;
+  keyed_pt_t *kp;
+  int n = 0, i;
+  double t0 = fh_now();
+  (void)n_threads; /* the GPUs evaluate every cell concurrently */
+  prepare(s, sm);
+  cells = scan_cells(s, large_grid_sp, &n);
   set_original_rows();
   out = fh_malloc(sizeof(fsclg_point_t) * (n ? n : 1), "points");
   eval_cells(cells, n, eval_range, bp_resl, out);
@@ -2271,6 +2278,196 @@ void search_maxalpha(scan_pt_t *pt, snp_t *snps, sm_ptable_t *sm) {
   pthread_mutex_lock(&g_dropin_mu);
   search_maxalpha_locked(pt, snps, sm);
   pthread_mutex_unlock(&g_dropin_mu);
+}
+
+/* --------------------------------------------------------------- profile */
+/* The fine grid (-g) of the reference's disabled loops (scan-chromosome.c:269-327): every
+   small_grid_sp-spaced position of each chromosome over the extent its coarse cells cover, and
+   the cell of each position.  Host only: no device is touched. */
+int fscl_amd_profile_grid(const scan_t *s, int small_grid_sp, int large_grid_sp, int **chr_out, int **pos_out,
+                          int **cell_out) {
+  fsclg_cell_t *cells;
+  int n_cells = 0, n = 0, cap = 1024, a, b;
+  int *gc, *gp, *ge;
+  if (chr_out) *chr_out = NULL;
+  if (pos_out) *pos_out = NULL;
+  if (cell_out) *cell_out = NULL;
+  if (!s || small_grid_sp < 1 || large_grid_sp < 1 || large_grid_sp % small_grid_sp != 0) return -1;
+  cells = scan_cells(s, large_grid_sp, &n_cells);
+  gc = fh_malloc(sizeof(int) * cap, "grid"); gp = fh_malloc(sizeof(int) * cap, "grid"); ge = fh_malloc(sizeof(int) * cap, "grid");
+  for (a = 0; a < n_cells; a = b) { /* cells [a, b): one chromosome's */
+    const int start = cells[a].start_pos;
+    long long p;
+    int end, k = a;
+    for (b = a + 1; b < n_cells && cells[b].chr == cells[a].chr; b++) {}
+    end = cells[b - 1].end_pos; /* the last cell's (clipped) end */
+    for (p = start; p <= end; p += p + small_grid_sp <= end || p == end ? small_grid_sp : end - p) {
+      /* the cell whose [start, end] holds p; a shared boundary belongs to the lower cell */
+      while (k < b - 1 && p > cells[k].end_pos) k++;
+      if (n == cap) {
+        cap *= 2;
+        gc = fh_realloc(gc, sizeof(int) * cap, "grid"); gp = fh_realloc(gp, sizeof(int) * cap, "grid");
+        ge = fh_realloc(ge, sizeof(int) * cap, "grid");
+      }
+      gc[n] = cells[a].chr; gp[n] = (int)p; ge[n] = k;
+      n++;
+    }
+  }
+  free(cells);
+  if (chr_out) *chr_out = gc; else free(gc);
+  if (pos_out) *pos_out = gp; else free(gp);
+  if (cell_out) *cell_out = ge; else free(ge);
+  return n;
+}
+
+static double g_profile_ms;
+double fscl_amd_profile_last_ms(void) { return g_profile_ms; }
+
+/* init_scan_result + search_maxalpha at every position of the runs, on the data as loaded.  One
+   device takes the runs as they are (fsclg_profile cuts them into the kernel's chunks).  Several
+   devices: the chunks are dealt in contiguous cost-balanced shares (fscl_amd_partition's rule;
+   cost: window size x positions), and each device gets its share as runs again -- a run the
+   share boundary falls in is split there, at a chunk boundary -- so the chunks, and with them
+   every point, are those of one device */
+int fscl_amd_profile_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int n_runs, int eval_range,
+                          fsclg_point_t *out) {
+  const int CH = fsclg_profile_chunk();
+  fsclg_run_t *dr;
+  double *cost;
+  int *crun;
+  long long *coff;
+  int lo[FH_MAX_DEV], hi[FH_MAX_DEV];
+  int i, k, l, n = 0, cap = 0, r = FSCLG_OK;
+  if (!s || !sm || (!runs && n_runs) || n_runs < 0) return FSCLG_E_ARG;
+  prepare(s, sm);
+  for (i = 0; i < n_runs; i++) {
+    if (runs[i].step < 1 || runs[i].count < 0 || runs[i].chr < 0 || runs[i].chr >= D.n_chr) return FSCLG_E_ARG;
+    cap += (runs[i].count + CH - 1) / CH;
+  }
+  set_original_rows();
+  g_profile_ms = 0.;
+  if (D.n_dev <= 1) {
+    r = fsclg_profile(D.ctx[0], runs, n_runs, eval_range, out);
+    g_profile_ms = fsclg_profile_last_ms(D.ctx[0]);
+    return r;
+  }
+  cost = fh_malloc(sizeof(double) * (cap ? cap : 1), "profile chunks");
+  crun = fh_malloc(sizeof(int) * (cap ? cap : 1), "profile chunks");           /* the chunk's run */
+  coff = fh_malloc(sizeof(long long) * ((size_t)cap + 1), "profile chunks");  /* its first point in out */
+  coff[0] = 0;
+  for (i = 0; i < n_runs; i++)
+    for (k = 0; k < runs[i].count; k += CH) {
+      const int cnt = runs[i].count - k < CH ? runs[i].count - k : CH;
+      cost[n] = window_cost(runs[i].chr, eval_range) * cnt;
+      crun[n] = i;
+      coff[n + 1] = coff[n] + cnt;
+      n++;
+    }
+  dr = fh_malloc(sizeof(fsclg_run_t) * ((size_t)n_runs + 2), "profile runs");
+  for (l = 0; l < D.n_dev; l++) fscl_amd_partition(cost, n, l, D.n_dev, &lo[l], &hi[l]);
+  for (l = 0; l < D.n_dev && r == FSCLG_OK; l++) {
+    int nr = 0, c0;
+    for (c0 = lo[l]; c0 < hi[l];) { /* chunks [c0, c1) of one run */
+      const fsclg_run_t *q = runs + crun[c0];
+      long long first = coff[c0], run0 = first; /* the run's first point: back to its first chunk */
+      int c1 = c0, cb = c0;
+      while (cb > 0 && crun[cb - 1] == crun[c0]) cb--;
+      run0 = coff[cb];
+      while (c1 < hi[l] && crun[c1] == crun[c0]) c1++;
+      dr[nr].chr = q->chr; dr[nr].step = q->step;
+      dr[nr].start_pos = (int)(q->start_pos + (first - run0) * q->step);
+      dr[nr].count = (int)(coff[c1] - first);
+      nr++;
+      c0 = c1;
+    }
+    DBG("profile: device %d, chunks [%d, %d) as %d runs\n", D.dev[l], lo[l], hi[l], nr);
+    r = fsclg_profile_submit(D.ctx[l], dr, nr, eval_range); /* (the runs are copied) */
+  }
+  for (k = 0; k < l; k++) {
+    const int rw = fsclg_profile_wait(D.ctx[k], out + coff[lo[k] < n ? lo[k] : n]);
+    const double ms = fsclg_profile_last_ms(D.ctx[k]);
+    if (r == FSCLG_OK) r = rw;
+    if (ms > g_profile_ms) g_profile_ms = ms; /* the devices run side by side */
+  }
+  free(dr); free(cost); free(crun); free(coff);
+  return r;
+}
+
+fscl_amd_profile_t *fscl_amd_scan_profile(scan_t *s, sm_ptable_t *sm, int eval_range, int small_grid_sp,
+                                          int large_grid_sp) {
+  fscl_amd_profile_t *pf;
+  fsclg_run_t *runs;
+  fsclg_point_t *out;
+  int *gc = NULL, n, i, a, nr = 0, r;
+  if (D.world > 1 && D.rank != 0) return NULL; /* rank 0 alone evaluates and writes the profile */
+  pf = fh_calloc(1, sizeof *pf, "profile");
+  n = fscl_amd_profile_grid(s, small_grid_sp, large_grid_sp, &gc, &pf->grid_pos, &pf->cell);
+  if (n < 0) logmsg(MSG_FATAL, "fscl_amd: profile: fine grid spacing %d must be positive and divide the coarse grid spacing %d",
+                    small_grid_sp, large_grid_sp);
+  pf->n_pts = n;
+  /* maximal runs of equal step within a chromosome (the appended last point is a run of its own) */
+  runs = fh_malloc(sizeof(fsclg_run_t) * (n ? n : 1), "profile runs");
+  for (a = 0; a < n; a = i) {
+    for (i = a + 1; i < n && gc[i] == gc[a] && pf->grid_pos[i] - pf->grid_pos[i - 1] == small_grid_sp; i++) {}
+    runs[nr].chr = gc[a]; runs[nr].start_pos = pf->grid_pos[a]; runs[nr].step = small_grid_sp; runs[nr].count = i - a;
+    nr++;
+  }
+  out = fh_malloc(sizeof(fsclg_point_t) * (n ? n : 1), "profile points");
+  r = fscl_amd_profile_runs(s, sm, runs, nr, eval_range, out);
+  dev_check(r, "profile");
+  pf->pts = fh_malloc(sizeof(scan_pt_t) * (n ? n : 1), "profile points");
+  for (i = 0; i < n; i++) to_scan_pt(pf->pts + i, out + i);
+  free(out); free(runs); free(gc);
+  return pf;
+}
+
+void fscl_amd_profile_free(fscl_amd_profile_t *pf) {
+  if (!pf) return;
+  free(pf->pts); free(pf->grid_pos); free(pf->cell);
+  free(pf);
+}
+
+/* the strict maximum over the fine positions of each coarse cell, first wins
+   (scan-chromosome.c:287): cell c's points are those with cell[] == c, preceded by the
+   boundary point it shares with cell c - 1 of the same chromosome (that cell's last point) */
+int fscl_amd_profile_cell_max(const fscl_amd_profile_t *pf, const scan_t *s, scan_pt_t *out_max, int *n_missed) {
+  int i = 0, c, missed = 0;
+  if (!pf || !s || !s->scan_pts || s->n_scan_pts <= 0) return -1;
+  for (c = 0; c < s->n_scan_pts; c++) {
+    int a, b, best;
+    while (i < pf->n_pts && pf->cell[i] < c) i++;
+    a = i;
+    for (b = a; b < pf->n_pts && pf->cell[b] == c; b++) {}
+    if (out_max) memset(out_max + c, 0, sizeof *out_max);
+    if (a == b) continue;
+    if (a > 0 && pf->cell[a - 1] == c - 1 && pf->pts[a - 1].chr == pf->pts[a].chr) a--;
+    best = a;
+    for (i = a + 1; i < b; i++)
+      if (pf->pts[i].clr > pf->pts[best].clr) best = i;
+    i = b;
+    if (out_max) out_max[c] = pf->pts[best];
+    if (pf->pts[best].clr > s->scan_pts[c].clr) missed++;
+  }
+  if (n_missed) *n_missed = missed;
+  return s->n_scan_pts;
+}
+
+/* one line per grid point, scan_output's no-permutation row (scan-chromosome.c:741-745) */
+void fscl_amd_profile_output(const char *fname, const scan_t *s, const fscl_amd_profile_t *pf, const char *label) {
+  FILE *f = stdout;
+  int i;
+  if (!pf || !s) return;
+  if (fname) {
+    f = fopen(fname, "w");
+    if (!f) { fprintf(stderr, "Can't open profile file \"%s\" (%s)", fname, strerror(errno)); return; }
+  }
+  for (i = 0; i < pf->n_pts; i++) {
+    const scan_pt_t *q = pf->pts + i;
+    if (label) fprintf(f, "%s\t", label);
+    fprintf(f, "%s\t%d\t%1.2f\t%1.3e\t%d\t%d\t%d\n", s->chr_limits[q->chr].name, q->sweep_pos, q->clr, exp(q->lalpha),
+            q->n_snps, s->snps[q->window_start].pos, s->snps[q->window_end].pos);
+  }
+  if (fname) fclose(f);
 }
 
 /* ---------------------------------------------------------------- output */

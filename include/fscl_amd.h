@@ -32,6 +32,8 @@
 
 #include <stdint.h>
 
+#include "fsclg.h"  /* fsclg_run_t, fsclg_point_t (fscl_amd_profile_runs) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -246,6 +248,49 @@ typedef struct {
 } fscl_amd_stats_t;
 void fscl_amd_get_stats(fscl_amd_stats_t *st);
 void fscl_amd_reset_stats(void);
+
+/* ---- fine-grid CLR profile (-g) ------------------------------------------------
+   The reference's disabled fine-grid loops (scan-chromosome.c:269-327): CLR and alpha at every
+   small_grid_sp-spaced position, and the strict maximum over the fine positions of each coarse
+   cell.  Each chromosome's grid covers the extent scan_chromosome's cells cover: from the first
+   cell's start in steps of small_grid_sp to the last cell's (clipped) end, inclusive; an end the
+   step does not land on is appended once.  small_grid_sp must divide large_grid_sp.
+   grid_pos[i] is the requested position, pts[i] the point init_scan_result + search_maxalpha
+   give there (sweep_pos after de-collision), cell[i] the index in scan_chromosome's cell order
+   (= scan_obj->scan_pts order) of the cell whose [start, end] holds grid_pos[i]; a shared
+   boundary belongs to the lower cell.  The profile is always of the data as loaded (also after
+   scan_permute), on the device context scan_chromosome uses; with several local devices the
+   kernel's chunks are dealt in contiguous cost-balanced shares (identical results); with
+   several ranks, rank 0 alone evaluates (the others get NULL). */
+typedef struct {
+  int n_pts;
+  scan_pt_t *pts;
+  int *grid_pos;
+  int *cell;
+} fscl_amd_profile_t;
+fscl_amd_profile_t *fscl_amd_scan_profile(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, int small_grid_sp,
+                                          int large_grid_sp);
+/* per coarse cell, the first grid point of strictly greatest clr among those with
+   start <= grid_pos <= end (ascending), into out_max[n_scan_pts] (may be NULL); *n_missed: the
+   cells whose grid maximum's clr exceeds scan_obj->scan_pts[cell].clr (the bisection's answer).
+   Returns the number of cells, or -1 if scan_chromosome has not run.  scan_obj is not altered. */
+int fscl_amd_profile_cell_max(const fscl_amd_profile_t *pf, const scan_t *scan_obj, scan_pt_t *out_max,
+                              int *n_missed);
+/* one line per grid point in scan_output's no-permutation row format (fname NULL: stdout) */
+void fscl_amd_profile_output(const char *fname, const scan_t *scan_obj, const fscl_amd_profile_t *pf,
+                             const char *prepend_label);
+void fscl_amd_profile_free(fscl_amd_profile_t *pf);
+/* the grid alone (no GPU): chromosome, position and cell of every grid point, malloc'd arrays
+   (any may be NULL); returns the point count, -1 for a spacing that is not positive or does
+   not divide large_grid_sp */
+int fscl_amd_profile_grid(const scan_t *scan_obj, int small_grid_sp, int large_grid_sp, int **chr, int **grid_pos,
+                          int **cell);
+/* the evaluation alone, for any runs of positions (fsclg_profile over this process's devices):
+   out holds sum(count) points; returns a fsclg status code.  fscl_amd_profile_last_ms: the
+   profile kernel's milliseconds of the last evaluation (the slowest device's). */
+int fscl_amd_profile_runs(scan_t *scan_obj, sm_ptable_t *sm_p, const fsclg_run_t *runs, int n_runs, int eval_range,
+                          fsclg_point_t *out);
+double fscl_amd_profile_last_ms(void);
 
 /* release the device context (tables / snps) */
 void fscl_amd_shutdown(void);

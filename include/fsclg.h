@@ -208,6 +208,29 @@ int fsclg_search_maxpos(fsclg_ctx *c, const fsclg_cell_t *cells, int n_cells, in
    already set (init_scan_result done by the caller); fills lalpha/sm_logl/clr */
 int fsclg_search_points(fsclg_ctx *c, fsclg_point_t *pts, int n_pts);
 
+/* Likelihood profile: init_scan_result + search_maxalpha at every position of dense runs
+   (the reference's disabled fine-grid loop, scan-chromosome.c:269-327).  A run is the positions
+   start_pos + k * step, k < count, of one chromosome; out holds sum(count) points in run order,
+   then position order, each what init_scan_result(chr, pos) followed by search_maxalpha gives on
+   the UPLOADED rows (the call restores them into slot 0; the whole-chromosome null sums are the
+   caller's, fsclg_set_chr_null, the window null sums are summed here).  sweep_pos is the
+   position after init_scan_result's de-collision; cost is the terms / 1024 the point's chunk
+   had spent when the point was stored.  The profile kernel gives one workgroup a chunk of
+   fsclg_profile_chunk() consecutive positions of a run ($FSCLG_PROFILE_CHUNK, default 16).
+   Synchronous, on batch 0 and slot 0 like fsclg_search_points; fsclg_profile_submit /
+   fsclg_profile_wait are its two halves (several devices at once).  FSCLG_E_ARG: step < 1,
+   count < 0, a bad chr, a position past the int range; FSCLG_E_STATE: tables or SNPs not
+   uploaded, batch 0 pending.  fsclg_profile_last_ms: the profile kernel's own time (HIP
+   events) of the context's last profile; the device counters accumulate as for any launch. */
+typedef struct {
+  int32_t chr, start_pos, step, count;
+} fsclg_run_t;
+int fsclg_profile(fsclg_ctx *c, const fsclg_run_t *runs, int n_runs, int eval_range, fsclg_point_t *out);
+int fsclg_profile_submit(fsclg_ctx *c, const fsclg_run_t *runs, int n_runs, int eval_range);
+int fsclg_profile_wait(fsclg_ctx *c, fsclg_point_t *out);
+int fsclg_profile_chunk(void);
+double fsclg_profile_last_ms(fsclg_ctx *c);
+
 /* the exact interval thresholds the kernel uses in place of spline_interpolate's
    division (sm-spline.c:52): thr[j] = least double x with
    (int)((x - LOG_AD_MIN) / log_ad_step) >= j, for j = 1..n_iv (thr has n_iv+1 slots) */

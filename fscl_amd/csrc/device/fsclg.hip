@@ -653,9 +653,11 @@ __device__ __forceinline__ double exact_chunk_add(double acc, double t, int lim)
 #pragma unroll                                                  // checked by the bounds below
         for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o, 64); sn += __shfl_xor(sn, o, 64); }
         const double A0 = acc * inv;  // an integer in (-2^53, -2^52]
-        // every partial lies in [A0 + sn, A0 + sp]; inside (-2^53, -2^52] it stays in the binade
+        // every partial lies in [A0 + sn, A0 + sp]; inside (-2^53, -2^52) it stays in the binade.  The
+        // edge -2^52 itself is excluded: a positive term added to it lands above the edge, where the
+        // sum rounds on the half-unit grid (-2^52 + 0.3 -> -2^52 + 0.5, not A0 + rint(0.3))
         if (sp < 9007199254740992.0 && sn > -9007199254740992.0 && A0 + sn > -9007199254740992.0 &&
-            A0 + sp <= -4503599627370496.0)
+            A0 + sp < -4503599627370496.0)
           return (A0 + sp + sn) * u;
       }
     }
@@ -1098,10 +1100,15 @@ __device__ __forceinline__ void resolve_walk(SM& S, int w) {
       S.appr[w] = pt.N + ((double)Ssum + S.Pd[w]) * u;
       S.bnd[w] = 2.0 * (len * u + len * 4.440892098500626e-16 * smax) + 2.0 * (len + 256.0) * 2.220446049250313e-16 * qt * u +
                  1e-300;
-      // a NaN sum has a NaN term (R = rint(t/u) is finite for finite t) or both infinities
-      // among the terms: the sequential sum of sm-search.c is then NaN in any order, and a
-      // NaN never wins the strict '>' of search_maxalpha (NaN spline rows, Q15)
-      if (S.appr[w] != S.appr[w]) { S.exact[w] = 1; S.val[w] = S.appr[w]; }
+      // a NaN sum of |R| has a NaN term (|R| of any other term is finite or +inf): the sequential
+      // sum of sm-search.c is then NaN in any order, and a NaN never wins the strict '>' of
+      // search_maxalpha (NaN spline rows, Q15).  A NaN sum of R alone comes from quotients of both
+      // signs that are infinite: from infinite terms (the sequential sum is NaN too) but also from
+      // finite ones (t / u overflows for |t| near DBL_MAX, and +t then -t cancel in the sequential
+      // sum), so the value is unknown: an unbounded interval, which never raises the argmax's
+      // lower bound and always sends the walk to the slow path
+      if (qt != qt) { S.exact[w] = 1; S.val[w] = qt; }
+      else if (S.appr[w] != S.appr[w]) { S.appr[w] = 0.0; S.bnd[w] = __longlong_as_double(0x7FF0000000000000ll); }
     } else {
       const double u = pt.u, len = (double)W.len;
       const double smax = fabs(pt.N) + ((double)A + len) * u;

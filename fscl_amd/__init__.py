@@ -27,6 +27,7 @@ __all__ = [
     "get_stats", "reset_stats", "set_device", "set_devices", "set_ranks", "set_ranks_shm", "srand", "shutdown", "run",
     "device_count", "set_dump_output", "ProfileT", "RunT", "PointT", "scan_profile", "profile_cell_max", "profile_grid",
     "profile_runs", "profile_output", "profile_last_ms", "profile_chunk",
+    "scan_chromosome_grid", "scan_permute_grid", "cellmax_runs", "cellmax_last_ms", "site_rows",
 ]
 
 ROOT = Path(__file__).resolve().parent
@@ -129,6 +130,9 @@ EXPORTS = [
     "fsclg_profile", "fsclg_profile_submit", "fsclg_profile_wait", "fsclg_profile_chunk", "fsclg_profile_last_ms",
     "fscl_amd_scan_profile", "fscl_amd_profile_cell_max", "fscl_amd_profile_output", "fscl_amd_profile_free",
     "fscl_amd_profile_grid", "fscl_amd_profile_runs", "fscl_amd_profile_last_ms",
+    "fsclg_cellmax_submit", "fsclg_cellmax_wait", "fsclg_cellmax_last_ms",
+    "fscl_amd_scan_chromosome_grid", "fscl_amd_scan_permute_grid", "fscl_amd_cellmax_runs",
+    "fscl_amd_cellmax_last_ms", "fscl_amd_site_rows",
 ]
 
 
@@ -184,6 +188,12 @@ def _load() -> C.CDLL:
         "fscl_amd_profile_grid": (C.c_int, [P(ScanT), C.c_int, C.c_int, P(P(C.c_int)), P(P(C.c_int)), P(P(C.c_int))]),
         "fscl_amd_profile_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(RunT), C.c_int, C.c_int, P(PointT)]),
         "fscl_amd_profile_last_ms": (C.c_double, []),
+        "fscl_amd_scan_chromosome_grid": (None, [P(ScanT), P(SmPtableT), C.c_int, C.c_int, C.c_int]),
+        "fscl_amd_scan_permute_grid": (None, [P(ScanT), P(SmPtableT), C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                              C.c_double]),
+        "fscl_amd_cellmax_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(RunT), C.c_int, C.c_int, C.c_void_p, P(PointT)]),
+        "fscl_amd_cellmax_last_ms": (C.c_double, []),
+        "fscl_amd_site_rows": (C.c_int, [P(ScanT), P(SmPtableT), C.c_void_p]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -420,6 +430,53 @@ def profile_output(path, scan, profile: np.ndarray, label=None) -> None:
     del keep
 
 
+def scan_chromosome_grid(scan, tables, eval_range: int = 81920, small_grid_sp: int = 1000,
+                         large_grid_sp: int = 100000) -> None:
+    """scan_chromosome's grid counterpart (include/fscl_amd.h): each cell's point is the first of
+    strictly greatest CLR among its small_grid_sp-spaced positions, in cell order."""
+    get_lib().fscl_amd_scan_chromosome_grid(scan, tables, int(eval_range), int(small_grid_sp), int(large_grid_sp))
+
+
+def scan_permute_grid(scan, tables, n_permute: int, permute_nbp: float = 0.1, eval_range: int = 81920,
+                      small_grid_sp: int = 1000, large_grid_sp: int = 100000, scan_width_mb: float = 1.0) -> None:
+    """scan_permute's grid counterpart on scan_chromosome_grid's points: every trial takes each
+    active point's own cell's grid maximum on the permuted rows (one process, parity stream)."""
+    get_lib().fscl_amd_scan_permute_grid(scan, tables, int(n_permute), float(permute_nbp), int(eval_range),
+                                         int(small_grid_sp), int(large_grid_sp), float(scan_width_mb))
+
+
+def site_rows(scan, tables) -> np.ndarray:
+    """The device row of every site as uploaded (uint32): what a permutation of the sites rearranges."""
+    out = np.zeros(max(scan.contents.n_snps, 1), dtype=np.uint32)
+    n = get_lib().fscl_amd_site_rows(scan, tables, out.ctypes.data)
+    if n < 0:
+        raise RuntimeError("fscl_amd_site_rows failed")
+    return out[:n]
+
+
+def cellmax_runs(scan, tables, runs, eval_range: int = 81920, rows=None) -> np.ndarray:
+    """Per (chr, start, step, count) of ``runs`` the first position of strictly greatest CLR, through
+    fsclg_cellmax_submit / fsclg_cellmax_wait on the scan's context: one POINT_DTYPE row per run (a
+    zero-count run: a zeroed row).  ``rows``: a uint32 array of n_snps device rows (a rearrangement of
+    site_rows) set into the slot first; None: the uploaded rows."""
+    arr = (RunT * max(len(runs), 1))(*[RunT(*[int(v) for v in r]) for r in runs])
+    out = (PointT * max(len(runs), 1))()
+    rp = None
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        if len(rows) != scan.contents.n_snps:
+            raise ValueError("rows must hold one row per site")
+        rp = rows.ctypes.data
+    r = get_lib().fscl_amd_cellmax_runs(scan, tables, arr, len(runs), int(eval_range), rp, out)
+    if r != 0:
+        raise RuntimeError(f"fscl_amd_cellmax_runs: code {r}: {get_lib().fsclg_last_error().decode()}")
+    return _pts_array(out, len(runs))
+
+
+def cellmax_last_ms() -> float:
+    return float(get_lib().fscl_amd_cellmax_last_ms())
+
+
 def get_stats() -> dict:
     st = Stats()
     get_lib().fscl_amd_get_stats(C.byref(st))
@@ -504,10 +561,15 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         permute_nbp=0.1, asc_depth=0, asc_min_freq=1, ascbias_background_only=False, include_invariant=False,
         force_neutral=False, minimum_depth=5, large_grid_sp=100000, scan_width_mb=1.0, max_only=False,
         label=None, eval_range=81920, bp_resl=128, verbosity=1, permute_mode="parity", permute_seed=0xFD821A6,
-        profile_file=None, small_grid_sp=1000):
+        profile_file=None, small_grid_sp=1000, scan_mode="bisection"):
     """The fscl main() pipeline (fscl.c:316-337) in-process; returns the scan_t
     pointer (points(scan) reads the results).  permute_mode "throughput": the
-    counter-based permutation test (set_permute_mode)."""
+    counter-based permutation test (set_permute_mode).  scan_mode "grid": the CLI's
+    --scan-mode=grid (scan_chromosome_grid and scan_permute_grid at small_grid_sp)."""
+    if scan_mode not in ("bisection", "grid"):
+        raise ValueError("scan_mode must be bisection or grid")
+    if scan_mode == "grid" and permute_mode != "parity":
+        raise ValueError("scan_mode grid runs on the parity stream only")
     get_lib().configure_logmsg(int(verbosity))
     set_permute_mode(permute_mode, permute_seed)
     init_log_table()
@@ -519,10 +581,15 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
     tab = compute_sweep_model_tables(scan, fsp, asc_depth, asc_min_freq, ascbias_background_only,
                                      include_invariant)
     compute_snp_null_model(scan, fsp)
-    scan_chromosome(scan, tab, eval_range, bp_resl, large_grid_sp)
+    if scan_mode == "grid":
+        scan_chromosome_grid(scan, tab, eval_range, small_grid_sp, large_grid_sp)
+    else:
+        scan_chromosome(scan, tab, eval_range, bp_resl, large_grid_sp)
     if profile_file is not None:  # the CLI's --profile-file: the -g spaced likelihood profile
         profile_output(profile_file, scan, scan_profile(scan, tab, eval_range, small_grid_sp, large_grid_sp), label)
-    if n_permute > 0:
+    if n_permute > 0 and scan_mode == "grid":
+        scan_permute_grid(scan, tab, n_permute, permute_nbp, eval_range, small_grid_sp, large_grid_sp, scan_width_mb)
+    elif n_permute > 0:
         scan_permute(scan, tab, n_permute, permute_nbp, 1.0, 1, eval_range, bp_resl, large_grid_sp, scan_width_mb)
     if output is not None:
         scan_output(output, scan, max_only, n_permute, label)

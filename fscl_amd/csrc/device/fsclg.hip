@@ -2364,7 +2364,11 @@ struct ProfChunk {
   int32_t out0, pad[3];                 // the chunk's first point in Params::out
 };
 
-template <bool LDS, class SM>
+// MAX (cellmax_kernel): the chunk's points are not stored; the first one of strictly greatest
+// clr (positions ascending, scan-chromosome.c:287) is kept in S.pt[3] -- the alpha search of
+// S.pt[0..1] never touches S.pt[2..3] -- with the OR of every point's flags in S.pt[2].flags,
+// and stored once, as point k of Params::out
+template <bool LDS, bool MAX = false, class SM>
 __device__ __forceinline__ void profile_body(SM& S, const Params& P, const ProfChunk* __restrict__ chunks) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int k = (int)blockIdx.x;
@@ -2395,13 +2399,31 @@ __device__ __forceinline__ void profile_body(SM& S, const Params& P, const ProfC
     __syncthreads();
     if (tid == 0) for (int q = 0; q < np; q++) S.cnt[1] += (unsigned long long)S.pt[q].n_snps;
     search_maxalpha_pts<LDS>(S, P, 0, np);  // (ends with a barrier: the points are final)
-    if (tid < np) {  // one store per point (P.out is host memory: no read-modify-write)
+    if constexpr (MAX) {
+      if (tid == 0) {  // the running maximum: strict >, so the first of equal points stays
+        int fl = i ? S.pt[2].flags : 0;
+        for (int q = 0; q < np; q++) {
+          fl |= S.pt[q].flags;
+          if ((i == 0 && q == 0) || S.pt[q].clr > S.pt[3].clr) S.pt[3] = S.pt[q];
+        }
+        S.pt[2].flags = fl;
+      }
+    } else if (tid < np) {  // one store per point (P.out is host memory: no read-modify-write)
       fsclg_point_t o;
       write_point(o, S.pt[tid]);
       o.cost = (uint32_t)min(S.cnt[0] >> 10, 0xFFFFFFFFull);  // the chunk's terms up to this search
       P.out[c.out0 + i + tid] = o;
     }
     __syncthreads();  // the next pair's init_scan_result rewrites S.pt[0..1]
+  }
+  if constexpr (MAX) {
+    if (tid == 0) {  // one store per chunk, by one thread (a plain vector store to host memory)
+      fsclg_point_t o;
+      write_point(o, S.pt[3]);
+      o.flags = S.pt[2].flags;
+      o.cost = (uint32_t)min(S.cnt[0] >> 10, 0xFFFFFFFFull);  // the chunk's terms
+      P.out[k] = o;
+    }
   }
   if (tid < 8 && S.cnt[tid]) atomicAdd(&P.stats[tid], S.cnt[tid]);
 }
@@ -2419,6 +2441,16 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(FSCLG_W
 profile_kernel(Params P, const ProfChunk* __restrict__ chunks) {
   __shared__ Smem S;
   profile_body<LDS>(S, P, chunks);
+}
+
+// The chunk maxima of dense runs on any slot's rows (fsclg_cellmax_submit): profile_kernel's
+// decomposition and register budget, one stored point per chunk in place of one per position.
+// Workgroups never wait for each other: the host folds a run's chunk maxima in chunk order
+template <bool LDS>
+__global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(FSCLG_WPE_PROFILE, FSCLG_WPE_PROFILE)))
+cellmax_kernel(Params P, const ProfChunk* __restrict__ chunks) {
+  __shared__ Smem S;
+  profile_body<LDS, true>(S, P, chunks);
 }
 
 // ------------------------------------------------------------ window null sums
@@ -3008,6 +3040,12 @@ struct Batch {
   unsigned int* d_xcnt = nullptr;
   size_t xacc_cap = 0;
   int xcnt_cap = 0;
+  // fsclg_cellmax_submit: the launch's chunks (pinned, read by the kernel), the chunks of each run
+  ProfChunk* p_cmchunks = nullptr;
+  int cmchunk_cap = 0;
+  std::vector<int> cm_nchunk;
+  bool cm_pending = false;
+  double cm_ms = 0.0;               // kernel time of the batch's last cell-maximum launch
 };
 
 struct fsclg_ctx {
@@ -3215,7 +3253,8 @@ int fsclg_close(fsclg_ctx* c) {
     if (B.d_ept) hipFree(B.d_ept);
     if (B.d_xacc) hipFree(B.d_xacc);
     if (B.d_xcnt) hipFree(B.d_xcnt);
-    for (void* p : {(void*)B.p_cells, (void*)B.p_out, (void*)B.p_epos, (void*)B.p_cell_ep, (void*)B.p_ctrace})
+    for (void* p : {(void*)B.p_cells, (void*)B.p_out, (void*)B.p_epos, (void*)B.p_cell_ep, (void*)B.p_ctrace,
+                    (void*)B.p_cmchunks})
       if (p) hipHostFree(p);
     hipEventDestroy(B.ev0);
     hipEventDestroy(B.ev1);
@@ -4531,6 +4570,7 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
   if (!B.pending) return set_err(FSCLG_E_STATE, "batch not submitted");
+  if (B.cm_pending) return set_err(FSCLG_E_STATE, "the batch holds cell maxima (fsclg_cellmax_wait)");
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   B.pending = false;
@@ -4817,6 +4857,134 @@ int fsclg_profile(fsclg_ctx* c, const fsclg_run_t* runs, int n_runs, int eval_ra
 }
 
 double fsclg_profile_last_ms(fsclg_ctx* c) { return c ? c->prof_ms : 0.0; }
+
+// The runs' maxima on the rows a slot holds: fsclg_profile_submit's chunks, evaluated by
+// cellmax_kernel on any batch and slot, one stored point per chunk (fsclg_cellmax_wait folds them)
+int fsclg_cellmax_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* runs, int n_runs, int eval_range) {
+  if (!c || (!runs && n_runs) || n_runs < 0 || eval_range < 0) return set_err(FSCLG_E_ARG, "runs");
+  if (batch < 0 || batch >= NBATCH || slot < 0 || slot >= NSLOT) return set_err(FSCLG_E_ARG, "batch/slot");
+  if (!c->d_pr0 || !c->d_coef || !c->d_la_coarse) return set_err(FSCLG_E_STATE, "tables/snps/alpha grid not set");
+  Batch& B = c->batch[batch];
+  if (B.pending) return set_err(FSCLG_E_STATE, "batch not waited for");
+  const int CH = fsclg_profile_chunk();
+  long long nchunk = 0;
+  for (int i = 0; i < n_runs; i++) {
+    const fsclg_run_t& r = runs[i];
+    if (r.step < 1 || r.count < 0) return set_err(FSCLG_E_ARG, "run step/count");
+    if (r.chr < 0 || r.chr >= c->n_chr) return set_err(FSCLG_E_ARG, "run chromosome");
+    // (the last position + 64: init_scan_result's de-collision may move a point past it)
+    if (r.count > 0 && (long long)r.start_pos + (long long)(r.count - 1) * r.step > 0x7FFFFFFFll - 64)
+      return set_err(FSCLG_E_ARG, "run position overflow");
+    const long long nwin = std::min((long long)c->h_chr_n[r.chr], 2ll * eval_range + 1);
+    if (nwin / SEG_SPLIT + 4 > (long long)MAXSEG_W) return set_err(FSCLG_E_UNSUPPORTED, "window above the segment table");
+    nchunk += (r.count + CH - 1) / CH;
+  }
+  if (nchunk > 0x7FFFFFFFll / (long long)sizeof(fsclg_point_t)) return set_err(FSCLG_E_ARG, "too many chunks");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  B.n_cells = n_runs; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
+  B.eval_range = eval_range; B.bp_resl = 0; B.cm_ms = 0.0;
+  B.cm_nchunk.resize((size_t)n_runs);
+  int r;
+  if (nchunk > 0) {
+    {  // the window null sums of every window the runs' positions touch, for the slot's rows: one
+       // covering cell per run (a slot another batch already runs on: only what is still missing)
+      std::vector<fsclg_cell_t> cover;
+      for (int i = 0; i < n_runs; i++)
+        if (runs[i].count > 0)
+          cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos,
+                                       runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
+      if (c->slot[slot].users == 0) r = fsclg_slot_windows(c, slot, cover.data(), (int)cover.size(), eval_range);
+      else r = ensure_windows(c, slot, eval_range, cover.data(), (int)cover.size(), &B.wr_memo);
+      if (r) return r;
+    }
+    if ((r = ensure_io(B, (int)nchunk))) return r;
+    if ((r = ensure_pinned(&B.p_cmchunks, &B.cmchunk_cap, (int)nchunk))) return r;
+  }
+  int nc = 0;
+  for (int i = 0; i < n_runs; i++) {
+    B.cm_nchunk[i] = (runs[i].count + CH - 1) / CH;
+    for (int k = 0; k < runs[i].count; k += CH, nc++)
+      B.p_cmchunks[nc] = ProfChunk{runs[i].chr, runs[i].start_pos + k * runs[i].step, runs[i].step,
+                                   std::min(CH, runs[i].count - k), nc, {0, 0, 0}};
+  }
+  if (nc > 0) {
+    HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
+    Params P = make_params(c, B, slot, nc, 3, eval_range, 0);
+    P.band_th = -1; P.ivc0 = c->c_ivc0; P.n_civ = c->c_civ;  // the walk-window path, as the profile kernel
+    P.civ_max = std::max(P.n_civ - 1, 0); P.n_cache = P.n_civ * P.stride;
+    P.off_thr = P.n_cache * 32; P.off_nul = P.off_thr + (c->n_iv + 1) * 8;
+    P.off_lt = P.off_nul + (c->n_rows + 1) * 8 - 256 * 8;
+    P.off_lx = (P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0) + 15) & ~15;
+    P.ctrace = nullptr;
+    const int dyn = P.lx_on ? P.off_lx + LX_BYTES : P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0);
+    const int stat_m = (int)((sizeof(Smem) + 15) / 16 * 16);
+    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
+    if (stat_m + dyn <= LDS_WG) {
+      static unsigned long long attr_set = 0;  // per device (bit = device id)
+      if (c->device >= 64 || !(attr_set >> c->device & 1ull)) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cellmax_kernel<true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WG - stat_m), "hipFuncSetAttribute");
+        if (c->device < 64) attr_set |= 1ull << c->device;
+      }
+      hipLaunchKernelGGL((cellmax_kernel<true>), dim3(nc), dim3(WG), dyn, B.stream, P, (const ProfChunk*)B.p_cmchunks);
+    } else {  // tables too large for the LDS copies: every coefficient from the global table
+      hipLaunchKernelGGL((cellmax_kernel<false>), dim3(nc), dim3(WG), 0, B.stream, P, (const ProfChunk*)B.p_cmchunks);
+    }
+    HIPCHK(hipGetLastError(), "launch cellmax_kernel");
+    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+  }
+  B.nu = nc;
+  B.pending = true; B.cm_pending = true;
+  c->slot[slot].users++;
+  return FSCLG_OK;
+}
+
+int fsclg_cellmax_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
+  if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
+  Batch& B = c->batch[batch];
+  if (!B.pending || !B.cm_pending) return set_err(FSCLG_E_STATE, "no cell maxima submitted on the batch");
+  if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  B.pending = false; B.cm_pending = false;
+  c->slot[B.slot].users--;
+  const int n_runs = B.n_cells, nc = B.nu;
+  if (nc > 0) {
+    HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+    float ms = 0.f, t0 = 0.f, t1 = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
+    B.cm_ms = ms;
+    c->kernel_ms += ms;
+    c->launches++;
+    c->busy.emplace_back((double)t0, (double)t1);
+  }
+  // a run's chunk maxima in chunk order, strict >: the first position of the greatest clr
+  int flags = 0;
+  for (int i = 0, k = 0; i < n_runs; i++) {
+    fsclg_point_t best;
+    memset(&best, 0, sizeof best);
+    unsigned long long cost = 0;
+    int fl = 0;
+    for (int j = 0; j < B.cm_nchunk[i]; j++, k++) {
+      const fsclg_point_t& q = B.p_out[k];
+      if (j == 0 || q.clr > best.clr) best = q;
+      fl |= q.flags;
+      cost += q.cost;
+    }
+    best.flags = fl;
+    best.cost = (uint32_t)std::min(cost, 0xFFFFFFFFull);
+    out[i] = best;
+    flags |= fl;
+  }
+  if (n_runs) note_alphas(c, out, n_runs);
+  if (flags) return set_err(flags & PF_UNSUPPORTED ? FSCLG_E_UNSUPPORTED : FSCLG_E_KERNEL, "device flag");
+  return FSCLG_OK;
+}
+
+double fsclg_cellmax_last_ms(fsclg_ctx* c, int batch) {
+  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].cm_ms : 0.0;
+}
 
 int fsclg_interval_thresholds(double log_ad_step, int n_iv, double* thr) {
   if (!thr || n_iv <= 0 || !(log_ad_step > 0)) return set_err(FSCLG_E_ARG, "thresholds");

@@ -55,7 +55,8 @@ int main(int argc, char **argv) {
   int small_grid_sp = 1000, large_grid_sp = 100000, dont_scan = 0, minimum_obs_depth = 5, n_threads = 1;
   int verbosity = MSG_STATUS, eval_range = 81920, bp_resl = 128, stop = 0, i, n_gpus = 0;
   double permute_nbp = 0.1, alpha_factor = 1.0, scan_width_mb = 1.0;
-  char *permute_mode = NULL, *permute_seed = NULL, *profile_fname = NULL;
+  char *permute_mode = NULL, *permute_seed = NULL, *profile_fname = NULL, *scan_mode = NULL;
+  int grid_mode = 0;
   scan_t *s;
   double **fsp;
   opt_t opts[] = {
@@ -90,6 +91,8 @@ int main(int argc, char **argv) {
       {0, "permute-mode", &permute_mode, T_STR, "parity (default: the reference's rand() stream, identical results) or "
                                                 "throughput (counter-based random numbers, trials independent; not identical)"},
       {0, "profile-file", &profile_fname, T_STR, "write CLR and alpha at every -g spaced position (the likelihood profile) to this file"},
+      {0, "scan-mode", &scan_mode, T_STR, "bisection (default: search_maxpos in every cell) or grid (the maximum over each cell's "
+                                          "-g spaced positions, in the scan and in the permutation test; one process, parity only)"},
       {0, "permute-seed", &permute_seed, T_STR, "seed of the throughput mode's random numbers (default 0xFD821A6)"},
       {0, NULL, NULL, 0, NULL}};
 
@@ -177,6 +180,20 @@ int main(int argc, char **argv) {
     logmsg(MSG_ERROR, "Error: --permute-mode must be parity or throughput.\n");
     stop = 1;
   }
+  if (scan_mode && strcmp(scan_mode, "bisection") && strcmp(scan_mode, "grid")) {
+    logmsg(MSG_ERROR, "Error: --scan-mode must be bisection or grid.\n");
+    stop = 1;
+  }
+  grid_mode = scan_mode && !strcmp(scan_mode, "grid");
+  if (grid_mode && permute_mode && !strcmp(permute_mode, "throughput")) {
+    logmsg(MSG_ERROR, "Error: --scan-mode=grid runs on the parity stream only (not with --permute-mode=throughput).\n");
+    stop = 1;
+  }
+  if (grid_mode && getenv("WORLD_SIZE") && getenv("RANK") && atoi(getenv("WORLD_SIZE")) > 1) {
+    logmsg(MSG_ERROR, "Error: --scan-mode=grid runs in one process (not with WORLD_SIZE=%s ranks).\n", getenv("WORLD_SIZE"));
+    stop = 1;
+  }
+  if (grid_mode && small_grid_sp < 1) { logmsg(MSG_ERROR, "Error: --scan-mode=grid needs a positive -g spacing.\n"); stop = 1; }
   if (permute_seed && !(permute_mode && !strcmp(permute_mode, "throughput")))
     logmsg(MSG_WARN, "Warning: --permute-seed is used only with --permute-mode=throughput.\n");
   if (stop) {
@@ -219,7 +236,13 @@ int main(int argc, char **argv) {
     }
     sm = compute_sweep_model_tables(s, fsp, asc_depth, asc_min_freq, bg_only, include_invariant);
     compute_snp_null_model(s, fsp);
-    scan_chromosome(s, sm, eval_range, bp_resl, large_grid_sp, n_threads);
+    if (grid_mode) {
+      logmsg(MSG_STATUS, "scan mode grid: each cell's statistic is its maximum over the %d bp grid positions, in the scan "
+                         "and in every permutation trial\n", small_grid_sp);
+      fscl_amd_scan_chromosome_grid(s, sm, eval_range, small_grid_sp, large_grid_sp);
+    } else {
+      scan_chromosome(s, sm, eval_range, bp_resl, large_grid_sp, n_threads);
+    }
     if (profile_fname) { /* the likelihood profile at -g spacing, of the data as loaded (rank 0 alone) */
       fscl_amd_profile_t *pf = fscl_amd_scan_profile(s, sm, eval_range, small_grid_sp, large_grid_sp);
       if (pf) {
@@ -231,7 +254,9 @@ int main(int argc, char **argv) {
         fscl_amd_profile_free(pf);
       }
     }
-    if (n_permute > 0)
+    if (n_permute > 0 && grid_mode)
+      fscl_amd_scan_permute_grid(s, sm, n_permute, permute_nbp, eval_range, small_grid_sp, large_grid_sp, scan_width_mb);
+    else if (n_permute > 0)
       scan_permute(s, sm, n_permute, permute_nbp, alpha_factor, n_threads, eval_range, bp_resl, large_grid_sp,
                    scan_width_mb);
     if (ms_fname && maximum_only) output_block_maxima(output_fname, s, prepend_label);

@@ -18,6 +18,7 @@
 #include <pthread.h>
 #include <sched.h>
 #include <signal.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -2468,6 +2469,243 @@ void fscl_amd_profile_output(const char *fname, const scan_t *s, const fscl_amd_
             q->n_snps, s->snps[q->window_start].pos, s->snps[q->window_end].pos);
   }
   if (fname) fclose(f);
+}
+
+/* ------------------------------------------------------ grid-maximum scan and test
+   The statistic of the reference's disabled fine-grid loops (scan-chromosome.c:269-296 the
+   scan, :505-523 the trial): a cell's point is the first position of strictly greatest clr
+   among its grid positions -- start + j * small_grid_sp with start <= pos <= end (the clipped
+   end; the start shared with the lower cell included; the end appended when the step misses
+   it), fscl_amd_profile_grid's positions of the cell.  One run per cell, or two for a
+   chromosome's last cell, evaluated by fsclg_cellmax_submit on the rows a slot holds. */
+static int cell_runs(const fsclg_cell_t *c, int g, fsclg_run_t *r) {
+  const int span = c->end_pos - c->start_pos;
+  r[0].chr = c->chr; r[0].start_pos = c->start_pos; r[0].step = g; r[0].count = span / g + 1;
+  if (span % g == 0) return 1;
+  r[1].chr = c->chr; r[1].start_pos = c->end_pos; r[1].step = g; r[1].count = 1;
+  return 2;
+}
+
+static double g_cellmax_ms;
+double fscl_amd_cellmax_last_ms(void) { return g_cellmax_ms; }
+
+/* the grid maxima of n cells on the rows of `slot`: the local devices take contiguous shares
+   of the cells balanced by window size x positions, every device is submitted to before the
+   first is waited for; out[i] is cell i's maximum */
+static void eval_cell_maxima(int slot, const fsclg_cell_t *cells, int n, int g, int eval_range, fsclg_point_t *out) {
+  fsclg_run_t *runs = fh_malloc(sizeof(fsclg_run_t) * 2 * (size_t)(n ? n : 1), "grid runs");
+  fsclg_point_t *ro = fh_malloc(sizeof(fsclg_point_t) * 2 * (size_t)(n ? n : 1), "grid points");
+  int *first = fh_malloc(sizeof(int) * ((size_t)n + 1), "grid runs"); /* cell i's runs: [first[i], first[i + 1]) */
+  double *cost = fh_malloc(sizeof(double) * (n ? n : 1), "cost");
+  int lo[FH_MAX_DEV], hi[FH_MAX_DEV], l, i, nr = 0;
+  for (i = 0; i < n; i++) {
+    int k, np = 0;
+    first[i] = nr;
+    nr += cell_runs(cells + i, g, runs + nr);
+    for (k = first[i]; k < nr; k++) np += runs[k].count;
+    cost[i] = window_cost(cells[i].chr, eval_range) * np;
+    D.st.gp_evals += (unsigned long long)np;
+  }
+  first[n] = nr;
+  dev_shares(cost, n, lo, hi);
+  g_cellmax_ms = 0.;
+  for (l = 0; l < D.n_dev; l++) {
+    DBG("cell maxima: device %d, cells [%d, %d)\n", D.dev[l], lo[l], hi[l]);
+    dev_check(fsclg_cellmax_submit(D.ctx[l], 0, slot, runs + first[lo[l]], first[hi[l]] - first[lo[l]], eval_range),
+              "cell maxima submit");
+  }
+  for (l = 0; l < D.n_dev; l++) {
+    double ms;
+    dev_check(fsclg_cellmax_wait(D.ctx[l], 0, ro + first[lo[l]]), "cell maxima wait");
+    ms = fsclg_cellmax_last_ms(D.ctx[l], 0);
+    if (ms > g_cellmax_ms) g_cellmax_ms = ms; /* the devices run side by side */
+  }
+  for (i = 0; i < n; i++) { /* a last cell's appended end: after its run, the same strict > */
+    out[i] = ro[first[i]];
+    if (first[i + 1] - first[i] == 2 && ro[first[i] + 1].clr > out[i].clr) out[i] = ro[first[i] + 1];
+  }
+  free(runs); free(ro); free(first); free(cost);
+}
+
+/* the test handle of fsclg_cellmax_submit / fsclg_cellmax_wait on the first device: the runs'
+   maxima on the uploaded rows (rows NULL: slot 0, batch 0) or on `rows` (n_snps device rows, set
+   into slot 1 with their whole-chromosome null sums; batch 1) */
+int fscl_amd_cellmax_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int n_runs, int eval_range,
+                          const uint32_t *rows, fsclg_point_t *out) {
+  int r, slot = 0;
+  if (!s || !sm || (!runs && n_runs) || n_runs < 0) return FSCLG_E_ARG;
+  prepare(s, sm);
+  g_cellmax_ms = 0.;
+  if (rows) {
+    double *nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
+    int i;
+    for (i = 0; i < s->n_snps; i++)
+      if (rows[i] >= (uint32_t)D.rm.n_dev_rows) { free(nul); return FSCLG_E_ARG; }
+    chr_null_sums_32(rows, nul);
+    slot = 1;
+    r = fsclg_slot_set_rows(D.ctx[0], slot, rows, nul);
+    free(nul);
+    if (r != FSCLG_OK) return r;
+  } else {
+    set_original_rows();
+  }
+  r = fsclg_cellmax_submit(D.ctx[0], slot, slot, runs, n_runs, eval_range);
+  if (r != FSCLG_OK) return r;
+  r = fsclg_cellmax_wait(D.ctx[0], slot, out);
+  g_cellmax_ms = fsclg_cellmax_last_ms(D.ctx[0], slot);
+  return r;
+}
+
+/* the device row of every site, as uploaded (n_snps values): what a permutation of the sites
+   rearranges (fscl_amd_cellmax_runs' rows) */
+int fscl_amd_site_rows(scan_t *s, sm_ptable_t *sm, uint32_t *out) {
+  if (!s || !sm || !out) return -1;
+  prepare(s, sm);
+  memcpy(out, D.row, sizeof(uint32_t) * (size_t)s->n_snps);
+  return s->n_snps;
+}
+
+/* the points fscl_amd_scan_chromosome_grid made last: fscl_amd_scan_permute_grid tests only
+   those, with the same spacings, on the same data (D.key) */
+static struct {
+  const scan_pt_t *pts;
+  int n, g, G;
+  uint64_t key, pkey;
+} GS;
+
+/* the points' content, chr .. clr (a freed and re-allocated point array may reuse its address) */
+static uint64_t points_hash(const scan_t *s) {
+  uint64_t h = 1469598103934665603ull;
+  int i;
+  for (i = 0; i < s->n_scan_pts; i++)
+    h = hash_words(s->scan_pts + i, offsetof(scan_pt_t, clr) + sizeof(double), h);
+  return h;
+}
+
+void fscl_amd_scan_chromosome_grid(scan_t *s, sm_ptable_t *sm, int eval_range, int small_grid_sp, int large_grid_sp) {
+  fsclg_cell_t *cells;
+  fsclg_point_t *out;
+  int n = 0, i;
+  double t0 = fh_now();
+  if (small_grid_sp < 1 || large_grid_sp < 1 || large_grid_sp % small_grid_sp != 0)
+    logmsg(MSG_FATAL, "fscl_amd: grid scan: fine grid spacing %d must be positive and divide the coarse grid spacing %d",
+           small_grid_sp, large_grid_sp);
+  if (D.world > 1) logmsg(MSG_FATAL, "fscl_amd: the grid scan mode runs in one process (not with %d ranks)", D.world);
+  prepare(s, sm);
+  cells = scan_cells(s, large_grid_sp, &n);
+  set_original_rows();
+  out = fh_malloc(sizeof(fsclg_point_t) * (n ? n : 1), "points");
+  eval_cell_maxima(0, cells, n, small_grid_sp, eval_range, out);
+  if (s->scan_pts)
+    for (i = 0; i < s->n_scan_pts; i++) free(s->scan_pts[i].permute_clr);
+  free(s->scan_pts);
+  s->scan_pts = fh_malloc(sizeof(scan_pt_t) * (n ? n : 1), "scan points");
+  for (i = 0; i < n; i++) { /* cell order is (chromosome, position) order: no sort */
+    to_scan_pt(s->scan_pts + i, out + i);
+    s->scan_pts[i].permute_clr = fh_malloc(sizeof(float) * CLR_NULL_DIST_SAVE, "permute_clr");
+  }
+  s->n_scan_pts = n;
+  GS.pts = s->scan_pts; GS.n = n; GS.g = small_grid_sp; GS.G = large_grid_sp; GS.key = D.key;
+  GS.pkey = points_hash(s);
+  free(out); free(cells);
+  D.st.scan_s += fh_now() - t0;
+  logmsg(MSG_STATUS, "\nInitial scan finished (grid maxima at %d bp).\n", small_grid_sp);
+}
+
+/* scan-chromosome.c:441-502 with a cell's search_maxpos replaced by its grid maximum on the
+   permuted rows, in lockstep: permute -> rows and null sums to slot 0 of every device -> the
+   grid maximum of every active cell -> count and prune.  The trial's cell is the point's own
+   cell (by cell index): the positions the original statistic was maximised over */
+void fscl_amd_scan_permute_grid(scan_t *s, sm_ptable_t *sm, int n_perm, double permute_nbp, int eval_range,
+                                int small_grid_sp, int large_grid_sp, double scan_width_mb) {
+  fh_rand_t *g = perm_rng();
+  void *prow;
+  int *act, n_act, n_cells = 0, i, k, trial = -1;
+  const int save = CLR_NULL_DIST_SAVE;
+  fsclg_cell_t *all, *cells;
+  fsclg_point_t *out;
+  double *nul, t0 = fh_now();
+  struct sigaction sa;
+  const char *e = getenv("FSCL_AMD_PERMUTE");
+  if (D.world > 1)
+    logmsg(MSG_FATAL, "fscl_amd: the grid permutation test runs in one process (not with %d ranks)", D.world);
+  if (g_pmode == FSCL_AMD_PERMUTE_THROUGHPUT || (e && !strncmp(e, "throughput", 10)))
+    logmsg(MSG_FATAL, "fscl_amd: the grid permutation test runs on the parity stream only (not in throughput mode)");
+  prepare(s, sm);
+  if (!s->scan_pts || s->scan_pts != GS.pts || s->n_scan_pts != GS.n || small_grid_sp != GS.g ||
+      large_grid_sp != GS.G || D.key != GS.key || points_hash(s) != GS.pkey)
+    logmsg(MSG_FATAL, "fscl_amd: the grid permutation test needs the points of fscl_amd_scan_chromosome_grid with the "
+                      "same spacings (-g %d -G %d)", small_grid_sp, large_grid_sp);
+  all = scan_cells(s, large_grid_sp, &n_cells);
+  if (n_cells != s->n_scan_pts) logmsg(MSG_FATAL, "fscl_amd: grid permutation test: %d cells, %d points", n_cells, s->n_scan_pts);
+  n_act = s->n_scan_pts;
+  {
+    const char *w = getenv("FSCL_AMD_SIGINT_WINDOW_MS");
+    g_sigint_window = w ? atof(w) / 1e3 : 10.;
+  }
+  memset(&sa, 0, sizeof sa);
+  sa.sa_handler = on_sigint;
+  sigemptyset(&sa.sa_mask);
+  gettimeofday(&g_last_dump, NULL);
+  sigaction(SIGINT, &sa, NULL);
+  D.chr_list = fh_malloc(sizeof(int) * (D.n_chr ? D.n_chr : 1), "chromosomes");
+  D.n_chr_list = 0;
+  for (i = 0; i < D.n_chr; i++)
+    if ((long long)D.chr_n[i] <= 2ll * eval_range + 1) D.chr_list[D.n_chr_list++] = i;
+  perm_geom(scan_width_mb);
+  (void)fh_rand(g); /* scan-chromosome.c:440: the single thread's usleep() draw */
+  act = fh_malloc(sizeof(int) * (n_act ? n_act : 1), "active points");
+  cells = fh_malloc(sizeof(fsclg_cell_t) * (n_act ? n_act : 1), "cells");
+  out = fh_malloc(sizeof(fsclg_point_t) * (n_act ? n_act : 1), "points");
+  nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
+  for (i = 0; i < s->n_scan_pts; i++) act[i] = i;
+  for (;;) {
+    double tp = fh_now();
+    prow = slot_stage(0);
+    block_permute(prow, D.rowp, s->n_snps, permute_nbp, scan_width_mb, g, &D.st.negj, NULL, 0);
+    D.st.host_perm_s += fh_now() - tp;
+    trial++;
+    for (i = k = 0; i < n_act; i++)
+      if (!s->scan_pts[act[i]].permute_finished) act[k++] = act[i];
+    n_act = k;
+    cr_logmsg(MSG_STATUS, "Scanning snp block permutations... %7d (%d scan pts remaining)        ", trial, n_act);
+    if (n_act == 0 || trial > n_perm) break;
+    tp = fh_now();
+    chr_null_sums(prow, nul);
+    D.st.host_null_s += fh_now() - tp;
+    tp = fh_now();
+    slot_upload(0, nul);
+    D.st.host_upload_s += fh_now() - tp;
+    for (i = 0; i < n_act; i++) cells[i] = all[act[i]];
+    tp = fh_now();
+    eval_cell_maxima(0, cells, n_act, small_grid_sp, eval_range, out);
+    D.st.search_s += fh_now() - tp;
+    tp = fh_now();
+    D.st.trials++;
+    for (i = 0; i < n_act; i++) { /* scan-chromosome.c:488-502, ascending point order */
+      scan_pt_t *q = s->scan_pts + act[i];
+      const double clr = out[i].clr;
+      if (clr >= q->clr) {
+        q->permute_p++;
+        if (q->permute_p >= 20 && q->permute_p / (double)q->permute_n >= fh_rand(g) / (2147483647 + 1.0))
+          q->permute_finished = 1; /* Q7: ratio uses the pre-increment count */
+      }
+      if (q->permute_n < save) q->permute_clr[q->permute_n] = (float)clr;
+      q->permute_n++;
+      if (clr < 0 || clr > 1000000 || isnan(clr))
+        fprintf(stderr, "%d\t%d\t%g\t%1.3e\n", q->chr, cells[i].start_pos, clr, exp(out[i].lalpha));
+    }
+    D.st.prune_s += fh_now() - tp;
+    if (sigint_agreed()) sigint_dump(s, n_perm);
+  }
+  free(act); free(cells); free(out); free(nul); free(all);
+  cr_logmsg(MSG_STATUS, "Scanning snp block permutations... finished.\n");
+  signal(SIGINT, SIG_DFL);
+  free(D.chr_list);
+  D.chr_list = NULL;
+  D.n_chr_list = 0;
+  set_original_rows();
+  D.st.permute_s += fh_now() - t0;
 }
 
 /* ---------------------------------------------------------------- output */

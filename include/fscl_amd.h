@@ -292,6 +292,45 @@ int fscl_amd_profile_runs(scan_t *scan_obj, sm_ptable_t *sm_p, const fsclg_run_t
                           fsclg_point_t *out);
 double fscl_amd_profile_last_ms(void);
 
+/* ---- grid-maximum scan and permutation test (--scan-mode=grid) --------------------
+   The statistic of the reference's disabled fine-grid loops (scan-chromosome.c:269-296 the
+   scan, :505-523 the trial): a cell's point is the first grid position of strictly greatest
+   clr among start + j * small_grid_sp, start <= pos <= end (fscl_amd_profile_grid's positions
+   of the cell: the start shared with the lower cell included, a clipped end the step misses
+   appended), found on the device by fsclg_cellmax_submit.
+
+   fscl_amd_scan_chromosome_grid is scan_chromosome's counterpart: the same cells, one point per
+   cell in cell order (which is (chromosome, position) order; not re-sorted), counters zeroed, a
+   permute_clr buffer each; bit for bit fscl_amd_profile_cell_max(fscl_amd_scan_profile(...)).
+   Fatal if small_grid_sp does not divide large_grid_sp.
+
+   fscl_amd_scan_permute_grid is scan_permute's: the reference's trial loop
+   (scan-chromosome.c:441-502 -- the rand() stream with its leading usleep draw, the block
+   permutation, >= counting, the permute_p >= 20 prune draw, permute_clr saved as float, SIGINT)
+   with a cell's search_maxpos replaced by its grid maximum on the permuted rows.  The trial's
+   cell is the point's OWN cell, by cell index -- the positions the original statistic was
+   maximised over -- not the G-aligned unclipped cell of the bisection path.  Several local
+   devices share a trial's active cells (contiguous shares balanced by window size x positions);
+   the results are those of one device.  Limits: one process, the parity stream only, trials in
+   lockstep (no pipelining).  Fatal, with a message: several ranks, throughput permute mode,
+   points that are not fscl_amd_scan_chromosome_grid's last result with the same spacings.
+   The original rows are restored at the end. */
+void fscl_amd_scan_chromosome_grid(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, int small_grid_sp,
+                                   int large_grid_sp);
+void fscl_amd_scan_permute_grid(scan_t *scan_obj, sm_ptable_t *sm_p, int n_permute, double permute_nbp,
+                                int eval_range, int small_grid_sp, int large_grid_sp, double scan_width_mb);
+/* fsclg_cellmax_submit / fsclg_cellmax_wait on the first device, for any runs (the device
+   entry's test handle): out holds n_runs points.  rows NULL: on the uploaded rows (slot 0);
+   else on `rows`, n_snps device rows (a rearrangement of fscl_amd_site_rows), set into slot 1
+   with their whole-chromosome null sums.  Returns a fsclg status code.
+   fscl_amd_cellmax_last_ms: the cell-maximum kernel's milliseconds of the last evaluation (the
+   slowest device's); fscl_amd_site_rows: the device row of every site as uploaded, returns
+   n_snps. */
+int fscl_amd_cellmax_runs(scan_t *scan_obj, sm_ptable_t *sm_p, const fsclg_run_t *runs, int n_runs, int eval_range,
+                          const uint32_t *rows, fsclg_point_t *out);
+double fscl_amd_cellmax_last_ms(void);
+int fscl_amd_site_rows(scan_t *scan_obj, sm_ptable_t *sm_p, uint32_t *out);
+
 /* release the device context (tables / snps) */
 void fscl_amd_shutdown(void);
 

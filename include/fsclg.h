@@ -231,6 +231,25 @@ int fsclg_profile_wait(fsclg_ctx *c, fsclg_point_t *out);
 int fsclg_profile_chunk(void);
 double fsclg_profile_last_ms(fsclg_ctx *c);
 
+/* Cell maxima: the first position of strictly greatest clr of each run (the reference's disabled
+   fine-grid loops: the scan's, scan-chromosome.c:269-296, `>` at :287, and the trial's, :505-523),
+   on the rows a slot HOLDS -- whatever fsclg_slot_set_rows* put there, e.g. one trial's
+   permutation -- with the slot's whole-chromosome null sums; the window null sums are summed
+   here, for the slot's rows.  out holds n_runs points in run order, each the point
+   fsclg_profile gives at that position on the same rows; a run with count == 0 yields a zeroed
+   point (n_snps = 0).  The kernel takes fsclg_profile's chunks (fsclg_profile_chunk() positions,
+   one workgroup each) and stores one point per chunk, the chunk's first strict maximum; the wait
+   folds a run's chunk maxima in chunk order with the same `>`.  cost is the terms / 1024 of the
+   run's chunks.  Asynchronous, like fsclg_search_submit / fsclg_search_wait, on any batch and
+   slot (runs are copied; the batch must be idle; several devices: submit to all, then wait).
+   FSCLG_E_ARG: step < 1, count < 0, a bad chr, batch or slot, a position past the int range;
+   FSCLG_E_STATE: tables or SNPs not uploaded, the batch pending (submit), no cell maxima
+   submitted on it (wait).  fsclg_cellmax_last_ms: the kernel's own time (HIP events) of the
+   batch's last launch; the device counters accumulate as for any launch. */
+int fsclg_cellmax_submit(fsclg_ctx *c, int batch, int slot, const fsclg_run_t *runs, int n_runs, int eval_range);
+int fsclg_cellmax_wait(fsclg_ctx *c, int batch, fsclg_point_t *out);
+double fsclg_cellmax_last_ms(fsclg_ctx *c, int batch);
+
 /* the exact interval thresholds the kernel uses in place of spline_interpolate's
    division (sm-spline.c:52): thr[j] = least double x with
    (int)((x - LOG_AD_MIN) / log_ad_step) >= j, for j = 1..n_iv (thr has n_iv+1 slots) */

@@ -242,7 +242,9 @@ class Shim:
         if r != 0:
             raise RuntimeError(f"{what}: code {r}: {self.L.fsclg_last_error().decode()}")
 
-    def upload(self, T: Tables):
+    def upload(self, T: Tables, chr_start=None, chr_n=None):
+        """The tables and sites; chr_start / chr_n: the chromosomes' first sites and lengths (default:
+        one chromosome)."""
         coef = np.ascontiguousarray(T.coef, dtype=np.float64)
         nul = np.ascontiguousarray(T.nullrow, dtype=np.float64)
         lt = np.ascontiguousarray(T.log_table, dtype=np.float64)
@@ -250,9 +252,12 @@ class Shim:
                                             T.step), "fsclg_upload_tables")
         pos = np.ascontiguousarray(T.pos, dtype=np.int32)
         row = np.ascontiguousarray(T.row, dtype=np.uint32)
-        cs, cn = (C.c_int32 * 1)(0), (C.c_int32 * 1)(len(pos))
+        if chr_start is None:
+            chr_start, chr_n = [0], [len(pos)]
+        nc = len(chr_start)
+        cs, cn = (C.c_int32 * nc)(*chr_start), (C.c_int32 * nc)(*chr_n)
         self._ok(self.L.fsclg_upload_snps(self.ctx, pos.ctypes.data_as(C.POINTER(C.c_int32)),
-                                          row.ctypes.data_as(C.POINTER(C.c_uint32)), len(pos), cs, cn, 1),
+                                          row.ctypes.data_as(C.POINTER(C.c_uint32)), len(pos), cs, cn, nc),
                  "fsclg_upload_snps")
 
     def search(self, pts: list[Point], lalpha0: float = LOG_AD_MAX):
@@ -267,14 +272,18 @@ class Shim:
         self._ok(self.L.fsclg_search_points(self.ctx, a, n), "fsclg_search_points")
         return [(q.lalpha, q.sm_logl, q.clr) for q in a]
 
-    def set_chr_null(self, N: float):
-        v = (C.c_double * 1)(N)
+    def set_chr_null(self, N, n_chr: int = 1):
+        v = (C.c_double * n_chr)(*([N] * n_chr))
         self._ok(self.L.fsclg_set_chr_null(self.ctx, v), "fsclg_set_chr_null")
 
-    def profile(self, start_pos: int, step: int, count: int, eval_range: int):
-        run = (RunT * 1)(RunT(0, start_pos, step, count))
+    def profile(self, start_pos, step: int = 0, count: int = 0, eval_range: int = 0):
+        """One run (start_pos, step, count) on chromosome 0, or start_pos = a list of runs
+        (chr, start_pos, step, count) in one call; the points of all runs in order."""
+        runs = [(0, start_pos, step, count)] if isinstance(start_pos, int) else list(start_pos)
+        run = (RunT * len(runs))(*[RunT(*r) for r in runs])
+        count = sum(r[3] for r in runs)
         out = (PointT * count)()
-        self._ok(self.L.fsclg_profile(self.ctx, run, 1, eval_range, out), "fsclg_profile")
+        self._ok(self.L.fsclg_profile(self.ctx, run, len(runs), eval_range, out), "fsclg_profile")
         return [(Point(q.nearest_snp, q.sweep_pos, q.window_start, q.window_end, q.null_logl),
                  (q.lalpha, q.sm_logl, q.clr)) for q in out]
 

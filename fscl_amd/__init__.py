@@ -28,6 +28,8 @@ __all__ = [
     "device_count", "set_dump_output", "ProfileT", "RunT", "PointT", "scan_profile", "profile_cell_max", "profile_grid",
     "profile_runs", "profile_output", "profile_last_ms", "profile_chunk",
     "scan_chromosome_grid", "scan_permute_grid", "cellmax_runs", "cellmax_last_ms", "site_rows",
+    "scan_curves", "scan_point_curves", "curve_runs", "curve_support", "curve_output", "curve_last_ms",
+    "curve_forced", "CURVE_DTYPE",
 ]
 
 ROOT = Path(__file__).resolve().parent
@@ -133,6 +135,9 @@ EXPORTS = [
     "fsclg_cellmax_submit", "fsclg_cellmax_wait", "fsclg_cellmax_last_ms",
     "fscl_amd_scan_chromosome_grid", "fscl_amd_scan_permute_grid", "fscl_amd_cellmax_runs",
     "fscl_amd_cellmax_last_ms", "fscl_amd_site_rows",
+    "fsclg_curve_submit", "fsclg_curve_wait", "fsclg_curve_last_ms", "fsclg_curve_forced",
+    "fscl_amd_scan_curves", "fscl_amd_scan_point_curves", "fscl_amd_curve_support", "fscl_amd_curve_output",
+    "fscl_amd_curve_runs", "fscl_amd_curve_last_ms", "fscl_amd_curve_forced",
 ]
 
 
@@ -194,6 +199,14 @@ def _load() -> C.CDLL:
         "fscl_amd_cellmax_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(RunT), C.c_int, C.c_int, C.c_void_p, P(PointT)]),
         "fscl_amd_cellmax_last_ms": (C.c_double, []),
         "fscl_amd_site_rows": (C.c_int, [P(ScanT), P(SmPtableT), C.c_void_p]),
+        "fscl_amd_scan_curves": (C.c_int, [P(ScanT), P(SmPtableT), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+        "fscl_amd_scan_point_curves": (C.c_int, [P(ScanT), P(SmPtableT), C.c_int, C.c_void_p]),
+        "fscl_amd_curve_support": (C.c_int, [C.c_void_p, C.c_double, P(C.c_double), P(C.c_double), P(C.c_int),
+                                             P(C.c_int)]),
+        "fscl_amd_curve_output": (None, [C.c_char_p, P(ScanT), C.c_void_p, C.c_int, C.c_double, C.c_char_p]),
+        "fscl_amd_curve_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(RunT), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+        "fscl_amd_curve_last_ms": (C.c_double, []),
+        "fscl_amd_curve_forced": (C.c_ulonglong, []),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -477,6 +490,91 @@ def cellmax_last_ms() -> float:
     return float(get_lib().fscl_amd_cellmax_last_ms())
 
 
+CURVE_MAX = 27  # FSCLG_CURVE_MAX: 11 coarse + 16 refine candidates at most
+# fsclg_curve_t (= fscl_amd_curve_t): the position's point, then the alpha search's candidates in the
+# reference's evaluation order -- la[k] the log alpha, sm[k] its sm_likelihood value, k < n_coarse + n_refine
+CURVE_DTYPE = np.dtype([("pt", _POINT_RAW), ("n_coarse", "i4"), ("n_refine", "i4"), ("la", "f8", (CURVE_MAX,)),
+                        ("sm", "f8", (CURVE_MAX,))])
+assert CURVE_DTYPE.itemsize == _POINT_RAW.itemsize + 8 + 16 * CURVE_MAX
+
+
+def _curve_check(r: int, what: str) -> None:
+    if r != 0:
+        raise RuntimeError(f"{what}: code {r}: {get_lib().fsclg_last_error().decode()}")
+
+
+def scan_curves(scan, tables, chr_pos, eval_range: int = 81920) -> np.ndarray:
+    """The alpha likelihood curve at each (chromosome index, position) of ``chr_pos``, on the data as
+    loaded (include/fscl_amd.h): a CURVE_DTYPE array in the given order."""
+    cp = np.ascontiguousarray(np.asarray(chr_pos, dtype=np.int32).reshape(-1, 2).T)  # [chr..., pos...]
+    n = cp.shape[1]
+    out = np.zeros(max(n, 1), dtype=CURVE_DTYPE)
+    _curve_check(get_lib().fscl_amd_scan_curves(scan, tables, int(eval_range), cp[0].ctypes.data, cp[1].ctypes.data, n,
+                                                out.ctypes.data), "fscl_amd_scan_curves")
+    return out[:n]
+
+
+def scan_point_curves(scan, tables, eval_range: int = 81920) -> np.ndarray:
+    """The curve of every scan point at its own sweep_pos (after scan_chromosome or
+    scan_chromosome_grid): a CURVE_DTYPE array in points() order."""
+    n = scan.contents.n_scan_pts
+    out = np.zeros(max(n, 1), dtype=CURVE_DTYPE)
+    _curve_check(get_lib().fscl_amd_scan_point_curves(scan, tables, int(eval_range), out.ctypes.data),
+                 "fscl_amd_scan_point_curves")
+    return out[:n]
+
+
+def curve_runs(scan, tables, runs, eval_range: int = 81920, rows=None, out=None) -> np.ndarray:
+    """The curves at start + k * step, k < count, for each (chr, start, step, count) of ``runs``, through
+    fsclg_curve_submit / fsclg_curve_wait on the scan's first device (the shim-level handle, next to
+    cellmax_runs): a CURVE_DTYPE array in run order.  ``rows`` as for cellmax_runs; ``out``: a
+    CURVE_DTYPE array to fill (tests pre-fill it)."""
+    arr = (RunT * max(len(runs), 1))(*[RunT(*[int(v) for v in r]) for r in runs])
+    n = sum(max(int(r[3]), 0) for r in runs)
+    if out is None:
+        out = np.zeros(max(n, 1), dtype=CURVE_DTYPE)
+    if out.dtype != CURVE_DTYPE or len(out) < n or not out.flags.c_contiguous:
+        raise ValueError("out must be a contiguous CURVE_DTYPE array of sum(count) records")
+    rp = None
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        if len(rows) != scan.contents.n_snps:
+            raise ValueError("rows must hold one row per site")
+        rp = rows.ctypes.data
+    _curve_check(get_lib().fscl_amd_curve_runs(scan, tables, arr, len(runs), int(eval_range), rp, out.ctypes.data),
+                 "fscl_amd_curve_runs")
+    return out[:n]
+
+
+def curve_support(curve, drop: float = 2.0):
+    """(la_lo, la_hi, open_lo, open_hi) of one CURVE_DTYPE record: the log alphas bounding the
+    connected run around the argmax whose sm >= sm_max - drop, and whether it reaches the lowest /
+    highest evaluated alpha; None if no value beat the initial state (all NaN).  Host only.  The
+    likelihood is composite: the interval describes the curve, it is not a calibrated confidence interval."""
+    rec = np.ascontiguousarray(np.asarray(curve, dtype=CURVE_DTYPE).reshape(1))
+    lo, hi, ol, oh = C.c_double(), C.c_double(), C.c_int(), C.c_int()
+    r = get_lib().fscl_amd_curve_support(rec.ctypes.data, float(drop), C.byref(lo), C.byref(hi), C.byref(ol), C.byref(oh))
+    if r < 0:
+        raise ValueError("drop must be >= 0")
+    return (lo.value, hi.value, bool(ol.value), bool(oh.value)) if r == 1 else None
+
+
+def curve_output(path, scan, curves: np.ndarray, drop: float = 2.0, label=None) -> None:
+    """The --alpha-file format (include/fscl_amd.h, README): one row per point and alpha, one
+    summary row per point."""
+    cv = np.ascontiguousarray(curves, dtype=CURVE_DTYPE)
+    get_lib().fscl_amd_curve_output(_b(path), scan, cv.ctypes.data if len(cv) else None, len(cv), float(drop), _b(label))
+
+
+def curve_last_ms() -> float:
+    return float(get_lib().fscl_amd_curve_last_ms())
+
+
+def curve_forced() -> int:
+    """Walks summed sequentially only because a curve wants every value exact (since reset_stats)."""
+    return int(get_lib().fscl_amd_curve_forced())
+
+
 def get_stats() -> dict:
     st = Stats()
     get_lib().fscl_amd_get_stats(C.byref(st))
@@ -561,7 +659,7 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         permute_nbp=0.1, asc_depth=0, asc_min_freq=1, ascbias_background_only=False, include_invariant=False,
         force_neutral=False, minimum_depth=5, large_grid_sp=100000, scan_width_mb=1.0, max_only=False,
         label=None, eval_range=81920, bp_resl=128, verbosity=1, permute_mode="parity", permute_seed=0xFD821A6,
-        profile_file=None, small_grid_sp=1000, scan_mode="bisection"):
+        profile_file=None, small_grid_sp=1000, scan_mode="bisection", alpha_file=None, alpha_drop=2.0):
     """The fscl main() pipeline (fscl.c:316-337) in-process; returns the scan_t
     pointer (points(scan) reads the results).  permute_mode "throughput": the
     counter-based permutation test (set_permute_mode).  scan_mode "grid": the CLI's
@@ -587,6 +685,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         scan_chromosome(scan, tab, eval_range, bp_resl, large_grid_sp)
     if profile_file is not None:  # the CLI's --profile-file: the -g spaced likelihood profile
         profile_output(profile_file, scan, scan_profile(scan, tab, eval_range, small_grid_sp, large_grid_sp), label)
+    if alpha_file is not None:  # the CLI's --alpha-file: the scan points' alpha likelihood curves
+        curve_output(alpha_file, scan, scan_point_curves(scan, tab, eval_range), alpha_drop, label)
     if n_permute > 0 and scan_mode == "grid":
         scan_permute_grid(scan, tab, n_permute, permute_nbp, eval_range, small_grid_sp, large_grid_sp, scan_width_mb)
     elif n_permute > 0:

@@ -85,6 +85,8 @@ constexpr int MAXSEG_W = (163841 / SEG_SPLIT + 4 + 31) / 32 * 32;  // segments p
 constexpr int SEGWORDS = MAXSEG_W / 32;
 constexpr int MAXTIES = 512;       // per eval_walks; overflow sends the affected argmax to the exact slow path
 constexpr int MAXREF = 16;
+constexpr int NCOARSE_REF = 11;    // the reference's coarse alphas (sm-search.c:277)
+static_assert(FSCLG_CURVE_MAX == NCOARSE_REF + MAXREF, "fsclg_curve_t holds every candidate of one alpha search");
 constexpr int LDS_WG = FSCLG_LDS_WG;  // LDS per workgroup (default: two workgroups per CU, 160 KiB)
 
 #ifndef FSCLG_U
@@ -2044,8 +2046,15 @@ __device__ __forceinline__ int argmax_wave(SM& S, int first, int count, double p
 // refine argmax runs on them at once; only the points whose guess missed take a second phase.
 // The candidates, their values and the order of the strict '>' comparisons are the reference's
 // either way; a wrong guess costs only its walks.
-template <bool LDS, bool SPLIT = false, class SM>
-__device__ __forceinline__ void search_maxalpha_pts(SM& S, const Params& P, int p0, int np) {
+// CURVE (curve_kernel): every walk of both phases is made exact after its phase's argmax has
+// settled -- the argmax reads only exact values, so the extra pass cannot change a winner -- and
+// stored, alpha and value, into the points' records rec[0 .. np) (host memory) before the walk
+// slots are reused: coarse walk a at entry a, refine walk r at entry n_coarse + r.
+template <bool LDS, bool SPLIT = false, bool CURVE = false, class SM>
+__device__ __forceinline__ void search_maxalpha_pts(SM& S, const Params& P, int p0, int np,
+                                                    fsclg_curve_t* __restrict__ rec = nullptr,
+                                                    unsigned long long* __restrict__ forced = nullptr) {
+  static_assert(!(CURVE && SPLIT), "the curve kernel has one workgroup per chunk");
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nc = P.n_coarse;
   const bool spec = SPLIT && P.spec_refine && np * (nc + MAXREF) <= SM::MAXW;  // uniform
@@ -2135,9 +2144,31 @@ __device__ __forceinline__ void search_maxalpha_pts(SM& S, const Params& P, int 
     }
     __syncthreads();
   };
+  // CURVE: the phase's walks that the argmax left inexact, summed sequentially (settle's slow
+  // path for every one of them); ends with a barrier
+  auto force_exact = [&]() {
+    const int nwk = __builtin_amdgcn_readfirstlane(S.nwalk);
+    if (tid < nwk && !S.exact[tid]) S.need_slow[tid] = 1;
+    __syncthreads();
+    for (int w = wave; w < nwk; w += NWAVE) {
+      if (__builtin_amdgcn_readfirstlane(S.need_slow[w])) {
+        const double v = walk_sequential<LDS>(S, S.w[w], S.pt[S.w[w].p], P, lane);
+        if (lane == 0) { S.val[w] = v; S.exact[w] = 1; S.need_slow[w] = 0; atomicAdd(forced, 1ull); }
+      }
+    }
+    __syncthreads();
+  };
   const unsigned all = (1u << np) - 1u;
   eval_walks<LDS, SPLIT>(S, P);
   settle(all, false);
+  if constexpr (CURVE) {
+    force_exact();
+    if (tid < np * nc) {  // one lane per entry, before lay_refine reuses the slots
+      fsclg_curve_t& R = rec[tid / nc];
+      R.la[tid % nc] = S.w[tid].la;
+      R.sm[tid % nc] = S.val[tid];
+    }
+  }
   // coarse winners (or the untouched initial state); the points whose guess held
   if (wave == 0) {
     bool hit = false;
@@ -2171,6 +2202,19 @@ __device__ __forceinline__ void search_maxalpha_pts(SM& S, const Params& P, int 
     __syncthreads();
     eval_walks<LDS, SPLIT>(S, P);
     settle(miss, true);
+    if constexpr (CURVE) {  // (no speculative walks here: every point is in `miss`)
+      force_exact();
+      if (tid < np * 64) {  // wave p: point p's refine list behind its coarse entries, zeros after it
+        const int first = S.pt[p0 + wave].pad >> 8, count = S.pt[p0 + wave].pad & 0xFF;
+        fsclg_curve_t& R = rec[wave];
+        if (nc + lane < FSCLG_CURVE_MAX) {
+          const bool in = lane < count;
+          R.la[nc + lane] = in ? S.w[first + lane].la : 0.0;
+          R.sm[nc + lane] = in ? S.val[first + lane] : 0.0;
+        }
+        if (lane == 0) { R.n_coarse = nc; R.n_refine = count; }
+      }
+    }
     finish(miss);
   }
 }
@@ -2368,8 +2412,13 @@ struct ProfChunk {
 // clr (positions ascending, scan-chromosome.c:287) is kept in S.pt[3] -- the alpha search of
 // S.pt[0..1] never touches S.pt[2..3] -- with the OR of every point's flags in S.pt[2].flags,
 // and stored once, as point k of Params::out
-template <bool LDS, bool MAX = false, class SM>
-__device__ __forceinline__ void profile_body(SM& S, const Params& P, const ProfChunk* __restrict__ chunks) {
+// CURVE (curve_kernel): a position's point goes into its record of `curve` (ProfChunk::out0 indexes
+// it), beside the alpha search's 25-26 candidate values, every one the exact sequential sum
+template <bool LDS, bool MAX = false, bool CURVE = false, class SM>
+__device__ __forceinline__ void profile_body(SM& S, const Params& P, const ProfChunk* __restrict__ chunks,
+                                             fsclg_curve_t* __restrict__ curve = nullptr,
+                                             unsigned long long* __restrict__ forced = nullptr) {
+  static_assert(!(MAX && CURVE), "a curve per position");
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int k = (int)blockIdx.x;
   if (k >= P.n_cells) return;
@@ -2398,7 +2447,8 @@ __device__ __forceinline__ void profile_body(SM& S, const Params& P, const ProfC
     if (wave < np) init_point_wave(S.pt[wave], c.chr, c.start_pos + (i + wave) * c.step, P, lane);
     __syncthreads();
     if (tid == 0) for (int q = 0; q < np; q++) S.cnt[1] += (unsigned long long)S.pt[q].n_snps;
-    search_maxalpha_pts<LDS>(S, P, 0, np);  // (ends with a barrier: the points are final)
+    if constexpr (CURVE) search_maxalpha_pts<LDS, false, true>(S, P, 0, np, curve + c.out0 + i, forced);
+    else search_maxalpha_pts<LDS>(S, P, 0, np);  // (ends with a barrier: the points are final)
     if constexpr (MAX) {
       if (tid == 0) {  // the running maximum: strict >, so the first of equal points stays
         int fl = i ? S.pt[2].flags : 0;
@@ -2412,7 +2462,8 @@ __device__ __forceinline__ void profile_body(SM& S, const Params& P, const ProfC
       fsclg_point_t o;
       write_point(o, S.pt[tid]);
       o.cost = (uint32_t)min(S.cnt[0] >> 10, 0xFFFFFFFFull);  // the chunk's terms up to this search
-      P.out[c.out0 + i + tid] = o;
+      if constexpr (CURVE) curve[c.out0 + i + tid].pt = o;
+      else P.out[c.out0 + i + tid] = o;
     }
     __syncthreads();  // the next pair's init_scan_result rewrites S.pt[0..1]
   }
@@ -2451,6 +2502,18 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(FSCLG_W
 cellmax_kernel(Params P, const ProfChunk* __restrict__ chunks) {
   __shared__ Smem S;
   profile_body<LDS, true>(S, P, chunks);
+}
+
+// The alpha likelihood curve of every position of dense runs (fsclg_curve_submit): profile_kernel's
+// decomposition and register budget; a record per position in host memory, written with plain
+// stores by the position's own workgroup (no workgroup waits for another).  `forced` counts the
+// walks summed sequentially only because the curve wants every value exact.
+template <bool LDS>
+__global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(FSCLG_WPE_PROFILE, FSCLG_WPE_PROFILE)))
+curve_kernel(Params P, const ProfChunk* __restrict__ chunks, fsclg_curve_t* __restrict__ curve,
+             unsigned long long* __restrict__ forced) {
+  __shared__ Smem S;
+  profile_body<LDS, false, true>(S, P, chunks, curve, forced);
 }
 
 // ------------------------------------------------------------ window null sums
@@ -3046,6 +3109,12 @@ struct Batch {
   std::vector<int> cm_nchunk;
   bool cm_pending = false;
   double cm_ms = 0.0;               // kernel time of the batch's last cell-maximum launch
+  // fsclg_curve_submit: the records (pinned, written by the kernel; the chunks are p_cmchunks)
+  fsclg_curve_t* p_curve = nullptr;
+  int curve_cap = 0;
+  int cv_n = 0;                     // records of the submitted launch
+  bool cv_pending = false;
+  double cv_ms = 0.0;               // kernel time of the batch's last curve launch
 };
 
 struct fsclg_ctx {
@@ -3219,8 +3288,8 @@ int fsclg_open(int device, fsclg_ctx** out) {
   HIPCHK(hipEventCreate(&c->ev_ref), "hipEventCreate");
   HIPCHK(hipEventCreate(&c->wev0), "hipEventCreate");
   HIPCHK(hipEventCreate(&c->wev1), "hipEventCreate");
-  HIPCHK(hipMalloc((void**)&c->d_stats, sizeof(unsigned long long) * 24), "hipMalloc stats");  // 8 + FSCLG_TRIP_STAMPS
-  HIPCHK(hipMemset(c->d_stats, 0, sizeof(unsigned long long) * 24), "hipMemset");
+  HIPCHK(hipMalloc((void**)&c->d_stats, sizeof(unsigned long long) * 25), "hipMalloc stats");  // 8 + FSCLG_TRIP_STAMPS + curve_kernel's forced walks
+  HIPCHK(hipMemset(c->d_stats, 0, sizeof(unsigned long long) * 25), "hipMemset");
   HIPCHK(hipEventRecord(c->ev_ref, c->ustream), "hipEventRecord");
   HIPCHK(hipEventSynchronize(c->ev_ref), "hipEventSynchronize");
   *out = c;
@@ -3254,7 +3323,7 @@ int fsclg_close(fsclg_ctx* c) {
     if (B.d_xacc) hipFree(B.d_xacc);
     if (B.d_xcnt) hipFree(B.d_xcnt);
     for (void* p : {(void*)B.p_cells, (void*)B.p_out, (void*)B.p_epos, (void*)B.p_cell_ep, (void*)B.p_ctrace,
-                    (void*)B.p_cmchunks})
+                    (void*)B.p_cmchunks, (void*)B.p_curve})
       if (p) hipHostFree(p);
     hipEventDestroy(B.ev0);
     hipEventDestroy(B.ev1);
@@ -4571,6 +4640,7 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
   Batch& B = c->batch[batch];
   if (!B.pending) return set_err(FSCLG_E_STATE, "batch not submitted");
   if (B.cm_pending) return set_err(FSCLG_E_STATE, "the batch holds cell maxima (fsclg_cellmax_wait)");
+  if (B.cv_pending) return set_err(FSCLG_E_STATE, "the batch holds curves (fsclg_curve_wait)");
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   B.pending = false;
@@ -4986,6 +5056,128 @@ double fsclg_cellmax_last_ms(fsclg_ctx* c, int batch) {
   return c && batch >= 0 && batch < NBATCH ? c->batch[batch].cm_ms : 0.0;
 }
 
+// The runs' alpha likelihood curves on the rows a slot holds: fsclg_cellmax_submit's checks, chunks,
+// slot and window null sums; curve_kernel stores one record per position
+int fsclg_curve_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* runs, int n_runs, int eval_range) {
+  if (!c || (!runs && n_runs) || n_runs < 0 || eval_range < 0) return set_err(FSCLG_E_ARG, "runs");
+  if (batch < 0 || batch >= NBATCH || slot < 0 || slot >= NSLOT) return set_err(FSCLG_E_ARG, "batch/slot");
+  if (!c->d_pr0 || !c->d_coef || !c->d_la_coarse) return set_err(FSCLG_E_STATE, "tables/snps/alpha grid not set");
+  if (c->n_coarse > NCOARSE_REF) return set_err(FSCLG_E_ARG, "alpha grid above the curve record");
+  Batch& B = c->batch[batch];
+  if (B.pending) return set_err(FSCLG_E_STATE, "batch not waited for");
+  const int CH = fsclg_profile_chunk();
+  long long total = 0, nchunk = 0;
+  for (int i = 0; i < n_runs; i++) {
+    const fsclg_run_t& r = runs[i];
+    if (r.step < 1 || r.count < 0) return set_err(FSCLG_E_ARG, "run step/count");
+    if (r.chr < 0 || r.chr >= c->n_chr) return set_err(FSCLG_E_ARG, "run chromosome");
+    // (the last position + 64: init_scan_result's de-collision may move a point past it)
+    if (r.count > 0 && (long long)r.start_pos + (long long)(r.count - 1) * r.step > 0x7FFFFFFFll - 64)
+      return set_err(FSCLG_E_ARG, "run position overflow");
+    const long long nwin = std::min((long long)c->h_chr_n[r.chr], 2ll * eval_range + 1);
+    if (nwin / SEG_SPLIT + 4 > (long long)MAXSEG_W) return set_err(FSCLG_E_UNSUPPORTED, "window above the segment table");
+    total += r.count;
+    nchunk += (r.count + CH - 1) / CH;
+  }
+  if (total > 0x7FFFFFFFll / (long long)sizeof(fsclg_curve_t)) return set_err(FSCLG_E_ARG, "too many curve positions");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
+  B.eval_range = eval_range; B.bp_resl = 0; B.cv_ms = 0.0; B.cv_n = (int)total;
+  int r;
+  int nc = 0;
+  if (total > 0) {
+    {  // the window null sums of every window the runs' positions touch, for the slot's rows: one
+       // covering cell per run (a slot another batch already runs on: only what is still missing)
+      std::vector<fsclg_cell_t> cover;
+      for (int i = 0; i < n_runs; i++)
+        if (runs[i].count > 0)
+          cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos,
+                                       runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
+      if (c->slot[slot].users == 0) r = fsclg_slot_windows(c, slot, cover.data(), (int)cover.size(), eval_range);
+      else r = ensure_windows(c, slot, eval_range, cover.data(), (int)cover.size(), &B.wr_memo);
+      if (r) return r;
+    }
+    if ((r = ensure_io(B, 1))) return r;  // (make_params' cells and points: unused by this kernel)
+    if ((r = ensure_pinned(&B.p_curve, &B.curve_cap, (int)total))) return r;
+    if ((r = ensure_pinned(&B.p_cmchunks, &B.cmchunk_cap, (int)nchunk))) return r;
+    int o = 0;
+    for (int i = 0; i < n_runs; i++)
+      for (int k = 0; k < runs[i].count; k += CH) {
+        const int cnt = std::min(CH, runs[i].count - k);
+        B.p_cmchunks[nc++] = ProfChunk{runs[i].chr, runs[i].start_pos + k * runs[i].step, runs[i].step, cnt, o, {0, 0, 0}};
+        o += cnt;
+      }
+    HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
+    Params P = make_params(c, B, slot, nc, 3, eval_range, 0);
+    P.band_th = -1; P.ivc0 = c->c_ivc0; P.n_civ = c->c_civ;  // the walk-window path, as the profile kernel
+    P.civ_max = std::max(P.n_civ - 1, 0); P.n_cache = P.n_civ * P.stride;
+    P.off_thr = P.n_cache * 32; P.off_nul = P.off_thr + (c->n_iv + 1) * 8;
+    P.off_lt = P.off_nul + (c->n_rows + 1) * 8 - 256 * 8;
+    P.off_lx = (P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0) + 15) & ~15;
+    P.ctrace = nullptr;
+    const int dyn = P.lx_on ? P.off_lx + LX_BYTES : P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0);
+    const int stat_m = (int)((sizeof(Smem) + 15) / 16 * 16);
+    unsigned long long* forced = c->d_stats + 24;
+    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
+    if (stat_m + dyn <= LDS_WG) {
+      static unsigned long long attr_set = 0;  // per device (bit = device id)
+      if (c->device >= 64 || !(attr_set >> c->device & 1ull)) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&curve_kernel<true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WG - stat_m), "hipFuncSetAttribute");
+        if (c->device < 64) attr_set |= 1ull << c->device;
+      }
+      hipLaunchKernelGGL((curve_kernel<true>), dim3(nc), dim3(WG), dyn, B.stream, P, (const ProfChunk*)B.p_cmchunks,
+                         B.p_curve, forced);
+    } else {  // tables too large for the LDS copies: every coefficient from the global table
+      hipLaunchKernelGGL((curve_kernel<false>), dim3(nc), dim3(WG), 0, B.stream, P, (const ProfChunk*)B.p_cmchunks,
+                         B.p_curve, forced);
+    }
+    HIPCHK(hipGetLastError(), "launch curve_kernel");
+    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+  }
+  B.nu = nc;
+  B.pending = true; B.cv_pending = true;
+  c->slot[slot].users++;
+  return FSCLG_OK;
+}
+
+int fsclg_curve_wait(fsclg_ctx* c, int batch, fsclg_curve_t* out) {
+  if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
+  Batch& B = c->batch[batch];
+  if (!B.pending || !B.cv_pending) return set_err(FSCLG_E_STATE, "no curves submitted on the batch");
+  if (!out && B.cv_n) return set_err(FSCLG_E_ARG, "out");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  B.pending = false; B.cv_pending = false;
+  c->slot[B.slot].users--;
+  const int n = B.cv_n;
+  if (n == 0) return FSCLG_OK;
+  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  memcpy(out, B.p_curve, sizeof(fsclg_curve_t) * (size_t)n);
+  float ms = 0.f, t0 = 0.f, t1 = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
+  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
+  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
+  B.cv_ms = ms;
+  c->kernel_ms += ms;
+  c->launches++;
+  c->busy.emplace_back((double)t0, (double)t1);
+  int flags = 0;
+  for (int i = 0; i < n; i++) flags |= out[i].pt.flags;
+  if (flags) return set_err(flags & PF_UNSUPPORTED ? FSCLG_E_UNSUPPORTED : FSCLG_E_KERNEL, "device flag");
+  return FSCLG_OK;
+}
+
+double fsclg_curve_last_ms(fsclg_ctx* c, int batch) {
+  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].cv_ms : 0.0;
+}
+
+unsigned long long fsclg_curve_forced(fsclg_ctx* c) {
+  unsigned long long h = 0;
+  if (!c || hipSetDevice(c->device) != hipSuccess) return 0;
+  if (hipMemcpy(&h, c->d_stats + 24, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  return h;
+}
+
 int fsclg_interval_thresholds(double log_ad_step, int n_iv, double* thr) {
   if (!thr || n_iv <= 0 || !(log_ad_step > 0)) return set_err(FSCLG_E_ARG, "thresholds");
   thr[0] = 0.0;
@@ -5039,7 +5231,7 @@ int fsclg_get_stats(fsclg_ctx* c, fsclg_stats_t* st) {
 int fsclg_reset_stats(fsclg_ctx* c) {
   if (!c) return set_err(FSCLG_E_ARG, "stats");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  HIPCHK(hipMemset(c->d_stats, 0, sizeof(unsigned long long) * 24), "hipMemset");
+  HIPCHK(hipMemset(c->d_stats, 0, sizeof(unsigned long long) * 25), "hipMemset");
   for (int k = 0; k < NSLOT; k++) window_time(c, c->slot[k]);  // pending times belong before the reset
   c->kernel_ms = 0.0; c->launches = 0; c->window_ms = 0.0; c->n_dup_cells = 0; c->n_ep_saved = 0; c->n_split_retry = 0;
   c->busy.clear();

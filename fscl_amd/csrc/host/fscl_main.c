@@ -55,7 +55,8 @@ int main(int argc, char **argv) {
   int small_grid_sp = 1000, large_grid_sp = 100000, dont_scan = 0, minimum_obs_depth = 5, n_threads = 1;
   int verbosity = MSG_STATUS, eval_range = 81920, bp_resl = 128, stop = 0, i, n_gpus = 0;
   double permute_nbp = 0.1, alpha_factor = 1.0, scan_width_mb = 1.0;
-  char *permute_mode = NULL, *permute_seed = NULL, *profile_fname = NULL, *scan_mode = NULL;
+  char *permute_mode = NULL, *permute_seed = NULL, *profile_fname = NULL, *scan_mode = NULL, *alpha_fname = NULL;
+  double alpha_drop = 2.0;
   int grid_mode = 0;
   scan_t *s;
   double **fsp;
@@ -91,6 +92,9 @@ int main(int argc, char **argv) {
       {0, "permute-mode", &permute_mode, T_STR, "parity (default: the reference's rand() stream, identical results) or "
                                                 "throughput (counter-based random numbers, trials independent; not identical)"},
       {0, "profile-file", &profile_fname, T_STR, "write CLR and alpha at every -g spaced position (the likelihood profile) to this file"},
+      {0, "alpha-file", &alpha_fname, T_STR, "write every scan point's alpha likelihood curve and support interval to this file"},
+      {0, "alpha-drop", &alpha_drop, T_DBL, "log-likelihood drop of the support interval in --alpha-file (default 2.0; descriptive: "
+                                            "the likelihood is composite)"},
       {0, "scan-mode", &scan_mode, T_STR, "bisection (default: search_maxpos in every cell) or grid (the maximum over each cell's "
                                           "-g spaced positions, in the scan and in the permutation test; one process, parity only)"},
       {0, "permute-seed", &permute_seed, T_STR, "seed of the throughput mode's random numbers (default 0xFD821A6)"},
@@ -174,6 +178,8 @@ int main(int argc, char **argv) {
   }
   if (profile_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --profile-file needs the scan (not with --no-scan).\n"); stop = 1; }
   if (profile_fname && small_grid_sp < 1) { logmsg(MSG_ERROR, "Error: --profile-file needs a positive -g spacing.\n"); stop = 1; }
+  if (alpha_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --alpha-file needs the scan (not with --no-scan).\n"); stop = 1; }
+  if (!(alpha_drop >= 0.0)) { logmsg(MSG_ERROR, "Error: --alpha-drop must be >= 0.\n"); stop = 1; }
   if (large_grid_sp < 1) { logmsg(MSG_ERROR, "Error: coarse grid spacing must be positive.\n"); stop = 1; }
   if (n_gpus < 0) { logmsg(MSG_ERROR, "Error: --n-gpus must be >= 0.\n"); stop = 1; }
   if (permute_mode && strcmp(permute_mode, "parity") && strcmp(permute_mode, "throughput")) {
@@ -253,6 +259,18 @@ int main(int argc, char **argv) {
                pf->n_pts, small_grid_sp, fscl_amd_profile_last_ms(), n_missed, s->n_scan_pts);
         fscl_amd_profile_free(pf);
       }
+    }
+    if (alpha_fname && !(ws && rk && atoi(ws) > 1 && atoi(rk) != 0)) {
+      /* the scan points' alpha curves, of the data as loaded (rank 0 alone); no rand() draw */
+      fscl_amd_curve_t *cv = malloc(sizeof *cv * (size_t)(s->n_scan_pts > 0 ? s->n_scan_pts : 1));
+      int r;
+      if (!cv) logmsg(MSG_FATAL, "fscl: out of memory (alpha curves)");
+      r = fscl_amd_scan_point_curves(s, sm, eval_range, cv);
+      if (r != 0) logmsg(MSG_FATAL, "fscl: alpha curves failed (code %d)", r);
+      fscl_amd_curve_output(alpha_fname, s, cv, s->n_scan_pts, alpha_drop, prepend_label);
+      logmsg(MSG_STATUS, "Alpha curves: %d points, kernel %.3f ms, %llu walks summed sequentially for the curves alone\n",
+             s->n_scan_pts, fscl_amd_curve_last_ms(), fscl_amd_curve_forced());
+      free(cv);
     }
     if (n_permute > 0 && grid_mode)
       fscl_amd_scan_permute_grid(s, sm, n_permute, permute_nbp, eval_range, small_grid_sp, large_grid_sp, scan_width_mb);

@@ -2565,6 +2565,176 @@ int fscl_amd_site_rows(scan_t *s, sm_ptable_t *sm, uint32_t *out) {
   return s->n_snps;
 }
 
+/* ------------------------------------------------------ alpha likelihood curves
+   Every composite likelihood search_maxalpha evaluates at a position (fsclg_curve_submit), on
+   the data as loaded.  Positions go to the device as runs of one; the local devices take
+   contiguous shares balanced by window size, every device is submitted to before the first is
+   waited for (the records are those of one device: a record depends on its position alone). */
+static double g_curve_ms;
+double fscl_amd_curve_last_ms(void) { return g_curve_ms; }
+
+unsigned long long fscl_amd_curve_forced(void) {
+  unsigned long long n = 0;
+  int l;
+  for (l = 0; l < D.n_dev; l++) n += fsclg_curve_forced(D.ctx[l]);
+  return n;
+}
+
+int fscl_amd_scan_curves(scan_t *s, sm_ptable_t *sm, int eval_range, const int *chr, const int *pos, int n,
+                         fscl_amd_curve_t *out) {
+  fsclg_run_t *runs;
+  double *cost;
+  int lo[FH_MAX_DEV], hi[FH_MAX_DEV], i, l, k, r = FSCLG_OK;
+  if (!s || !sm || n < 0 || (n && (!chr || !pos || !out))) return FSCLG_E_ARG;
+  if (D.world > 1 && D.rank != 0) return FSCLG_OK; /* rank 0 alone evaluates, as the profile */
+  prepare(s, sm);
+  for (i = 0; i < n; i++)
+    if (chr[i] < 0 || chr[i] >= D.n_chr) return FSCLG_E_ARG;
+  set_original_rows();
+  g_curve_ms = 0.;
+  runs = fh_malloc(sizeof(fsclg_run_t) * (n ? n : 1), "curve runs");
+  cost = fh_malloc(sizeof(double) * (n ? n : 1), "cost");
+  for (i = 0; i < n; i++) {
+    runs[i].chr = chr[i]; runs[i].start_pos = pos[i]; runs[i].step = 1; runs[i].count = 1;
+    cost[i] = window_cost(chr[i], eval_range);
+  }
+  for (l = 0; l < D.n_dev; l++) {
+    if (D.n_dev <= 1) { lo[l] = 0; hi[l] = n; }
+    else fscl_amd_partition(cost, n, l, D.n_dev, &lo[l], &hi[l]);
+  }
+  for (l = 0; l < D.n_dev && r == FSCLG_OK; l++) {
+    DBG("curves: device %d, positions [%d, %d)\n", D.dev[l], lo[l], hi[l]);
+    r = fsclg_curve_submit(D.ctx[l], 0, 0, runs + lo[l], hi[l] - lo[l], eval_range); /* (the runs are copied) */
+  }
+  for (k = 0; k < l; k++) {
+    int rw;
+    double ms;
+    if (k == l - 1 && r != FSCLG_OK) break; /* the submit that failed left nothing to wait for */
+    rw = fsclg_curve_wait(D.ctx[k], 0, out + lo[k]);
+    ms = fsclg_curve_last_ms(D.ctx[k], 0);
+    if (r == FSCLG_OK) r = rw;
+    if (ms > g_curve_ms) g_curve_ms = ms; /* the devices run side by side */
+  }
+  free(runs); free(cost);
+  return r;
+}
+
+int fscl_amd_scan_point_curves(scan_t *s, sm_ptable_t *sm, int eval_range, fscl_amd_curve_t *out) {
+  int *cp, i, r, n;
+  if (!s || !sm || !s->scan_pts || s->n_scan_pts < 0) return FSCLG_E_ARG;
+  n = s->n_scan_pts;
+  cp = fh_malloc(sizeof(int) * 2 * (size_t)(n ? n : 1), "curve positions");
+  for (i = 0; i < n; i++) { cp[i] = s->scan_pts[i].chr; cp[n + i] = s->scan_pts[i].sweep_pos; }
+  r = fscl_amd_scan_curves(s, sm, eval_range, cp, cp + n, n, out);
+  free(cp);
+  return r;
+}
+
+/* the test handle of fsclg_curve_submit / fsclg_curve_wait on the first device, for any runs: on
+   the uploaded rows (rows NULL: slot 0, batch 0) or on `rows` (slot 1, batch 1), as
+   fscl_amd_cellmax_runs */
+int fscl_amd_curve_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int n_runs, int eval_range,
+                        const uint32_t *rows, fscl_amd_curve_t *out) {
+  int r, slot = 0;
+  if (!s || !sm || (!runs && n_runs) || n_runs < 0) return FSCLG_E_ARG;
+  prepare(s, sm);
+  g_curve_ms = 0.;
+  if (rows) {
+    double *nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
+    int i;
+    for (i = 0; i < s->n_snps; i++)
+      if (rows[i] >= (uint32_t)D.rm.n_dev_rows) { free(nul); return FSCLG_E_ARG; }
+    chr_null_sums_32(rows, nul);
+    slot = 1;
+    r = fsclg_slot_set_rows(D.ctx[0], slot, rows, nul);
+    free(nul);
+    if (r != FSCLG_OK) return r;
+  } else {
+    set_original_rows();
+  }
+  r = fsclg_curve_submit(D.ctx[0], slot, slot, runs, n_runs, eval_range);
+  if (r != FSCLG_OK) return r;
+  r = fsclg_curve_wait(D.ctx[0], slot, out);
+  g_curve_ms = fsclg_curve_last_ms(D.ctx[0], slot);
+  return r;
+}
+
+/* the curve's distinct alphas in ascending order: idx[0 .. m) index la[] / sm[], an alpha
+   evaluated twice (a coarse value that is also in the refine list) kept once, its first
+   evaluation; *imax: where in idx the argmax is -- the first strict maximum of sm in evaluation
+   order from -DBL_MAX, as search_maxalpha's two loops find it -- or -1 if no value beat
+   -DBL_MAX (NaN never does).  Entries whose alpha is NaN are left out. */
+static int curve_order(const fscl_amd_curve_t *c, int *idx, int *imax) {
+  int n = c->n_coarse + c->n_refine, m = 0, k, j, best = -1;
+  double bv = -DBL_MAX;
+  if (n > FSCLG_CURVE_MAX) n = FSCLG_CURVE_MAX;
+  if (n < 0) n = 0;
+  for (k = 0; k < n; k++) {
+    if (c->sm[k] > bv) { bv = c->sm[k]; best = k; }
+    if (c->la[k] != c->la[k]) continue;
+    for (j = 0; j < m && c->la[idx[j]] != c->la[k]; j++) {}
+    if (j < m) continue; /* the same candidate again */
+    for (j = m; j > 0 && c->la[idx[j - 1]] > c->la[k]; j--) idx[j] = idx[j - 1];
+    idx[j] = k;
+    m++;
+  }
+  *imax = -1;
+  for (j = 0; best >= 0 && j < m; j++)
+    if (c->la[idx[j]] == c->la[best]) *imax = j;
+  return m;
+}
+
+int fscl_amd_curve_support(const fscl_amd_curve_t *c, double drop, double *la_lo, double *la_hi, int *open_lo,
+                           int *open_hi) {
+  int idx[FSCLG_CURVE_MAX], imax, m, a, b;
+  double cut, nan_ = 0.0;
+  nan_ = nan_ / nan_;
+  if (la_lo) *la_lo = nan_;
+  if (la_hi) *la_hi = nan_;
+  if (open_lo) *open_lo = 0;
+  if (open_hi) *open_hi = 0;
+  if (!c || !(drop >= 0.0)) return -1;
+  m = curve_order(c, idx, &imax);
+  if (imax < 0) return 0;
+  cut = c->sm[idx[imax]] - drop;
+  for (a = imax; a > 0 && c->sm[idx[a - 1]] >= cut; a--) {}   /* (a NaN fails the comparison) */
+  for (b = imax; b < m - 1 && c->sm[idx[b + 1]] >= cut; b++) {}
+  if (la_lo) *la_lo = c->la[idx[a]];
+  if (la_hi) *la_hi = c->la[idx[b]];
+  if (open_lo) *open_lo = a == 0;
+  if (open_hi) *open_hi = b == m - 1;
+  return 1;
+}
+
+void fscl_amd_curve_output(const char *fname, const scan_t *s, const fscl_amd_curve_t *curves, int n, double drop,
+                           const char *label) {
+  FILE *f = stdout;
+  int i, j;
+  if (!curves || !s) return;
+  if (fname) {
+    f = fopen(fname, "w");
+    if (!f) { fprintf(stderr, "Can't open alpha curve file \"%s\" (%s)", fname, strerror(errno)); return; }
+  }
+  for (i = 0; i < n; i++) {
+    const fscl_amd_curve_t *c = curves + i;
+    const char *name = s->chr_limits[c->pt.chr].name;
+    int idx[FSCLG_CURVE_MAX], imax, ol, oh;
+    double lo, hi;
+    const int m = curve_order(c, idx, &imax);
+    for (j = 0; j < m; j++) {
+      if (label) fprintf(f, "%s\t", label);
+      fprintf(f, "%s\t%d\t%1.3e\t%1.2f\t%s\n", name, c->pt.sweep_pos, exp(c->la[idx[j]]),
+              2.0 * (c->sm[idx[j]] - c->pt.null_logl), j == imax ? "*" : "-");
+    }
+    if (label) fprintf(f, "%s\t", label);
+    if (fscl_amd_curve_support(c, drop, &lo, &hi, &ol, &oh) == 1)
+      fprintf(f, "%s\t%d\tsupport\t%1.3e\t%1.3e\t%d\t%d\n", name, c->pt.sweep_pos, exp(lo), exp(hi), ol, oh);
+    else
+      fprintf(f, "%s\t%d\tsupport\tNA\tNA\t0\t0\n", name, c->pt.sweep_pos);
+  }
+  if (fname) fclose(f);
+}
+
 /* the points fscl_amd_scan_chromosome_grid made last: fscl_amd_scan_permute_grid tests only
    those, with the same spacings, on the same data (D.key) */
 static struct {

@@ -331,6 +331,52 @@ int fscl_amd_cellmax_runs(scan_t *scan_obj, sm_ptable_t *sm_p, const fsclg_run_t
 double fscl_amd_cellmax_last_ms(void);
 int fscl_amd_site_rows(scan_t *scan_obj, sm_ptable_t *sm_p, uint32_t *out);
 
+/* ---- alpha likelihood curves (--alpha-file) ---------------------------------------
+   The alpha axis of the likelihood surface at a position: every composite likelihood
+   search_maxalpha (sm-search.c:269-300) evaluates there, in its evaluation order -- la[k] the
+   log alpha, sm[k] what sm_likelihood returns for it, k < n_coarse + n_refine (11 coarse values,
+   then the refine list around the coarse winner); pt is the point init_scan_result +
+   search_maxalpha give at the position (fscl_amd_profile_runs' point, bit for bit), and the first
+   strict maximum of sm[] in order is (pt.sm_logl, pt.lalpha).  A record is fsclg_curve_t.
+
+   fscl_amd_scan_curves: the curves at n (chromosome index, position) pairs, on the data as loaded
+   (also after scan_permute), on the device context scan_chromosome uses; several local devices
+   take contiguous shares balanced by window size (identical results); with several ranks, rank 0
+   alone evaluates (the others return FSCLG_OK and leave out untouched).  Returns a fsclg status
+   code.  fscl_amd_scan_point_curves: the curve of every scan point at its own sweep_pos, after
+   scan_chromosome or fscl_amd_scan_chromosome_grid; out holds n_scan_pts records.
+
+   fscl_amd_curve_support (host only): the evaluated alphas sorted, an alpha evaluated twice kept
+   once; the connected run around the argmax whose sm >= sm_max - drop: *la_lo / *la_hi its least
+   and greatest log alpha, *open_lo / *open_hi set when the run reaches the lowest / highest
+   evaluated alpha (the interval may extend past the search range).  A NaN value breaks the run.
+   Returns 1, 0 if no value beat the initial -DBL_MAX (all NaN: *la_lo = *la_hi = NaN), -1 for a
+   NULL curve or a drop that is negative or NaN.  With drop = 2 the interval is the usual
+   2-log-likelihood-unit support interval; the likelihood is a COMPOSITE one (sites are not
+   independent), so it describes the curve's shape and is not a calibrated confidence interval.
+
+   fscl_amd_curve_output (fname NULL: stdout): per curve, one row per distinct alpha, ascending:
+     [label TAB] chromosome TAB position TAB alpha (%1.3e) TAB 2 * (sm - null_logl) (%1.2f) TAB mark
+   mark is * on the argmax row and - elsewhere; then one summary row
+     [label TAB] chromosome TAB position TAB support TAB alpha_lo TAB alpha_hi TAB open_lo TAB open_hi
+   (alpha_lo, alpha_hi %1.3e, or NA NA 0 0 when there is no interval). */
+typedef fsclg_curve_t fscl_amd_curve_t;
+int fscl_amd_scan_curves(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, const int *chr, const int *pos, int n,
+                         fscl_amd_curve_t *out);
+int fscl_amd_scan_point_curves(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, fscl_amd_curve_t *out);
+int fscl_amd_curve_support(const fscl_amd_curve_t *curve, double drop, double *la_lo, double *la_hi, int *open_lo,
+                           int *open_hi);
+void fscl_amd_curve_output(const char *fname, const scan_t *scan_obj, const fscl_amd_curve_t *curves, int n,
+                           double drop, const char *prepend_label);
+/* fsclg_curve_submit / fsclg_curve_wait on the first device, for any runs (the device entry's
+   test handle): out holds sum(count) records; rows as for fscl_amd_cellmax_runs.
+   fscl_amd_curve_last_ms: the curve kernel's milliseconds of the last evaluation (the slowest
+   device's); fscl_amd_curve_forced: fsclg_curve_forced summed over the devices. */
+int fscl_amd_curve_runs(scan_t *scan_obj, sm_ptable_t *sm_p, const fsclg_run_t *runs, int n_runs, int eval_range,
+                        const uint32_t *rows, fscl_amd_curve_t *out);
+double fscl_amd_curve_last_ms(void);
+unsigned long long fscl_amd_curve_forced(void);
+
 /* release the device context (tables / snps) */
 void fscl_amd_shutdown(void);
 

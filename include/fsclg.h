@@ -250,6 +250,34 @@ int fsclg_cellmax_submit(fsclg_ctx *c, int batch, int slot, const fsclg_run_t *r
 int fsclg_cellmax_wait(fsclg_ctx *c, int batch, fsclg_point_t *out);
 double fsclg_cellmax_last_ms(fsclg_ctx *c, int batch);
 
+/* Alpha likelihood curves: every composite likelihood search_maxalpha (sm-search.c:269-300)
+   evaluates at a position -- the 11 coarse alphas, then the refine list around the coarse winner
+   (or around LOG_AD_MAX when no coarse candidate beat the initial -DBL_MAX) -- in the
+   reference's evaluation order.  sm[k] is what sm_likelihood (sm-search.c:105-150) returns for
+   la[k]: the null sum plus the terms in walk order, the exact sequential sum for every entry,
+   also for the candidates whose value the argmax never needed exactly; entries past
+   n_coarse + n_refine are zero.  pt is the point fsclg_profile gives at the position, on the
+   same rows, bit for bit: the first strict maximum of sm[] in order, from the reference's
+   -DBL_MAX / LOG_AD_MAX state, is (pt.sm_logl, pt.lalpha).
+   fsclg_curve_submit / fsclg_curve_wait take runs, batches, slots and window null sums exactly
+   as fsclg_cellmax_submit / fsclg_cellmax_wait do, and give one record per position, in run
+   order, then position order (out holds sum(count) records).  Further errors: FSCLG_E_ARG for an
+   alpha grid with more than 11 coarse values.  fsclg_curve_last_ms: the kernel's own time (HIP
+   events) of the batch's last curve launch.  fsclg_curve_forced: the walks summed sequentially
+   only because a curve wants every value exact (beyond n_slow, which still counts those an
+   argmax needed), since fsclg_open or fsclg_reset_stats. */
+#define FSCLG_CURVE_MAX 27 /* 11 coarse + 16 refine candidates at most */
+typedef struct {
+  fsclg_point_t pt;
+  int32_t n_coarse, n_refine;
+  double la[FSCLG_CURVE_MAX];
+  double sm[FSCLG_CURVE_MAX];
+} fsclg_curve_t;
+int fsclg_curve_submit(fsclg_ctx *c, int batch, int slot, const fsclg_run_t *runs, int n_runs, int eval_range);
+int fsclg_curve_wait(fsclg_ctx *c, int batch, fsclg_curve_t *out);
+double fsclg_curve_last_ms(fsclg_ctx *c, int batch);
+unsigned long long fsclg_curve_forced(fsclg_ctx *c);
+
 /* the exact interval thresholds the kernel uses in place of spline_interpolate's
    division (sm-spline.c:52): thr[j] = least double x with
    (int)((x - LOG_AD_MIN) / log_ad_step) >= j, for j = 1..n_iv (thr has n_iv+1 slots) */

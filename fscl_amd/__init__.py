@@ -30,6 +30,8 @@ __all__ = [
     "scan_chromosome_grid", "scan_permute_grid", "cellmax_runs", "cellmax_last_ms", "site_rows",
     "scan_curves", "scan_point_curves", "curve_runs", "curve_support", "curve_output", "curve_last_ms",
     "curve_forced", "CURVE_DTYPE",
+    "scan_sites", "scan_point_sites", "sites_summary", "sites_output", "sites_last_ms", "sites_cap", "SitesT",
+    "SITES_DTYPE", "SITE_REQ_DTYPE", "SITES_SUMMARY_DTYPE",
 ]
 
 ROOT = Path(__file__).resolve().parent
@@ -105,6 +107,11 @@ class RunT(C.Structure):  # fsclg_run_t
     _fields_ = [("chr", C.c_int32), ("start_pos", C.c_int32), ("step", C.c_int32), ("count", C.c_int32)]
 
 
+class SitesT(C.Structure):  # fscl_amd_sites_t
+    _fields_ = [("n", C.c_int), ("point", C.POINTER(C.c_int)), ("hdr", C.c_void_p), ("terms", C.POINTER(C.c_double)),
+                ("n_terms", C.c_size_t)]
+
+
 class PointT(C.Structure):  # fsclg_point_t
     _fields_ = [("chr", C.c_int32), ("nearest_snp", C.c_int32), ("sweep_pos", C.c_int32), ("n_snps", C.c_int32),
                 ("window_start", C.c_int32), ("window_end", C.c_int32), ("flags", C.c_int32), ("cost", C.c_uint32),
@@ -138,6 +145,9 @@ EXPORTS = [
     "fsclg_curve_submit", "fsclg_curve_wait", "fsclg_curve_last_ms", "fsclg_curve_forced",
     "fscl_amd_scan_curves", "fscl_amd_scan_point_curves", "fscl_amd_curve_support", "fscl_amd_curve_output",
     "fscl_amd_curve_runs", "fscl_amd_curve_last_ms", "fscl_amd_curve_forced",
+    "fsclg_sites_submit", "fsclg_sites_wait", "fsclg_sites_last_ms", "fsclg_sites_cap",
+    "fscl_amd_scan_sites", "fscl_amd_scan_point_sites", "fscl_amd_sites_free", "fscl_amd_sites_summary",
+    "fscl_amd_sites_output", "fscl_amd_sites_last_ms",
 ]
 
 
@@ -207,6 +217,13 @@ def _load() -> C.CDLL:
         "fscl_amd_curve_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(RunT), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
         "fscl_amd_curve_last_ms": (C.c_double, []),
         "fscl_amd_curve_forced": (C.c_ulonglong, []),
+        "fscl_amd_scan_sites": (C.c_int, [P(ScanT), P(SmPtableT), C.c_int, C.c_void_p, C.c_int, P(SitesT)]),
+        "fscl_amd_scan_point_sites": (C.c_int, [P(ScanT), P(SmPtableT), C.c_int, C.c_int, P(SitesT)]),
+        "fscl_amd_sites_free": (None, [P(SitesT)]),
+        "fscl_amd_sites_summary": (None, [P(ScanT), P(SitesT), C.c_void_p]),
+        "fscl_amd_sites_output": (None, [C.c_char_p, P(ScanT), P(SitesT), C.c_char_p]),
+        "fscl_amd_sites_last_ms": (C.c_double, []),
+        "fsclg_sites_cap": (C.c_size_t, []),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -575,6 +592,89 @@ def curve_forced() -> int:
     return int(get_lib().fscl_amd_curve_forced())
 
 
+# fsclg_site_req_t: one walk of sm_likelihood -- chromosome index, position, log alpha
+SITE_REQ_DTYPE = np.dtype([("chr", "i4"), ("pos", "i4"), ("lalpha", "f8")])
+# fsclg_site_hdr_t: the walk's point (lalpha the request's, sm_logl the sequential sum of null_logl and
+# the terms), the terms left / right of the nearest SNP, len = 0 or 1 + nl + nr, and where the walk's
+# terms start in the flat terms array; term k belongs to site nearest_snp (k = 0), nearest_snp - k
+# (k <= nl) or nearest_snp + k - nl
+SITES_DTYPE = np.dtype([("pt", _POINT_RAW), ("nl", "i4"), ("nr", "i4"), ("len", "i4"), ("pad", "i4"), ("off", "u8")])
+assert SITES_DTYPE.itemsize == _POINT_RAW.itemsize + 24
+# fscl_amd_sites_summary_t (include/fscl_amd.h); top_term / top_share NaN where the file prints NA
+SITES_SUMMARY_DTYPE = np.dtype([("n_sites", "i4"), ("first_pos", "i4"), ("last_pos", "i4"), ("n_pos", "i4"),
+                                ("n_neg", "i4"), ("top_pos", "i4"), ("n_half", "i4"), ("pad", "i4"),
+                                ("top_term", "f8"), ("top_share", "f8")])
+
+
+def _sites_take(res: SitesT):
+    """(headers, terms) copied out of a native result, which is released."""
+    n, nt = int(res.n), int(res.n_terms)
+    hdr = np.zeros(n, dtype=SITES_DTYPE)
+    terms = np.zeros(nt, dtype=np.float64)
+    if n:
+        C.memmove(hdr.ctypes.data, res.hdr, n * SITES_DTYPE.itemsize)
+    if nt:
+        C.memmove(terms.ctypes.data, res.terms, nt * 8)
+    get_lib().fscl_amd_sites_free(C.byref(res))
+    return hdr, terms
+
+
+def scan_sites(scan, tables, requests, eval_range: int = 81920):
+    """The per-site likelihood terms of one sm_likelihood walk per (chromosome index, position, log alpha)
+    of ``requests``, on the data as loaded (include/fscl_amd.h): (headers, terms) -- a SITES_DTYPE array
+    in the given order and the flat float64 array its ``off`` / ``len`` index, in walk order."""
+    req = np.zeros(len(requests), dtype=SITE_REQ_DTYPE)
+    for q, r in zip(req, requests):
+        q["chr"], q["pos"], q["lalpha"] = int(r[0]), int(r[1]), float(r[2])
+    res = SitesT()
+    _curve_check(get_lib().fscl_amd_scan_sites(scan, tables, int(eval_range), req.ctypes.data if len(req) else None,
+                                               len(req), C.byref(res)), "fscl_amd_scan_sites")
+    return _sites_take(res)
+
+
+def scan_point_sites(scan, tables, top: int = 10, eval_range: int = 81920):
+    """The walks of the scan points at their own sweep_pos and lalpha (after scan_chromosome or
+    scan_chromosome_grid): the ``top`` points of greatest CLR (0: every point), in points() order."""
+    res = SitesT()
+    _curve_check(get_lib().fscl_amd_scan_point_sites(scan, tables, int(eval_range), int(top), C.byref(res)),
+                 "fscl_amd_scan_point_sites")
+    return _sites_take(res)
+
+
+def _sites_view(hdr, terms):
+    h = np.ascontiguousarray(hdr, dtype=SITES_DTYPE)
+    t = np.ascontiguousarray(terms, dtype=np.float64)
+    if len(h) and int((h["off"] + h["len"].astype(np.uint64)).max()) > len(t):
+        raise ValueError("a header's terms lie past the terms array")
+    res = SitesT(len(h), None, h.ctypes.data if len(h) else None,
+                 t.ctypes.data_as(C.POINTER(C.c_double)) if len(t) else None, len(t))
+    return res, (h, t)  # (the arrays stay alive with the view)
+
+
+def sites_summary(scan, hdr, terms) -> np.ndarray:
+    """The footprint summary of each walk (include/fscl_amd.h): a SITES_SUMMARY_DTYPE array.  Host only."""
+    res, keep = _sites_view(hdr, terms)
+    out = np.zeros(max(res.n, 1), dtype=SITES_SUMMARY_DTYPE)
+    get_lib().fscl_amd_sites_summary(scan, C.byref(res), out.ctypes.data)
+    return out[:res.n]
+
+
+def sites_output(path, scan, hdr, terms, label=None) -> None:
+    """The --sites-file format (include/fscl_amd.h, README): per walk one row per site in ascending
+    position, then one summary row.  Host only."""
+    res, keep = _sites_view(hdr, terms)
+    get_lib().fscl_amd_sites_output(_b(path), scan, C.byref(res), _b(label))
+
+
+def sites_last_ms() -> float:
+    return float(get_lib().fscl_amd_sites_last_ms())
+
+
+def sites_cap() -> int:
+    """Terms per launch of the term kernel ($FSCLG_SITES_CAP)."""
+    return int(get_lib().fsclg_sites_cap())
+
+
 def get_stats() -> dict:
     st = Stats()
     get_lib().fscl_amd_get_stats(C.byref(st))
@@ -659,7 +759,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         permute_nbp=0.1, asc_depth=0, asc_min_freq=1, ascbias_background_only=False, include_invariant=False,
         force_neutral=False, minimum_depth=5, large_grid_sp=100000, scan_width_mb=1.0, max_only=False,
         label=None, eval_range=81920, bp_resl=128, verbosity=1, permute_mode="parity", permute_seed=0xFD821A6,
-        profile_file=None, small_grid_sp=1000, scan_mode="bisection", alpha_file=None, alpha_drop=2.0):
+        profile_file=None, small_grid_sp=1000, scan_mode="bisection", alpha_file=None, alpha_drop=2.0,
+        sites_file=None, sites_top=10):
     """The fscl main() pipeline (fscl.c:316-337) in-process; returns the scan_t
     pointer (points(scan) reads the results).  permute_mode "throughput": the
     counter-based permutation test (set_permute_mode).  scan_mode "grid": the CLI's
@@ -668,6 +769,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         raise ValueError("scan_mode must be bisection or grid")
     if scan_mode == "grid" and permute_mode != "parity":
         raise ValueError("scan_mode grid runs on the parity stream only")
+    if int(sites_top) < 0:
+        raise ValueError("sites_top must be >= 0")
     get_lib().configure_logmsg(int(verbosity))
     set_permute_mode(permute_mode, permute_seed)
     init_log_table()
@@ -687,6 +790,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         profile_output(profile_file, scan, scan_profile(scan, tab, eval_range, small_grid_sp, large_grid_sp), label)
     if alpha_file is not None:  # the CLI's --alpha-file: the scan points' alpha likelihood curves
         curve_output(alpha_file, scan, scan_point_curves(scan, tab, eval_range), alpha_drop, label)
+    if sites_file is not None:  # the CLI's --sites-file: the per-site terms of the scan points' walks
+        sites_output(sites_file, scan, *scan_point_sites(scan, tab, sites_top, eval_range), label)
     if n_permute > 0 and scan_mode == "grid":
         scan_permute_grid(scan, tab, n_permute, permute_nbp, eval_range, small_grid_sp, large_grid_sp, scan_width_mb)
     elif n_permute > 0:

@@ -2516,6 +2516,81 @@ curve_kernel(Params P, const ProfChunk* __restrict__ chunks, fsclg_curve_t* __re
   profile_body<LDS, false, true>(S, P, chunks, curve, forced);
 }
 
+// ------------------------------------------------------------ per-site terms
+// The terms of single walks (fsclg_sites_submit): no alpha search.  Pass 0, one workgroup per
+// request: wave 0 does init_scan_result, waves 0 and 1 find the walk's left and right bound with a
+// 65-way search of the direct predicate log(alpha d) > 4 (the request's alpha is any double, so
+// Params::dfail, indexed by the grid's alphas, does not apply; logt is nondecreasing in |d|, so the
+// predicate is monotone on either side as walk_bounds_g's), and wave 0 forms the exact sequential
+// sum with walk_sequential and stores the header.  Pass 1, after the host's prefix sum over the
+// lengths, one workgroup per task (a piece of one walk): every thread strides over k and stores
+// term_dev(walk_index(k)) -- the very expression walk_sequential adds -- with one plain 8-byte
+// vector store per lane, consecutive lanes to consecutive doubles of the launch's staging area
+// (host memory).  Coefficients, thresholds and null values come from the global tables (LDS =
+// false): a walk is visited once, there is no prologue to amortise.
+struct SiteTask {
+  int32_t nearest, nl, sweep, k0, k1, pad;  // terms [k0, k1) of the walk ...
+  double la;
+  unsigned long long dst;                   // ... to staging[dst .. dst + k1 - k0)
+};
+struct SitesSmem {
+  Pt pt;
+  Walk w;
+};
+
+__global__ void __launch_bounds__(WG)
+sites_kernel(Params P, int pass, const fsclg_site_req_t* __restrict__ req, fsclg_site_hdr_t* __restrict__ hdr,
+             const SiteTask* __restrict__ tasks, double* __restrict__ staging) {
+  __shared__ SitesSmem S;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = (int)blockIdx.x;
+  if (b >= P.n_cells) return;
+  if (pass == 1) {
+    const SiteTask t = tasks[b];
+    double* __restrict__ dst = staging + t.dst;
+    for (int k = t.k0 + tid; k < t.k1; k += WG)
+      dst[k - t.k0] = term_dev<false>(walk_index(k, t.nearest, t.nl), t.sweep, t.la, S, P);
+    return;
+  }
+  const fsclg_site_req_t r = req[b];
+  if (wave == 0) init_point_wave(S.pt, r.chr, r.pos, P, lane);
+  __syncthreads();
+  if (wave < 2) {  // wave 0: the left bound, wave 1: the right one
+    const int near = S.pt.nearest, sweep = S.pt.sweep;
+    const double la = r.lalpha;
+    auto outside = [&](int i) { return log_ad_of(i, sweep, la, P) > LOG_AD_MAX; };
+    int lo = 0, hi = 1;
+    bool ok1 = false;
+    if (wave == 0) { lo = S.pt.wstart - 1; hi = near; }
+    else {
+      ok1 = near + 1 <= S.pt.wend && !outside(near + 1);
+      if (ok1) { lo = near + 1; hi = S.pt.wend + 1; }
+    }
+    const int e = group_search<64>(lo, hi, lane, [&](int m) { return outside(m) != (wave == 1); });
+    if (lane == 0) {
+      if (wave == 0) { S.w.len = outside(near) ? 0 : 1; S.w.nl = near - e; }
+      else S.w.nr = (ok1 ? e - 1 : near) - near;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    if (S.w.len) S.w.len = 1 + S.w.nl + S.w.nr;
+    else { S.w.nl = 0; S.w.nr = 0; }
+    S.w.p = 0; S.w.la = r.lalpha;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const double sm = walk_sequential<false>(S, S.w, S.pt, P, lane);
+    if (lane == 0) {  // one store of the header (host memory: no read-modify-write)
+      fsclg_site_hdr_t h;
+      S.pt.la = r.lalpha; S.pt.sm = sm; S.pt.clr = 2.0 * (sm - S.pt.N);
+      write_point(h.pt, S.pt);
+      h.nl = S.w.nl; h.nr = S.w.nr; h.len = S.w.len; h.pad = 0; h.off = 0;
+      hdr[b] = h;
+    }
+  }
+}
+
 // ------------------------------------------------------------ window null sums
 // init_scan_result's window sum (scan-chromosome.c:92-94) for every window start of the
 // chromosomes longer than the window: acc = 0.0; acc += null_logl[i] for i = ws..ws+W-1,
@@ -3115,6 +3190,17 @@ struct Batch {
   int cv_n = 0;                     // records of the submitted launch
   bool cv_pending = false;
   double cv_ms = 0.0;               // kernel time of the batch's last curve launch
+  // fsclg_sites_submit: requests and headers (pinned; read / written by pass 0), the tasks and the
+  // staging area of one term launch (pinned; read / written by pass 1)
+  fsclg_site_req_t* p_sreq = nullptr;
+  fsclg_site_hdr_t* p_shdr = nullptr;
+  SiteTask* p_stasks = nullptr;
+  double* p_sterms = nullptr;
+  int sreq_cap = 0, shdr_cap = 0, stask_cap = 0, sterm_cap = 0;
+  int st_n = 0;                     // requests of the submitted call
+  bool st_pending = false;
+  bool st_synced = false;           // the header launch has been waited for (a wait that only sized the buffer)
+  double st_ms = 0.0;               // kernel time of the batch's last sites call
 };
 
 struct fsclg_ctx {
@@ -3323,7 +3409,8 @@ int fsclg_close(fsclg_ctx* c) {
     if (B.d_xacc) hipFree(B.d_xacc);
     if (B.d_xcnt) hipFree(B.d_xcnt);
     for (void* p : {(void*)B.p_cells, (void*)B.p_out, (void*)B.p_epos, (void*)B.p_cell_ep, (void*)B.p_ctrace,
-                    (void*)B.p_cmchunks, (void*)B.p_curve})
+                    (void*)B.p_cmchunks, (void*)B.p_curve, (void*)B.p_sreq, (void*)B.p_shdr, (void*)B.p_stasks,
+                    (void*)B.p_sterms})
       if (p) hipHostFree(p);
     hipEventDestroy(B.ev0);
     hipEventDestroy(B.ev1);
@@ -4641,6 +4728,7 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
   if (!B.pending) return set_err(FSCLG_E_STATE, "batch not submitted");
   if (B.cm_pending) return set_err(FSCLG_E_STATE, "the batch holds cell maxima (fsclg_cellmax_wait)");
   if (B.cv_pending) return set_err(FSCLG_E_STATE, "the batch holds curves (fsclg_curve_wait)");
+  if (B.st_pending) return set_err(FSCLG_E_STATE, "the batch holds site terms (fsclg_sites_wait)");
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   B.pending = false;
@@ -5176,6 +5264,150 @@ unsigned long long fsclg_curve_forced(fsclg_ctx* c) {
   if (!c || hipSetDevice(c->device) != hipSuccess) return 0;
   if (hipMemcpy(&h, c->d_stats + 24, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) return 0;
   return h;
+}
+
+// ------------------------------------------------------------ per-site terms (host side)
+// terms per launch of sites_kernel's pass 1 = doubles of the pinned staging area.  Default 2^22
+// (32 MiB): a launch of that size amortises its launch and synchronisation, and the area stays small
+// beside the row and window buffers; tests force it down to 1 to cut walks across launches
+size_t fsclg_sites_cap(void) {
+  const char* e = getenv("FSCLG_SITES_CAP");
+  long long v = e ? atoll(e) : (1ll << 22);
+  if (v < 1) v = 1;
+  if (v > (1ll << 27)) v = 1ll << 27;
+  return (size_t)v;
+}
+constexpr int SITE_TASK_MAX = 16 * WG;  // terms per workgroup of pass 1: a long walk spreads over the CUs
+
+int fsclg_sites_submit(fsclg_ctx* c, int batch, int slot, const fsclg_site_req_t* req, int n_req, int eval_range) {
+  if (!c || (!req && n_req) || n_req < 0 || eval_range < 0) return set_err(FSCLG_E_ARG, "requests");
+  if (batch < 0 || batch >= NBATCH || slot < 0 || slot >= NSLOT) return set_err(FSCLG_E_ARG, "batch/slot");
+  if (!c->d_pr0 || !c->d_coef) return set_err(FSCLG_E_STATE, "tables/snps not set");
+  Batch& B = c->batch[batch];
+  if (B.pending) return set_err(FSCLG_E_STATE, "batch not waited for");
+  for (int i = 0; i < n_req; i++) {
+    if (req[i].chr < 0 || req[i].chr >= c->n_chr) return set_err(FSCLG_E_ARG, "request chromosome");
+    // (+ 64: init_scan_result's de-collision may move a point past its position)
+    if (req[i].pos > 0x7FFFFFFF - 64) return set_err(FSCLG_E_ARG, "request position overflow");
+    // interval_of needs log(alpha d) >= LOG_AD_MIN, as fsclg_set_alpha_grid checks for the grid
+    if (!(req[i].lalpha >= LOG_AD_MIN)) return set_err(FSCLG_E_ARG, "request lalpha below LOG_AD_MIN or NaN");
+  }
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
+  B.eval_range = eval_range; B.bp_resl = 0; B.st_ms = 0.0; B.st_n = n_req; B.st_synced = false;
+  int r;
+  if (n_req > 0) {
+    {  // the window null sums for the slot's rows: one covering cell per request
+      std::vector<fsclg_cell_t> cover((size_t)n_req);
+      for (int i = 0; i < n_req; i++) cover[i] = fsclg_cell_t{req[i].chr, req[i].pos, req[i].pos, 0};
+      if (c->slot[slot].users == 0) r = fsclg_slot_windows(c, slot, cover.data(), n_req, eval_range);
+      else r = ensure_windows(c, slot, eval_range, cover.data(), n_req, &B.wr_memo);
+      if (r) return r;
+    }
+    if ((r = ensure_io(B, 1))) return r;  // (make_params' cells and points: unused by this kernel)
+    if ((r = ensure_pinned(&B.p_sreq, &B.sreq_cap, n_req))) return r;
+    if ((r = ensure_pinned(&B.p_shdr, &B.shdr_cap, n_req))) return r;
+    memcpy(B.p_sreq, req, sizeof(fsclg_site_req_t) * (size_t)n_req);
+    HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
+    Params P = make_params(c, B, slot, n_req, 3, eval_range, 0);
+    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
+    hipLaunchKernelGGL(sites_kernel, dim3(n_req), dim3(WG), 0, B.stream, P, 0, (const fsclg_site_req_t*)B.p_sreq,
+                       B.p_shdr, (const SiteTask*)nullptr, (double*)nullptr);
+    HIPCHK(hipGetLastError(), "launch sites_kernel");
+    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+  }
+  B.pending = true; B.st_pending = true;
+  c->slot[slot].users++;
+  return FSCLG_OK;
+}
+
+// the time of the launch bracketed by the batch's events, added to the context's totals
+static int sites_time(fsclg_ctx* c, Batch& B) {
+  float ms = 0.f, t0 = 0.f, t1 = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
+  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
+  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
+  B.st_ms += ms;
+  c->kernel_ms += ms;
+  c->launches++;
+  c->busy.emplace_back((double)t0, (double)t1);
+  return FSCLG_OK;
+}
+
+static int sites_wait_impl(fsclg_ctx* c, Batch& B, fsclg_site_hdr_t* hdr, double* terms) {
+  const int n = B.st_n;
+  const size_t cap = fsclg_sites_cap();
+  int r, flags = 0;
+  if ((r = ensure_pinned(&B.p_sterms, &B.sterm_cap, (int)cap))) return r;
+  for (int i = 0; i < n; i++) flags |= B.p_shdr[i].pt.flags;
+  memcpy(hdr, B.p_shdr, sizeof(fsclg_site_hdr_t) * (size_t)n);
+  if (flags) return set_err(flags & PF_UNSUPPORTED ? FSCLG_E_UNSUPPORTED : FSCLG_E_KERNEL, "device flag");
+  const Params P0 = make_params(c, B, B.slot, 0, 3, B.eval_range, 0);
+  std::vector<SiteTask> tasks;
+  int i = 0, k = 0;  // the next term: term k of walk i
+  size_t done = 0;   // terms copied out so far = the launch's first term in terms[]
+  for (;;) {
+    tasks.clear();
+    size_t fill = 0;
+    while (i < n && fill < cap) {
+      const fsclg_site_hdr_t& h = hdr[i];
+      if (k >= h.len) { i++; k = 0; continue; }
+      const int k1 = (int)std::min<size_t>({(size_t)h.len, (size_t)k + (cap - fill), (size_t)k + SITE_TASK_MAX});
+      tasks.push_back(SiteTask{h.pt.nearest_snp, h.nl, h.pt.sweep_pos, k, k1, 0, h.pt.lalpha, (unsigned long long)fill});
+      fill += (size_t)(k1 - k);
+      k = k1;
+    }
+    if (tasks.empty()) break;
+    if ((r = ensure_pinned(&B.p_stasks, &B.stask_cap, (int)tasks.size()))) return r;
+    memcpy(B.p_stasks, tasks.data(), sizeof(SiteTask) * tasks.size());
+    Params P = P0;
+    P.n_cells = (int)tasks.size();
+    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
+    hipLaunchKernelGGL(sites_kernel, dim3((unsigned)tasks.size()), dim3(WG), 0, B.stream, P, 1,
+                       (const fsclg_site_req_t*)nullptr, (fsclg_site_hdr_t*)nullptr, (const SiteTask*)B.p_stasks,
+                       B.p_sterms);
+    HIPCHK(hipGetLastError(), "launch sites_kernel");
+    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+    HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+    memcpy(terms + done, B.p_sterms, sizeof(double) * fill);
+    done += fill;
+    if ((r = sites_time(c, B))) return r;
+  }
+  return FSCLG_OK;
+}
+
+int fsclg_sites_wait(fsclg_ctx* c, int batch, fsclg_site_hdr_t* hdr, double* terms, size_t terms_cap, size_t* n_terms) {
+  if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
+  Batch& B = c->batch[batch];
+  if (!B.pending || !B.st_pending) return set_err(FSCLG_E_STATE, "no site terms submitted on the batch");
+  const int n = B.st_n;
+  if (!hdr && n) return set_err(FSCLG_E_ARG, "hdr");  // (the batch stays submitted)
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  int r = FSCLG_OK;
+  size_t total = 0;
+  if (n > 0 && !B.st_synced) {
+    hipError_t e = hipEventSynchronize(B.ev1);
+    if (e != hipSuccess) {  // the batch ends here
+      B.pending = false; B.st_pending = false; c->slot[B.slot].users--;
+      return set_err(FSCLG_E_HIP, "hipEventSynchronize");
+    }
+    B.st_synced = true;
+    r = sites_time(c, B);
+    uint64_t off = 0;  // the offsets: a running sum in request order
+    for (int i = 0; i < n && r == FSCLG_OK; i++) { B.p_shdr[i].off = off; off += (uint64_t)B.p_shdr[i].len; }
+  }
+  for (int i = 0; i < n; i++) total += (size_t)B.p_shdr[i].len;
+  if (n_terms) *n_terms = total;
+  if (r == FSCLG_OK && (terms_cap < total || (!terms && total)))  // (the batch stays submitted)
+    return set_err(FSCLG_E_ARG, "terms_cap below the walks' terms");
+  if (r == FSCLG_OK && n > 0) r = sites_wait_impl(c, B, hdr, terms);
+  B.pending = false; B.st_pending = false;
+  c->slot[B.slot].users--;
+  return r;
+}
+
+double fsclg_sites_last_ms(fsclg_ctx* c, int batch) {
+  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].st_ms : 0.0;
 }
 
 int fsclg_interval_thresholds(double log_ad_step, int n_iv, double* thr) {

@@ -57,6 +57,8 @@ int main(int argc, char **argv) {
   double permute_nbp = 0.1, alpha_factor = 1.0, scan_width_mb = 1.0;
   char *permute_mode = NULL, *permute_seed = NULL, *profile_fname = NULL, *scan_mode = NULL, *alpha_fname = NULL;
   double alpha_drop = 2.0;
+  char *sites_fname = NULL;
+  int sites_top = 10;
   int grid_mode = 0;
   scan_t *s;
   double **fsp;
@@ -95,6 +97,9 @@ int main(int argc, char **argv) {
       {0, "alpha-file", &alpha_fname, T_STR, "write every scan point's alpha likelihood curve and support interval to this file"},
       {0, "alpha-drop", &alpha_drop, T_DBL, "log-likelihood drop of the support interval in --alpha-file (default 2.0; descriptive: "
                                             "the likelihood is composite)"},
+      {0, "sites-file", &sites_fname, T_STR, "write the per-site likelihood terms of the scan points' walks, and a footprint summary per "
+                                             "point, to this file"},
+      {0, "sites-top", &sites_top, T_INT, "--sites-file takes this many points of greatest CLR (default 10; 0: every point)"},
       {0, "scan-mode", &scan_mode, T_STR, "bisection (default: search_maxpos in every cell) or grid (the maximum over each cell's "
                                           "-g spaced positions, in the scan and in the permutation test; one process, parity only)"},
       {0, "permute-seed", &permute_seed, T_STR, "seed of the throughput mode's random numbers (default 0xFD821A6)"},
@@ -179,6 +184,8 @@ int main(int argc, char **argv) {
   if (profile_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --profile-file needs the scan (not with --no-scan).\n"); stop = 1; }
   if (profile_fname && small_grid_sp < 1) { logmsg(MSG_ERROR, "Error: --profile-file needs a positive -g spacing.\n"); stop = 1; }
   if (alpha_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --alpha-file needs the scan (not with --no-scan).\n"); stop = 1; }
+  if (sites_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --sites-file needs the scan (not with --no-scan).\n"); stop = 1; }
+  if (sites_top < 0) { logmsg(MSG_ERROR, "Error: --sites-top must be >= 0.\n"); stop = 1; }
   if (!(alpha_drop >= 0.0)) { logmsg(MSG_ERROR, "Error: --alpha-drop must be >= 0.\n"); stop = 1; }
   if (large_grid_sp < 1) { logmsg(MSG_ERROR, "Error: coarse grid spacing must be positive.\n"); stop = 1; }
   if (n_gpus < 0) { logmsg(MSG_ERROR, "Error: --n-gpus must be >= 0.\n"); stop = 1; }
@@ -271,6 +278,16 @@ int main(int argc, char **argv) {
       logmsg(MSG_STATUS, "Alpha curves: %d points, kernel %.3f ms, %llu walks summed sequentially for the curves alone\n",
              s->n_scan_pts, fscl_amd_curve_last_ms(), fscl_amd_curve_forced());
       free(cv);
+    }
+    if (sites_fname && !(ws && rk && atoi(ws) > 1 && atoi(rk) != 0)) {
+      /* the per-site terms of the scan points' walks, of the data as loaded (rank 0 alone); no rand() draw */
+      fscl_amd_sites_t st;
+      const int r = fscl_amd_scan_point_sites(s, sm, eval_range, sites_top, &st);
+      if (r != 0) logmsg(MSG_FATAL, "fscl: site terms failed (code %d)", r);
+      fscl_amd_sites_output(sites_fname, s, &st, prepend_label);
+      logmsg(MSG_STATUS, "Site terms: %d walks, %llu terms, kernel %.3f ms\n", st.n, (unsigned long long)st.n_terms,
+             fscl_amd_sites_last_ms());
+      fscl_amd_sites_free(&st);
     }
     if (n_permute > 0 && grid_mode)
       fscl_amd_scan_permute_grid(s, sm, n_permute, permute_nbp, eval_range, small_grid_sp, large_grid_sp, scan_width_mb);

@@ -2735,6 +2735,214 @@ void fscl_amd_curve_output(const char *fname, const scan_t *s, const fscl_amd_cu
   if (fname) fclose(f);
 }
 
+/* ------------------------------------------------------ per-site likelihood terms
+   The terms of single sm_likelihood walks (fsclg_sites_submit), on the data as loaded.  The local
+   devices take contiguous shares of the requests balanced by window size; every device is
+   submitted to before the first is waited for.  A first wait with no room sizes the terms (the
+   batch stays submitted), a second one fills each device's part of the one array. */
+static double g_sites_ms;
+double fscl_amd_sites_last_ms(void) { return g_sites_ms; }
+
+void fscl_amd_sites_free(fscl_amd_sites_t *r) {
+  if (!r) return;
+  free(r->point); free(r->hdr); free(r->terms);
+  memset(r, 0, sizeof *r);
+}
+
+int fscl_amd_scan_sites(scan_t *s, sm_ptable_t *sm, int eval_range, const fsclg_site_req_t *req, int n,
+                        fscl_amd_sites_t *out) {
+  double *cost;
+  size_t nt[FH_MAX_DEV], base[FH_MAX_DEV], total = 0;
+  int lo[FH_MAX_DEV], hi[FH_MAX_DEV], i, l, k, r = FSCLG_OK;
+  if (!s || !sm || !out || n < 0 || (n && !req)) return FSCLG_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (D.world > 1 && D.rank != 0) return FSCLG_OK; /* rank 0 alone evaluates, as the curves */
+  prepare(s, sm);
+  for (i = 0; i < n; i++)
+    if (req[i].chr < 0 || req[i].chr >= D.n_chr) return FSCLG_E_ARG;
+  set_original_rows();
+  g_sites_ms = 0.;
+  cost = fh_malloc(sizeof(double) * (n ? n : 1), "cost");
+  for (i = 0; i < n; i++) cost[i] = window_cost(req[i].chr, eval_range);
+  for (l = 0; l < D.n_dev; l++) {
+    if (D.n_dev <= 1) { lo[l] = 0; hi[l] = n; }
+    else fscl_amd_partition(cost, n, l, D.n_dev, &lo[l], &hi[l]);
+    nt[l] = 0;
+  }
+  free(cost);
+  out->hdr = fh_malloc(sizeof(fscl_amd_site_hdr_t) * (n ? n : 1), "site headers");
+  for (l = 0; l < D.n_dev && r == FSCLG_OK; l++) {
+    DBG("sites: device %d, requests [%d, %d)\n", D.dev[l], lo[l], hi[l]);
+    r = fsclg_sites_submit(D.ctx[l], 0, 0, req + lo[l], hi[l] - lo[l], eval_range); /* (the requests are copied) */
+  }
+  if (r != FSCLG_OK) l--; /* the submit that failed left nothing to wait for */
+  for (k = 0; k < l; k++) { /* the sizes (the headers are ready once this returns) */
+    const int rw = fsclg_sites_wait(D.ctx[k], 0, out->hdr + lo[k], NULL, 0, &nt[k]);
+    if (rw != FSCLG_OK && !(rw == FSCLG_E_ARG && nt[k] > 0)) { nt[k] = (size_t)-1; if (r == FSCLG_OK) r = rw; }
+    else if (rw == FSCLG_OK) nt[k] = (size_t)-2; /* no terms: that wait ended the batch */
+  }
+  for (k = 0; k < l; k++) {
+    base[k] = total;
+    if (nt[k] < (size_t)-2) total += nt[k];
+  }
+  out->terms = fh_malloc(sizeof(double) * (total ? total : 1), "site terms");
+  for (k = 0; k < l; k++) {
+    double ms;
+    if (nt[k] < (size_t)-2) {
+      const int rw = fsclg_sites_wait(D.ctx[k], 0, out->hdr + lo[k], out->terms + base[k], nt[k], NULL);
+      if (r == FSCLG_OK) r = rw;
+    }
+    for (i = lo[k]; i < hi[k]; i++) out->hdr[i].off += base[k];
+    ms = fsclg_sites_last_ms(D.ctx[k], 0);
+    if (ms > g_sites_ms) g_sites_ms = ms; /* the devices run side by side */
+  }
+  out->n = n; out->n_terms = total;
+  if (r != FSCLG_OK) fscl_amd_sites_free(out);
+  return r;
+}
+
+int fscl_amd_scan_point_sites(scan_t *s, sm_ptable_t *sm, int eval_range, int top_k, fscl_amd_sites_t *out) {
+  fsclg_site_req_t *req;
+  int *pick, i, j, n, m, r;
+  if (!s || !sm || !out || (!s->scan_pts && s->n_scan_pts) || s->n_scan_pts < 0 || top_k < 0) return FSCLG_E_ARG;
+  n = s->n_scan_pts;
+  m = top_k == 0 || top_k > n ? n : top_k;
+  /* the m points of greatest CLR, ties in scan order (a NaN CLR ranks last): insertion into a list
+     kept in descending order, then back into scan order */
+  pick = fh_malloc(sizeof(int) * (size_t)(m ? m : 1), "site points");
+  for (i = 0; m == n && i < n; i++) pick[i] = i; /* every point */
+  for (i = 0, j = 0; m < n && i < n; i++) {
+    const double v = s->scan_pts[i].clr;
+    int k = j;
+    while (k > 0 && v == v && !(s->scan_pts[pick[k - 1]].clr >= v)) k--;
+    if (k >= m) continue;
+    if (j < m) j++;
+    memmove(pick + k + 1, pick + k, sizeof(int) * (size_t)(j - k - 1));
+    pick[k] = i;
+  }
+  for (i = 1; i < m; i++) { /* ascending index */
+    const int v = pick[i];
+    for (j = i; j > 0 && pick[j - 1] > v; j--) pick[j] = pick[j - 1];
+    pick[j] = v;
+  }
+  req = fh_malloc(sizeof(fsclg_site_req_t) * (size_t)(m ? m : 1), "site requests");
+  for (i = 0; i < m; i++) {
+    const scan_pt_t *q = s->scan_pts + pick[i];
+    req[i].chr = q->chr; req[i].pos = q->sweep_pos; req[i].lalpha = q->lalpha;
+  }
+  r = fscl_amd_scan_sites(s, sm, eval_range, req, m, out);
+  free(req);
+  if (r == FSCLG_OK && out->hdr) out->point = pick; /* (not rank 0: nothing was evaluated) */
+  else free(pick);
+  return r;
+}
+
+/* term k of a walk belongs to site walk_site(h, k); site i of the walk holds term walk_term(h, i) */
+static int walk_site(const fscl_amd_site_hdr_t *h, int k) {
+  return k == 0 ? h->pt.nearest_snp : (k <= h->nl ? h->pt.nearest_snp - k : h->pt.nearest_snp + (k - h->nl));
+}
+static int walk_term(const fscl_amd_site_hdr_t *h, int i) {
+  return i == h->pt.nearest_snp ? 0 : (i < h->pt.nearest_snp ? h->pt.nearest_snp - i : h->nl + (i - h->pt.nearest_snp));
+}
+
+typedef struct { double t; int k; } site_term_t;
+static int site_term_cmp(const void *va, const void *vb) { /* descending term, then walk order */
+  const site_term_t *a = va, *b = vb;
+  if (a->t != b->t) return a->t > b->t ? -1 : 1;
+  return a->k - b->k;
+}
+
+void fscl_amd_sites_summary(const scan_t *s, const fscl_amd_sites_t *r, fscl_amd_sites_summary_t *out) {
+  int i, k;
+  if (!s || !r || !out) return;
+  for (i = 0; i < r->n; i++) {
+    const fscl_amd_site_hdr_t *h = r->hdr + i;
+    const double *t = r->terms + h->off;
+    fscl_amd_sites_summary_t *o = out + i;
+    double nan_ = 0.0, sum = 0.0, acc = 0.0;
+    int top = -1, np = 0;
+    nan_ = nan_ / nan_;
+    memset(o, 0, sizeof *o);
+    o->n_sites = h->len;
+    o->first_pos = o->last_pos = o->top_pos = -1;
+    o->top_term = o->top_share = nan_;
+    if (h->len <= 0) continue;
+    o->first_pos = s->snps[h->pt.nearest_snp - h->nl].pos;
+    o->last_pos = s->snps[h->pt.nearest_snp + h->nr].pos;
+    for (k = 0; k < h->len; k++) {
+      if (t[k] > 0.0) o->n_pos++;
+      if (t[k] < 0.0) o->n_neg++;
+      if (t[k] == t[k] && (top < 0 || t[k] > t[top])) top = k; /* strict: the first in walk order wins; never a NaN */
+    }
+    if (top >= 0) {
+      o->top_pos = s->snps[walk_site(h, top)].pos;
+      o->top_term = t[top];
+      if (h->pt.clr > 0.0) o->top_share = 2.0 * t[top] / h->pt.clr;
+    }
+    /* n_half: the positive terms in descending order (ties in walk order), summed one by one in
+       that order; then the least count whose running sum, formed the same way, reaches half of it */
+    if (o->n_pos > 0) {
+      site_term_t *v = fh_malloc(sizeof *v * (size_t)o->n_pos, "positive terms");
+      for (k = 0; k < h->len; k++)
+        if (t[k] > 0.0) { v[np].t = t[k]; v[np].k = k; np++; }
+      qsort(v, (size_t)np, sizeof *v, site_term_cmp);
+      for (k = 0; k < np; k++) sum += v[k].t;
+      for (k = 0; k < np; k++) {
+        acc += v[k].t;
+        if (acc >= 0.5 * sum) break;
+      }
+      o->n_half = k + 1;
+      free(v);
+    }
+  }
+}
+
+/* sm-search.c:40-46 */
+static double sites_logt(long long d) {
+  if (d < 0) d = -d;
+  if (d > 0xFFFFFF) return 11.783502069519070 + g_log_table[d >> 16];
+  if (d > 0xFFFF) return 5.545177444479562 + g_log_table[d >> 8];
+  return g_log_table[d];
+}
+
+void fscl_amd_sites_output(const char *fname, const scan_t *s, const fscl_amd_sites_t *r, const char *label) {
+  FILE *f = stdout;
+  fscl_amd_sites_summary_t *sum;
+  int i, j;
+  if (!r || !s) return;
+  if (D.world > 1 && D.rank != 0) return; /* one writer */
+  init_log_table();
+  if (fname) {
+    f = fopen(fname, "w");
+    if (!f) { fprintf(stderr, "Can't open site term file \"%s\" (%s)", fname, strerror(errno)); return; }
+  }
+  sum = fh_malloc(sizeof *sum * (size_t)(r->n > 0 ? r->n : 1), "site summaries");
+  fscl_amd_sites_summary(s, r, sum);
+  for (i = 0; i < r->n; i++) {
+    const fscl_amd_site_hdr_t *h = r->hdr + i;
+    const fscl_amd_sites_summary_t *o = sum + i;
+    const char *name = s->chr_limits[h->pt.chr].name;
+    for (j = h->pt.nearest_snp - h->nl; h->len > 0 && j <= h->pt.nearest_snp + h->nr; j++) {
+      const snp_t *p = s->snps + j;
+      if (label) fprintf(f, "%s\t", label);
+      fprintf(f, "%s\t%d\t%d\t%d\t%d\t%d\t%d\t%1.4f\t%1.4f\n", name, h->pt.sweep_pos, p->pos, p->pos - h->pt.sweep_pos,
+              p->obs_freq, s->sample_depths[p->depth_p], p->folded,
+              sites_logt((long long)h->pt.sweep_pos - p->pos) + h->pt.lalpha, r->terms[h->off + walk_term(h, j)]);
+    }
+    if (label) fprintf(f, "%s\t", label);
+    fprintf(f, "%s\t%d\tsummary\t%d\t", name, h->pt.sweep_pos, o->n_sites);
+    if (h->len > 0) fprintf(f, "%d\t%d\t%d\t%d\t", o->first_pos, o->last_pos, o->n_pos, o->n_neg);
+    else fprintf(f, "NA\tNA\t0\t0\t");
+    if (o->top_pos >= 0) fprintf(f, "%d\t%1.4f\t", o->top_pos, o->top_term);
+    else fprintf(f, "NA\tNA\t");
+    if (o->top_share == o->top_share) fprintf(f, "%1.4f\t", o->top_share);
+    else fprintf(f, "NA\t");
+    fprintf(f, "%d\n", o->n_half);
+  }
+  free(sum);
+  if (fname) fclose(f);
+}
+
 /* the points fscl_amd_scan_chromosome_grid made last: fscl_amd_scan_permute_grid tests only
    those, with the same spacings, on the same data (D.key) */
 static struct {

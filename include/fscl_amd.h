@@ -377,6 +377,60 @@ int fscl_amd_curve_runs(scan_t *scan_obj, sm_ptable_t *sm_p, const fsclg_run_t *
 double fscl_amd_curve_last_ms(void);
 unsigned long long fscl_amd_curve_forced(void);
 
+/* ---- per-site likelihood terms (--sites-file) --------------------------------------
+   The data axis of a sweep position: which sites made this CLR.  A walk is one sm_likelihood
+   (sm-search.c:105-150) at (chromosome index, position, log alpha); its header and terms are
+   fsclg_site_hdr_t and the doubles of include/fsclg.h: terms[hdr.off + k] is snp_likelihood's value
+   at the walk's k-th site in walk order (the nearest SNP, then leftwards, then rightwards), and
+   folding them from hdr.pt.null_logl gives hdr.pt.sm_logl bit for bit.  A result owns its arrays
+   (fscl_amd_sites_free; a zeroed one is empty); point[i] is the scan point of walk i, or NULL.
+
+   fscl_amd_scan_sites: the walks of n requests, on the data as loaded (also after scan_permute),
+   on the device context scan_chromosome uses; several local devices take contiguous shares
+   balanced by window size (identical results); with several ranks, rank 0 alone evaluates (the
+   others return FSCLG_OK and an empty result).  Returns a fsclg status code.
+   fscl_amd_scan_point_sites: the walks of the scan points at their own sweep_pos and lalpha, after
+   scan_chromosome or fscl_amd_scan_chromosome_grid: the top_k points of greatest CLR (ties keep
+   scan order, a NaN CLR ranks last; top_k = 0: every point), listed in scan order.
+
+   fscl_amd_sites_summary (host only), per walk into out[n]: n_sites = len; first_pos / last_pos
+   the positions of the footprint's first and last site (-1 for an empty walk); n_pos / n_neg the
+   terms above / below 0; top_term the greatest term and top_pos its site's position, the first in
+   walk order on a tie, never a NaN (-1 and NaN when there is none); top_share = 2 * top_term / clr,
+   NaN ("NA") when clr <= 0 or is NaN; n_half: with the positive terms in descending order (ties in
+   walk order) and added one by one in double, the least count whose sum reaches half of the sum
+   of all of them (0: no positive term).
+
+   fscl_amd_sites_output (fname NULL: stdout), per walk in the result's order: one row per site in
+   ascending site position
+     [label TAB] chromosome TAB sweep_pos TAB site_pos TAB site_pos - sweep_pos TAB obs_freq TAB depth
+       TAB folded TAB log(alpha d) (%1.4f) TAB term (%1.4f)
+   then one summary row
+     [label TAB] chromosome TAB sweep_pos TAB summary TAB n_sites TAB first_pos TAB last_pos TAB n_pos
+       TAB n_neg TAB top_pos TAB top_term (%1.4f) TAB top_share (%1.4f) TAB n_half
+   with NA for a position, term or share that does not exist. */
+typedef fsclg_site_hdr_t fscl_amd_site_hdr_t;
+typedef struct {
+  int n;            /* walks */
+  int *point;       /* [n] scan point index of each walk (fscl_amd_scan_point_sites), or NULL */
+  fscl_amd_site_hdr_t *hdr;
+  double *terms;
+  size_t n_terms;
+} fscl_amd_sites_t;
+typedef struct {
+  int32_t n_sites, first_pos, last_pos, n_pos, n_neg, top_pos, n_half, pad;
+  double top_term, top_share;
+} fscl_amd_sites_summary_t;
+int fscl_amd_scan_sites(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, const fsclg_site_req_t *req, int n,
+                        fscl_amd_sites_t *out);
+int fscl_amd_scan_point_sites(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, int top_k, fscl_amd_sites_t *out);
+void fscl_amd_sites_free(fscl_amd_sites_t *r);
+void fscl_amd_sites_summary(const scan_t *scan_obj, const fscl_amd_sites_t *r, fscl_amd_sites_summary_t *out);
+void fscl_amd_sites_output(const char *fname, const scan_t *scan_obj, const fscl_amd_sites_t *r,
+                           const char *prepend_label);
+/* the summed kernel milliseconds of the last evaluation (the slowest device's) */
+double fscl_amd_sites_last_ms(void);
+
 /* release the device context (tables / snps) */
 void fscl_amd_shutdown(void);
 

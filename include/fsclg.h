@@ -278,6 +278,50 @@ int fsclg_curve_wait(fsclg_ctx *c, int batch, fsclg_curve_t *out);
 double fsclg_curve_last_ms(fsclg_ctx *c, int batch);
 unsigned long long fsclg_curve_forced(fsclg_ctx *c);
 
+/* Per-site likelihood terms: the data axis of a sweep position.  A request is one walk of
+   sm_likelihood (sm-search.c:105-150) -- a chromosome, a position and a log alpha, any double
+   >= LOG_AD_MIN (-20), not only a value of the alpha grid -- on the rows a slot holds.  Its header's
+   pt is what init_scan_result(chr, pos) gives on those rows (nearest_snp, the de-collided sweep_pos,
+   the window, n_snps, null_logl; cost 0) with lalpha the request's, sm_logl the exact sequential sum
+   null_logl + t_0 + t_1 + ... and clr = 2 * (sm_logl - null_logl).  terms[off + k], k < len, is what
+   snp_likelihood (sm-search.c:85-103) returns for the walk's k-th site in walk order: the nearest
+   SNP (k = 0), then leftwards (site nearest_snp - k, k <= nl), then rightwards (site nearest_snp +
+   k - nl); folding them one by one from pt.null_logl in that order gives pt.sm_logl bit for bit.
+   Only the doubles are stored: the site of term k follows from the header.  A walk whose nearest
+   SNP is already outside log(alpha d) <= LOG_AD_MAX has len = nl = nr = 0 and sm_logl = null_logl;
+   otherwise len = 1 + nl + nr.  The walks' terms lie one after another in request order (off is
+   the running sum of len).
+   fsclg_sites_submit / fsclg_sites_wait take batches, slots and window null sums exactly as
+   fsclg_curve_submit / fsclg_curve_wait do (any batch and slot; the window sums of the slot's rows
+   are summed here, one covering cell per request; several devices: submit to all, then wait).
+   The submit launches the headers (one workgroup per request) and returns at once; the wait forms
+   the offsets on the host and launches the terms into a pinned staging area of
+   fsclg_sites_cap() terms ($FSCLG_SITES_CAP, default 4194304 = 32 MiB), as many launches as the
+   walks need -- a walk longer than the area is cut across launches -- copying each launch's terms
+   into terms[]; the result does not depend on the cut.  *n_terms (if not NULL) is set to the sum of
+   len.  If terms_cap is below it (or terms is NULL), the wait returns FSCLG_E_ARG, writes neither
+   hdr nor terms, and the batch STAYS submitted: a caller may wait with terms_cap = 0 to size its
+   buffer and wait again.  A NULL hdr is FSCLG_E_ARG in the same way.  Any other return ends the
+   batch.  Further errors: FSCLG_E_ARG for a bad chr, batch or
+   slot, a position above INT_MAX - 64, a lalpha that is NaN or below LOG_AD_MIN;
+   FSCLG_E_STATE for tables or SNPs not uploaded, a batch not waited for (submit), no sites
+   submitted on the batch (wait).  fsclg_sites_last_ms: the summed time (HIP events) of the batch's
+   last header launch and term launches; the device counters of fsclg_stats_t do not count these
+   walks (kernel_ms, n_launches and busy_ms do). */
+typedef struct {
+  int32_t chr, pos;
+  double lalpha;
+} fsclg_site_req_t;
+typedef struct {
+  fsclg_point_t pt;
+  int32_t nl, nr, len, pad;  /* terms left / right of the nearest SNP; len = 0 or 1 + nl + nr; pad 0 */
+  uint64_t off;              /* index of the walk's first term in terms[] */
+} fsclg_site_hdr_t;
+int fsclg_sites_submit(fsclg_ctx *c, int batch, int slot, const fsclg_site_req_t *req, int n_req, int eval_range);
+int fsclg_sites_wait(fsclg_ctx *c, int batch, fsclg_site_hdr_t *hdr, double *terms, size_t terms_cap, size_t *n_terms);
+double fsclg_sites_last_ms(fsclg_ctx *c, int batch);
+size_t fsclg_sites_cap(void);
+
 /* the exact interval thresholds the kernel uses in place of spline_interpolate's
    division (sm-spline.c:52): thr[j] = least double x with
    (int)((x - LOG_AD_MIN) / log_ad_step) >= j, for j = 1..n_iv (thr has n_iv+1 slots) */

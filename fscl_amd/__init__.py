@@ -32,6 +32,8 @@ __all__ = [
     "curve_forced", "CURVE_DTYPE",
     "scan_sites", "scan_point_sites", "sites_summary", "sites_output", "sites_last_ms", "sites_cap", "SitesT",
     "SITES_DTYPE", "SITE_REQ_DTYPE", "SITES_SUMMARY_DTYPE",
+    "simulate", "simulate_scan", "simulate_output", "simulate_last_ms", "scan_free", "bootstrap", "bootstrap_output",
+    "bootstrap_times", "parse_sweep", "nearest_sweep", "SWEEP_DTYPE", "BOOT_DTYPE",
 ]
 
 ROOT = Path(__file__).resolve().parent
@@ -148,6 +150,10 @@ EXPORTS = [
     "fsclg_sites_submit", "fsclg_sites_wait", "fsclg_sites_last_ms", "fsclg_sites_cap",
     "fscl_amd_scan_sites", "fscl_amd_scan_point_sites", "fscl_amd_sites_free", "fscl_amd_sites_summary",
     "fscl_amd_sites_output", "fscl_amd_sites_last_ms",
+    "fsclg_sample_tables", "fsclg_sample_submit", "fsclg_sample_wait", "fsclg_sample_last_ms",
+    "fscl_amd_simulate", "fscl_amd_simulate_scan", "fscl_amd_scan_free", "fscl_amd_simulate_output",
+    "fscl_amd_simulate_last_ms", "fscl_amd_bootstrap", "fscl_amd_bootstrap_times", "fscl_amd_bootstrap_output",
+    "fscl_amd_parse_sweep", "fscl_amd_nearest_sweep", "fscl_amd_sample_tables_build",
 ]
 
 
@@ -224,6 +230,18 @@ def _load() -> C.CDLL:
         "fscl_amd_sites_output": (None, [C.c_char_p, P(ScanT), P(SitesT), C.c_char_p]),
         "fscl_amd_sites_last_ms": (C.c_double, []),
         "fsclg_sites_cap": (C.c_size_t, []),
+        "fscl_amd_parse_sweep": (C.c_int, [P(ScanT), C.c_char_p, C.c_void_p]),
+        "fscl_amd_nearest_sweep": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+        "fscl_amd_simulate": (C.c_int, [P(ScanT), P(SmPtableT), C.c_void_p, C.c_int, C.c_ulonglong, C.c_int, C.c_void_p,
+                                        P(C.c_ulonglong)]),
+        "fscl_amd_simulate_scan": (P(ScanT), [P(ScanT), C.c_void_p]),
+        "fscl_amd_scan_free": (None, [P(ScanT)]),
+        "fscl_amd_simulate_output": (C.c_int, [C.c_char_p, P(ScanT)]),
+        "fscl_amd_simulate_last_ms": (C.c_double, []),
+        "fscl_amd_bootstrap": (C.c_int, [P(ScanT), P(SmPtableT), P(P(C.c_double)), C.c_void_p, C.c_int, C.c_int,
+                                         C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "fscl_amd_bootstrap_times": (None, [P(C.c_double)]),
+        "fscl_amd_bootstrap_output": (None, [C.c_char_p, P(ScanT), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_char_p]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -675,6 +693,102 @@ def sites_cap() -> int:
     return int(get_lib().fsclg_sites_cap())
 
 
+# fscl_amd_sweep_t: chromosome index, position, alpha (> 0)
+SWEEP_DTYPE = np.dtype([("chr", "i4"), ("pos", "i4"), ("alpha", "f8")])
+# fscl_amd_boot_t: one planted sweep in one replicate; est_pos -1 (and NaN est_lalpha / clr) when the
+# replicate's scan has no point within the window
+BOOT_DTYPE = np.dtype([("sweep", "i4"), ("rep", "i4"), ("chr", "i4"), ("planted_pos", "i4"), ("planted_alpha", "f8"),
+                       ("est_pos", "i4"), ("pad", "i4"), ("est_lalpha", "f8"), ("clr", "f8")])
+assert SWEEP_DTYPE.itemsize == 16 and BOOT_DTYPE.itemsize == 48
+
+
+def _sweeps(sweeps) -> np.ndarray:
+    a = np.zeros(len(sweeps), dtype=SWEEP_DTYPE)
+    for q, r in zip(a, sweeps):
+        q["chr"], q["pos"], q["alpha"] = int(r[0]), int(r[1]), float(r[2])
+    return a
+
+
+def parse_sweep(scan, text: str):
+    """"name:pos:alpha" (the chromosome name as in the input) -> (chromosome index, pos, alpha)."""
+    a = np.zeros(1, dtype=SWEEP_DTYPE)
+    r = get_lib().fscl_amd_parse_sweep(scan, _b(text), a.ctypes.data)
+    if r != 0:
+        raise ValueError({-2: "unknown chromosome name", -3: "alpha must be positive"}.get(r, "expected chr:pos:alpha")
+                         + f": {text!r}")
+    return int(a[0]["chr"]), int(a[0]["pos"]), float(a[0]["alpha"])
+
+
+def nearest_sweep(sweeps, chrom: int, pos: int) -> int:
+    """Index of the sweep governing a site at (chromosome index, pos), -1 if its chromosome has none."""
+    a = _sweeps(sweeps)
+    return int(get_lib().fscl_amd_nearest_sweep(a.ctypes.data if len(a) else None, len(a), int(chrom), int(pos)))
+
+
+def simulate(scan, tables, sweeps=(), seed: int = 0xFD821A6, rep: int = 0):
+    """One replicate under the sweep model at the scan's own sites (include/fscl_amd.h): the int32 array
+    of drawn derived counts and the number of degenerate sites (which keep their observed count).
+    ``sweeps``: (chromosome index, pos, alpha) each; none: a neutral replicate."""
+    a = _sweeps(sweeps)
+    out = np.zeros(max(scan.contents.n_snps, 1), dtype=np.int32)
+    deg = C.c_ulonglong(0)
+    _curve_check(get_lib().fscl_amd_simulate(scan, tables, a.ctypes.data if len(a) else None, len(a), int(seed), int(rep),
+                                             out.ctypes.data, C.byref(deg)), "fscl_amd_simulate")
+    return out[:scan.contents.n_snps], int(deg.value)
+
+
+def simulate_scan(scan, freq):
+    """A new scan_t with the scan's sites and ``freq`` as derived counts (folded at folded sites);
+    scan_free releases it."""
+    f = np.ascontiguousarray(freq, dtype=np.int32)
+    if len(f) != scan.contents.n_snps:
+        raise ValueError("one count per site")
+    return get_lib().fscl_amd_simulate_scan(scan, f.ctypes.data)
+
+
+def scan_free(scan) -> None:
+    get_lib().fscl_amd_scan_free(scan)
+
+
+def simulate_output(path, scan) -> None:
+    """The scan's sites in the SNP input format (load_snp_input reads them back)."""
+    if get_lib().fscl_amd_simulate_output(_b(path), scan) != 0:
+        raise OSError(f"cannot write {path}")
+
+
+def simulate_last_ms() -> float:
+    return float(get_lib().fscl_amd_simulate_last_ms())
+
+
+def bootstrap(scan, tables, fsp, sweeps, reps: int = 100, seed: int = 0xFD821A6, window_bp: int = 100000,
+              eval_range: int = 81920, bp_resl: int = 128, large_grid_sp: int = 100000) -> np.ndarray:
+    """The parametric bootstrap of planted sweeps (include/fscl_amd.h): a BOOT_DTYPE array of
+    len(sweeps) * reps rows, row sweep * reps + rep."""
+    a = _sweeps(sweeps)
+    out = np.zeros(max(len(a) * int(reps), 1), dtype=BOOT_DTYPE)
+    _curve_check(get_lib().fscl_amd_bootstrap(scan, tables, fsp, a.ctypes.data if len(a) else None, len(a), int(reps),
+                                              int(seed), int(window_bp), int(eval_range), int(bp_resl), int(large_grid_sp),
+                                              out.ctypes.data), "fscl_amd_bootstrap")
+    return out[:len(a) * int(reps)]
+
+
+def bootstrap_times() -> dict:
+    t = (C.c_double * 5)()
+    get_lib().fscl_amd_bootstrap_times(t)
+    return dict(zip(("total_s", "simulate_s", "null_s", "upload_s", "scan_s"), t))
+
+
+def bootstrap_output(path, scan, sweeps, reps: int, rows, label=None) -> None:
+    """The --bootstrap-file format (include/fscl_amd.h): per sweep one row per replicate, then a
+    quantile summary row.  Host only."""
+    a = _sweeps(sweeps)
+    b = np.ascontiguousarray(rows, dtype=BOOT_DTYPE)
+    if len(b) != len(a) * int(reps):
+        raise ValueError("rows must hold len(sweeps) * reps entries")
+    get_lib().fscl_amd_bootstrap_output(_b(path), scan, a.ctypes.data if len(a) else None, len(a), int(reps),
+                                        b.ctypes.data if len(b) else None, _b(label))
+
+
 def get_stats() -> dict:
     st = Stats()
     get_lib().fscl_amd_get_stats(C.byref(st))
@@ -760,7 +874,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         force_neutral=False, minimum_depth=5, large_grid_sp=100000, scan_width_mb=1.0, max_only=False,
         label=None, eval_range=81920, bp_resl=128, verbosity=1, permute_mode="parity", permute_seed=0xFD821A6,
         profile_file=None, small_grid_sp=1000, scan_mode="bisection", alpha_file=None, alpha_drop=2.0,
-        sites_file=None, sites_top=10):
+        sites_file=None, sites_top=10, simulate_file=None, simulate_sweeps=(), simulate_seed=0xFD821A6, simulate_rep=0,
+        bootstrap_file=None, bootstrap_reps=100, bootstrap_window=None, bootstrap_sweeps=(), bootstrap_top=3):
     """The fscl main() pipeline (fscl.c:316-337) in-process; returns the scan_t
     pointer (points(scan) reads the results).  permute_mode "throughput": the
     counter-based permutation test (set_permute_mode).  scan_mode "grid": the CLI's
@@ -771,6 +886,10 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         raise ValueError("scan_mode grid runs on the parity stream only")
     if int(sites_top) < 0:
         raise ValueError("sites_top must be >= 0")
+    if bootstrap_file is not None and scan_mode == "grid":
+        raise ValueError("the bootstrap rescans by bisection (not with scan_mode grid)")
+    if bootstrap_file is not None and (int(bootstrap_reps) < 0 or int(bootstrap_top) < 0):
+        raise ValueError("bootstrap_reps and bootstrap_top must be >= 0")
     get_lib().configure_logmsg(int(verbosity))
     set_permute_mode(permute_mode, permute_seed)
     init_log_table()
@@ -782,6 +901,12 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
     tab = compute_sweep_model_tables(scan, fsp, asc_depth, asc_min_freq, ascbias_background_only,
                                      include_invariant)
     compute_snp_null_model(scan, fsp)
+    as_sweep = lambda w: parse_sweep(scan, w) if isinstance(w, str) else w  # noqa: E731 -- "name:pos:alpha" or a tuple
+    sim_sw, boot_sw = [as_sweep(w) for w in simulate_sweeps], [as_sweep(w) for w in bootstrap_sweeps]
+    if simulate_file is not None:  # the CLI's --simulate-file: one replicate under the model
+        rep_scan = simulate_scan(scan, simulate(scan, tab, sim_sw, simulate_seed, simulate_rep)[0])
+        simulate_output(simulate_file, rep_scan)
+        scan_free(rep_scan)
     if scan_mode == "grid":
         scan_chromosome_grid(scan, tab, eval_range, small_grid_sp, large_grid_sp)
     else:
@@ -798,4 +923,18 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         scan_permute(scan, tab, n_permute, permute_nbp, 1.0, 1, eval_range, bp_resl, large_grid_sp, scan_width_mb)
     if output is not None:
         scan_output(output, scan, max_only, n_permute, label)
+    if bootstrap_file is not None:  # the CLI's --bootstrap-file, last
+        win = int(large_grid_sp if bootstrap_window is None else bootstrap_window)
+        if not boot_sw:  # the scan points of greatest CLR, none within the window of one already chosen
+            p = points(scan)
+            for i in sorted((i for i in range(len(p)) if p["clr"][i] == p["clr"][i]), key=lambda i: -p["clr"][i]):
+                if len(boot_sw) >= int(bootstrap_top):
+                    break
+                a = float(np.exp(p["lalpha"][i]))
+                if any(c == p["chr"][i] and abs(int(p["sweep_pos"][i]) - q) <= win for c, q, _ in boot_sw) or \
+                        not (0.0 < a < np.inf):
+                    continue
+                boot_sw.append((int(p["chr"][i]), int(p["sweep_pos"][i]), a))
+        rows = bootstrap(scan, tab, fsp, boot_sw, bootstrap_reps, simulate_seed, win, eval_range, bp_resl, large_grid_sp)
+        bootstrap_output(bootstrap_file, scan, boot_sw, bootstrap_reps, rows, label)
     return scan

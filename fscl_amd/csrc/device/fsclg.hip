@@ -2591,6 +2591,128 @@ sites_kernel(Params P, int pass, const fsclg_site_req_t* __restrict__ req, fsclg
   }
 }
 
+// ------------------------------------------------------------ sweep-model sampler
+// One replicate of derived counts under the model (fsclg_sample_submit; the idea of the reference's
+// sm-sample.c:164-212).  One wave per site, SAMPLE_WAVES sites per workgroup.  The site's set-up --
+// its depth, the nearest sweep of its chromosome, log_ad, the uniform draw -- is the same in every
+// lane.  A swept site takes its n - 1 probabilities 64 at a time: lane l of trip j has f = 1 + 64 j +
+// l and reads the 32-byte record (interval, f) of the sampler's own interval-major table
+// [depth][interval][f][c0..c3], consecutive lanes consecutive records.  Each trip's probabilities go
+// through an inclusive wave scan (six shuffle steps, a fixed order) on top of the trips before, and
+// every lane keeps its own cumulative sums in its own LDS cells -- no lane reads another lane's, so
+// the LDS is a per-lane array and needs no barrier -- with -1 where p_f is 0, which no threshold t >=
+// 0 lies below.  Once S is known, the least f with C_f > u S is the lowest set bit of the first trip's
+// non-empty ballot.  A neutral site (no sweep on its chromosome, or past LOG_AD_MAX) runs the same
+// search over the depth's prefix table, summed sequentially on the host, without an exponential.
+constexpr int SAMPLE_WAVES = 4;
+constexpr int SAMPLE_MAX_N = 8192;           // sample sizes up to this: (n - 1) * 8 B of LDS per wave
+constexpr int SAMPLE_MAX_SWEEPS = 4096;
+struct SampleDepth {
+  int32_t n, pad;
+  unsigned long long coef_off;   // doubles from SampleParams::coef to the depth's [interval][f][4]
+  unsigned long long neut_off;   // doubles from SampleParams::prefix to the depth's n - 1 entries
+  double neut_sum;               // S of the neutral spectrum (0 or not finite: degenerate)
+  int32_t neut_last, pad2;       // the greatest f with fsp[f] > 0 (0: none)
+};
+struct SampleParams {
+  const uint2* pr;               // the uploaded sites (biased position, row): positions only
+  const double* logt3;
+  const double* thr;
+  const double* coef;
+  const double* prefix;          // per depth: C_f of the neutral spectrum, -1 where fsp[f] counts as 0
+  const SampleDepth* depth;
+  const int32_t* chr_of;         // [n_snps] chromosome of each site, -1: none
+  const int32_t* depth_of;       // [n_snps] (host memory)
+  const fsclg_sweep_t* sweeps;   // (host memory)
+  int32_t* out;                  // [n_snps] (host memory)
+  int n_snps, n_sweeps, n_iv, lds_stride;
+  double inv_step, iv_off;
+  unsigned long long key;        // mix64(seed ^ 0x9E3779B97F4A7C15)
+  unsigned long long rep_hi;     // (uint64)(uint32)rep << 32
+};
+
+__host__ __device__ __forceinline__ unsigned long long sample_mix64(unsigned long long z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+__global__ void __launch_bounds__(64 * SAMPLE_WAVES)
+sample_kernel(SampleParams P) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int nw = (int)blockDim.x >> 6;
+  const long long site = (long long)blockIdx.x * nw + wave;
+  if (site >= P.n_snps) return;
+  const int i = (int)site;
+  double* __restrict__ cum = reinterpret_cast<double*>(fsclg_dyn) + (size_t)wave * P.lds_stride;
+  const SampleDepth D = P.depth[P.depth_of[i]];
+  const int m = D.n - 1;
+  const int trips = (m + 63) >> 6;
+  const int chr = P.chr_of[i];
+  const long long pos = (long long)(int)(P.pr[phys((uint32_t)i)].x ^ POS_BIAS);
+  // the nearest sweep of the chromosome: least |d|, then the lower position, then the first given
+  long long bd = -1, bp = 0;
+  double la = 0.0;
+  for (int k = 0; k < P.n_sweeps; k++) {
+    const fsclg_sweep_t s = P.sweeps[k];
+    if (s.chr != chr) continue;
+    const long long d = pos > s.pos ? pos - s.pos : (long long)s.pos - pos;
+    if (bd < 0 || d < bd || (d == bd && s.pos < bp)) { bd = d; bp = s.pos; la = s.lalpha; }
+  }
+  const double u = (double)(sample_mix64(P.key ^ (P.rep_hi | (unsigned long long)(uint32_t)i)) >> 11) * 0x1p-53;
+  const double x = bd >= 0 ? logt_dev((uint32_t)bd, P.logt3) + la : 0.0;
+  const bool swept = bd >= 0 && !(x > LOG_AD_MAX);
+  double S = D.neut_sum;
+  int last = D.neut_last;  // the greatest f with p_f > 0
+  const double* __restrict__ src = P.prefix + D.neut_off;
+  if (swept) {
+    int iv = (int)__builtin_fma(x, P.inv_step, P.iv_off);  // interval_of, with the clamp below LOG_AD_MIN
+    iv = max(0, min(iv, P.n_iv - 1));
+    iv += x >= P.thr[iv + 1] ? 1 : 0;
+    const double* __restrict__ row = P.coef + D.coef_off + (size_t)iv * (size_t)m * 4;
+    double base = 0.0;
+    int lastl = 0;
+    for (int j = 0; j < trips; j++) {
+      const int f = 1 + 64 * j + lane;
+      double p = 0.0;
+      if (f <= m) {
+        const double2 a = *reinterpret_cast<const double2*>(row + (size_t)(f - 1) * 4);
+        const double2 b = *reinterpret_cast<const double2*>(row + (size_t)(f - 1) * 4 + 2);
+        p = exp(x * (a.x * x * x + a.y * x + b.x) + b.y);
+        if (!(p >= 0.0) || p > 1.7976931348623157e308) p = 0.0;  // NaN, negative, infinite
+      }
+      double s = p;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const double v = __shfl_up(s, o, 64);
+        if (lane >= o) s += v;
+      }
+      s += base;
+      base = __shfl(s, 63, 64);
+      if (f <= m) cum[f - 1] = p > 0.0 ? s : -1.0;
+      if (p > 0.0) lastl = f;
+    }
+    S = base;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lastl = max(lastl, __shfl_xor(lastl, o, 64));
+    last = lastl;
+    src = cum;
+  }
+  int f_out = -1;  // degenerate: S zero or not finite
+  if (S > 0.0 && S <= 1.7976931348623157e308) {
+    const double t = u * S;
+    f_out = last;  // rounding left no C_f above t
+    for (int j = 0; j < trips; j++) {
+      const int f = 1 + 64 * j + lane;
+      const bool hit = f <= m && src[f - 1] > t;
+      const unsigned long long b = __ballot(hit);
+      if (b) { f_out = 1 + 64 * j + (int)__builtin_ctzll(b); break; }
+    }
+  }
+  if (lane == 0) P.out[i] = f_out;
+}
+
 // ------------------------------------------------------------ window null sums
 // init_scan_result's window sum (scan-chromosome.c:92-94) for every window start of the
 // chromosomes longer than the window: acc = 0.0; acc += null_logl[i] for i = ws..ws+W-1,
@@ -3201,6 +3323,16 @@ struct Batch {
   bool st_pending = false;
   bool st_synced = false;           // the header launch has been waited for (a wait that only sized the buffer)
   double st_ms = 0.0;               // kernel time of the batch's last sites call
+  // fsclg_sample_submit: the depth of every site and the drawn counts (pinned; read / written by the
+  // kernel), the sweeps (pinned staging, copied to d_sweeps on the batch's stream)
+  int32_t* p_sdepth = nullptr;
+  int32_t* p_sfreq = nullptr;
+  fsclg_sweep_t* p_ssweeps = nullptr;
+  fsclg_sweep_t* d_sweeps = nullptr;
+  int sdepth_cap = 0, sfreq_cap = 0, ssweep_cap = 0, dsweep_cap = 0;
+  int sm_n = 0;                     // sites of the submitted sample
+  bool sm_pending = false;
+  double sm_ms = 0.0;               // kernel time of the batch's last sample
 };
 
 struct fsclg_ctx {
@@ -3216,6 +3348,13 @@ struct fsclg_ctx {
   double* d_coef = nullptr;
   double* d_null = nullptr;
   double* d_thr = nullptr;
+  // the sampler's own tables (fsclg_sample_tables) and the chromosome of every uploaded site
+  double* d_smp_coef = nullptr;
+  double* d_smp_prefix = nullptr;
+  SampleDepth* d_smp_depth = nullptr;
+  int32_t* d_smp_chr = nullptr;
+  bool smp_chr_valid = false;
+  int smp_n_depths = 0, smp_max_m = 0, smp_n_iv = 0;
   int n_rows = 0, n_iv = 0;
   double step = 0.0;
   // snps
@@ -3393,7 +3532,8 @@ int fsclg_close(fsclg_ctx* c) {
   hipDeviceSynchronize();
   void* ptrs[] = {c->d_ivhist, c->d_logt, c->d_coef, c->d_null, c->d_thr, c->d_pr0,
                   c->d_chr_start, c->d_chr_n, c->d_wtasks, c->d_la_coarse, c->d_la_refine, c->d_n_refine,
-                  c->d_stats, c->d_dfail, c->d_dband, c->d_tpos, c->d_plan_tmp, c->d_lx};
+                  c->d_stats, c->d_dfail, c->d_dband, c->d_tpos, c->d_plan_tmp, c->d_lx,
+                  c->d_smp_coef, c->d_smp_prefix, c->d_smp_depth, c->d_smp_chr};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->p_pchunks) hipHostFree(c->p_pchunks);
   for (Slot& S : c->slot) {
@@ -3408,9 +3548,10 @@ int fsclg_close(fsclg_ctx* c) {
     if (B.d_ept) hipFree(B.d_ept);
     if (B.d_xacc) hipFree(B.d_xacc);
     if (B.d_xcnt) hipFree(B.d_xcnt);
+    if (B.d_sweeps) hipFree(B.d_sweeps);
     for (void* p : {(void*)B.p_cells, (void*)B.p_out, (void*)B.p_epos, (void*)B.p_cell_ep, (void*)B.p_ctrace,
                     (void*)B.p_cmchunks, (void*)B.p_curve, (void*)B.p_sreq, (void*)B.p_shdr, (void*)B.p_stasks,
-                    (void*)B.p_sterms})
+                    (void*)B.p_sterms, (void*)B.p_sdepth, (void*)B.p_sfreq, (void*)B.p_ssweeps})
       if (p) hipHostFree(p);
     hipEventDestroy(B.ev0);
     hipEventDestroy(B.ev1);
@@ -3573,6 +3714,7 @@ int fsclg_upload_snps(fsclg_ctx* c, const int32_t* pos, const uint32_t* row, int
   c->h_chr_start.assign(chr_start, chr_start + n_chr);
   c->h_pos.assign(pos, pos + n_snps);
   c->sidx_valid = false;
+  c->smp_chr_valid = false;
   c->cell_cost.clear();
   {  // |d| of a walk stays within a chromosome's span (plus grid slack): branch-2 index range
     long long span = 0;
@@ -4729,6 +4871,7 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
   if (B.cm_pending) return set_err(FSCLG_E_STATE, "the batch holds cell maxima (fsclg_cellmax_wait)");
   if (B.cv_pending) return set_err(FSCLG_E_STATE, "the batch holds curves (fsclg_curve_wait)");
   if (B.st_pending) return set_err(FSCLG_E_STATE, "the batch holds site terms (fsclg_sites_wait)");
+  if (B.sm_pending) return set_err(FSCLG_E_STATE, "the batch holds a sample (fsclg_sample_wait)");
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   B.pending = false;
@@ -5408,6 +5551,139 @@ int fsclg_sites_wait(fsclg_ctx* c, int batch, fsclg_site_hdr_t* hdr, double* ter
 
 double fsclg_sites_last_ms(fsclg_ctx* c, int batch) {
   return c && batch >= 0 && batch < NBATCH ? c->batch[batch].st_ms : 0.0;
+}
+
+// ------------------------------------------------------------ sweep-model sampler (host side)
+int fsclg_sample_tables(fsclg_ctx* c, const double* coef_t, const double* neutral, const int32_t* depth_n, int n_depths,
+                        int n_iv, double log_ad_step) {
+  if (!c || !coef_t || !neutral || !depth_n || n_depths <= 0 || n_iv <= 0) return set_err(FSCLG_E_ARG, "sample tables");
+  if (!c->d_thr || !c->d_logt) return set_err(FSCLG_E_STATE, "tables not uploaded");
+  if (n_iv != c->n_iv || log_ad_step != c->step) return set_err(FSCLG_E_ARG, "sample tables on another knot grid");
+  if (any_pending(c)) return set_err(FSCLG_E_STATE, "search batches in flight");
+  std::vector<SampleDepth> dep((size_t)n_depths);
+  size_t n_coef = 0, n_neut = 0;
+  int max_m = 0;
+  for (int d = 0; d < n_depths; d++) {
+    if (depth_n[d] < 2 || depth_n[d] > SAMPLE_MAX_N) return set_err(FSCLG_E_ARG, "sample size of a depth");
+    const int m = depth_n[d] - 1;
+    dep[d] = SampleDepth{depth_n[d], 0, (unsigned long long)n_coef, (unsigned long long)n_neut, 0.0, 0, 0};
+    n_coef += (size_t)n_iv * (size_t)m * 4;
+    n_neut += (size_t)m;
+    max_m = std::max(max_m, m);
+  }
+  // the neutral prefix sums, one by one in f order; -1 marks an f whose probability counts as 0
+  std::vector<double> prefix(n_neut);
+  for (int d = 0; d < n_depths; d++) {
+    const double* p = neutral + dep[d].neut_off;
+    double* q = prefix.data() + dep[d].neut_off;
+    double acc = 0.0;
+    for (int f = 1; f < depth_n[d]; f++) {
+      const double v = p[f - 1];
+      const bool ok = v > 0.0 && v <= 1.7976931348623157e308;
+      if (ok) { acc += v; dep[d].neut_last = f; }
+      q[f - 1] = ok ? acc : -1.0;
+    }
+    dep[d].neut_sum = acc;
+  }
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  int r;
+  c->smp_n_depths = 0;
+  if ((r = upload(&c->d_smp_coef, coef_t, n_coef, c->ustream))) return r;
+  if ((r = upload(&c->d_smp_prefix, prefix.data(), prefix.size(), c->ustream))) return r;
+  if ((r = upload(&c->d_smp_depth, dep.data(), dep.size(), c->ustream))) return r;
+  c->smp_n_depths = n_depths; c->smp_max_m = max_m; c->smp_n_iv = n_iv;
+  return FSCLG_OK;
+}
+
+int fsclg_sample_submit(fsclg_ctx* c, int batch, const int32_t* depth_of_site, const fsclg_sweep_t* sweeps, int n_sweeps,
+                        unsigned long long seed, int rep) {
+  if (!c || !depth_of_site || n_sweeps < 0 || n_sweeps > SAMPLE_MAX_SWEEPS || (n_sweeps && !sweeps))
+    return set_err(FSCLG_E_ARG, "sample");
+  if (batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
+  if (!c->d_pr0 || !c->d_thr) return set_err(FSCLG_E_STATE, "tables/snps not set");
+  if (!c->smp_n_depths || c->smp_n_iv != c->n_iv) return set_err(FSCLG_E_STATE, "sample tables not set for these tables");
+  Batch& B = c->batch[batch];
+  if (B.pending) return set_err(FSCLG_E_STATE, "batch not waited for");
+  const int n = c->n_snps;
+  for (int i = 0; i < n; i++)
+    if (depth_of_site[i] < 0 || depth_of_site[i] >= c->smp_n_depths) return set_err(FSCLG_E_ARG, "depth of a site");
+  for (int k = 0; k < n_sweeps; k++) {
+    if (sweeps[k].chr < 0 || sweeps[k].chr >= c->n_chr) return set_err(FSCLG_E_ARG, "sweep chromosome");
+    if (sweeps[k].lalpha != sweeps[k].lalpha) return set_err(FSCLG_E_ARG, "sweep lalpha is NaN");
+  }
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  int r;
+  if (!c->smp_chr_valid) {  // the chromosome of every uploaded site
+    std::vector<int32_t> chr_of((size_t)n, -1);
+    for (int k = 0; k < c->n_chr; k++)
+      for (int i = c->h_chr_start[k]; i < c->h_chr_start[k] + c->h_chr_n[k]; i++) chr_of[i] = k;
+    if ((r = upload(&c->d_smp_chr, chr_of.data(), chr_of.size(), c->ustream))) return r;
+    c->smp_chr_valid = true;
+  }
+  if ((r = ensure_pinned(&B.p_sdepth, &B.sdepth_cap, n))) return r;
+  if ((r = ensure_pinned(&B.p_sfreq, &B.sfreq_cap, n))) return r;
+  if ((r = ensure_pinned(&B.p_ssweeps, &B.ssweep_cap, n_sweeps))) return r;
+  if (B.dsweep_cap < std::max(n_sweeps, 1)) {
+    if (B.d_sweeps) hipFree(B.d_sweeps);
+    B.d_sweeps = nullptr; B.dsweep_cap = 0;
+    const int k = std::max(n_sweeps, 64);
+    HIPCHK(hipMalloc((void**)&B.d_sweeps, sizeof(fsclg_sweep_t) * (size_t)k), "hipMalloc sweeps");
+    B.dsweep_cap = k;
+  }
+  memcpy(B.p_sdepth, depth_of_site, sizeof(int32_t) * (size_t)n);
+  if (n_sweeps) {
+    memcpy(B.p_ssweeps, sweeps, sizeof(fsclg_sweep_t) * (size_t)n_sweeps);
+    HIPCHK(hipMemcpyAsync(B.d_sweeps, B.p_ssweeps, sizeof(fsclg_sweep_t) * (size_t)n_sweeps, hipMemcpyHostToDevice,
+                          B.stream), "hipMemcpyAsync sweeps");
+  }
+  SampleParams P;
+  P.pr = c->d_pr0; P.logt3 = c->d_logt; P.thr = c->d_thr; P.coef = c->d_smp_coef; P.prefix = c->d_smp_prefix;
+  P.depth = c->d_smp_depth; P.chr_of = c->d_smp_chr; P.depth_of = B.p_sdepth; P.sweeps = B.d_sweeps; P.out = B.p_sfreq;
+  P.n_snps = n; P.n_sweeps = n_sweeps; P.n_iv = c->n_iv; P.lds_stride = c->smp_max_m;
+  P.inv_step = 1.0 / c->step; P.iv_off = -LOG_AD_MIN * P.inv_step - 1e-9;
+  P.key = sample_mix64(seed ^ 0x9E3779B97F4A7C15ull);
+  P.rep_hi = (unsigned long long)(uint32_t)rep << 32;
+  // waves per workgroup: as many of SAMPLE_WAVES as 64 KiB of LDS hold cumulative sums for
+  int nw = SAMPLE_WAVES;
+  while (nw > 1 && (size_t)nw * (size_t)c->smp_max_m * 8 > 65536) nw >>= 1;
+  const size_t lds = (size_t)nw * (size_t)c->smp_max_m * 8;
+  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = -1; B.ivhist = nullptr; B.traced = false;
+  B.sm_n = n; B.sm_ms = 0.0;
+  HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
+  hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((n + nw - 1) / nw)), dim3(64 * nw), lds, B.stream, P);
+  HIPCHK(hipGetLastError(), "launch sample_kernel");
+  HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+  B.pending = true; B.sm_pending = true;
+  return FSCLG_OK;
+}
+
+int fsclg_sample_wait(fsclg_ctx* c, int batch, int32_t* freq_out, unsigned long long* n_degenerate) {
+  if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
+  Batch& B = c->batch[batch];
+  if (!B.pending || !B.sm_pending) return set_err(FSCLG_E_STATE, "no sample submitted on the batch");
+  if (!freq_out) return set_err(FSCLG_E_ARG, "freq_out");  // (the batch stays submitted)
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  B.pending = false; B.sm_pending = false;
+  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  float ms = 0.f, t0 = 0.f, t1 = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
+  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
+  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
+  B.sm_ms = ms;
+  c->kernel_ms += ms;
+  c->launches++;
+  c->busy.emplace_back((double)t0, (double)t1);
+  unsigned long long deg = 0;
+  for (int i = 0; i < B.sm_n; i++) {
+    freq_out[i] = B.p_sfreq[i];
+    deg += B.p_sfreq[i] < 0;
+  }
+  if (n_degenerate) *n_degenerate = deg;
+  return FSCLG_OK;
+}
+
+double fsclg_sample_last_ms(fsclg_ctx* c, int batch) {
+  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].sm_ms : 0.0;
 }
 
 int fsclg_interval_thresholds(double log_ad_step, int n_iv, double* thr) {

@@ -16,7 +16,8 @@
 
 #include "fscl_host.h"
 
-enum { T_STR, T_INT, T_DBL, T_FLAG };
+enum { T_STR, T_INT, T_DBL, T_FLAG, T_LIST };
+typedef struct { char **v; int n; } strlist_t; /* T_LIST: an option that may be given several times */
 typedef struct { char s; const char *l; void *v; int t; const char *doc; } opt_t;
 
 /* fscl.c:33-34 */
@@ -29,6 +30,54 @@ static void usage(const opt_t *o) {
     if (o->s) fprintf(stderr, "  -%c, --%-28s %s\n", o->s, o->l, o->doc);
     else fprintf(stderr, "      --%-28s %s\n", o->l, o->doc);
   }
+}
+
+static void list_add(strlist_t *l, const char *arg) {
+  l->v = realloc(l->v, sizeof(char *) * (size_t)(l->n + 1));
+  if (!l->v) { fprintf(stderr, "out of memory (options)\n"); exit(1); }
+  l->v[l->n++] = strdup(arg);
+}
+
+/* "chr:pos:alpha" options into sweeps; a bad one is fatal before anything runs on the device */
+static fscl_amd_sweep_t *parse_sweeps(const scan_t *s, const strlist_t *l, const char *opt) {
+  fscl_amd_sweep_t *sw = malloc(sizeof *sw * (size_t)(l->n ? l->n : 1));
+  int i;
+  if (!sw) logmsg(MSG_FATAL, "fscl: out of memory (sweeps)");
+  for (i = 0; i < l->n; i++) {
+    const int r = fscl_amd_parse_sweep(s, l->v[i], sw + i);
+    if (r == -2) logmsg(MSG_FATAL, "fscl: --%s=%s: unknown chromosome name", opt, l->v[i]);
+    if (r == -3) logmsg(MSG_FATAL, "fscl: --%s=%s: alpha must be positive", opt, l->v[i]);
+    if (r != 0) logmsg(MSG_FATAL, "fscl: --%s=%s: expected chr:pos:alpha", opt, l->v[i]);
+  }
+  return sw;
+}
+
+/* the --bootstrap-top scan points: descending CLR (ties in scan order, a NaN never), at their fitted
+   sweep_pos and alpha, skipping a point within window_bp of one already chosen on its chromosome */
+static fscl_amd_sweep_t *top_sweeps(const scan_t *s, int top, int window_bp, int *n_out) {
+  fscl_amd_sweep_t *sw = malloc(sizeof *sw * (size_t)(top > 0 ? top : 1));
+  char *used = calloc((size_t)(s->n_scan_pts > 0 ? s->n_scan_pts : 1), 1);
+  int n = 0, i, k;
+  if (!sw || !used) logmsg(MSG_FATAL, "fscl: out of memory (sweeps)");
+  while (n < top) {
+    int best = -1;
+    for (i = 0; i < s->n_scan_pts; i++)
+      if (!used[i] && s->scan_pts[i].clr == s->scan_pts[i].clr && (best < 0 || s->scan_pts[i].clr > s->scan_pts[best].clr))
+        best = i;
+    if (best < 0) break;
+    used[best] = 1;
+    for (k = 0; k < n; k++) {
+      long long d = (long long)s->scan_pts[best].sweep_pos - sw[k].pos;
+      if (sw[k].chr == s->scan_pts[best].chr && (d < 0 ? -d : d) <= window_bp) break;
+    }
+    if (k < n) continue;
+    sw[n].chr = s->scan_pts[best].chr; sw[n].pos = s->scan_pts[best].sweep_pos; sw[n].alpha = exp(s->scan_pts[best].lalpha);
+    if (!(sw[n].alpha > 0.0) || sw[n].alpha > 1.7976931348623157e308) continue; /* (an alpha the sampler refuses) */
+    n++;
+  }
+  free(used);
+  *n_out = n;
+  return sw;
 }
 
 /* --max-only for ms input: one line per block (fscl.c:68-69, :307-308) */
@@ -60,6 +109,9 @@ int main(int argc, char **argv) {
   char *sites_fname = NULL;
   int sites_top = 10;
   int grid_mode = 0;
+  char *simulate_fname = NULL, *simulate_seed = NULL, *bootstrap_fname = NULL;
+  strlist_t simulate_sweep = {NULL, 0}, bootstrap_sweep = {NULL, 0};
+  int simulate_rep = 0, bootstrap_reps = 100, bootstrap_window = -1, bootstrap_top = 3, need_tables;
   scan_t *s;
   double **fsp;
   opt_t opts[] = {
@@ -103,6 +155,20 @@ int main(int argc, char **argv) {
       {0, "scan-mode", &scan_mode, T_STR, "bisection (default: search_maxpos in every cell) or grid (the maximum over each cell's "
                                           "-g spaced positions, in the scan and in the permutation test; one process, parity only)"},
       {0, "permute-seed", &permute_seed, T_STR, "seed of the throughput mode's random numbers (default 0xFD821A6)"},
+      {0, "simulate-file", &simulate_fname, T_STR, "write one replicate of the data simulated under the sweep model (SNP input format) "
+                                                   "to this file; needs no scan"},
+      {0, "simulate-sweep", &simulate_sweep, T_LIST, "chr:pos:alpha of a sweep planted in --simulate-file (may be given several times; "
+                                                     "none: a neutral replicate)"},
+      {0, "simulate-seed", &simulate_seed, T_STR, "seed of the simulation and the bootstrap (default 0xFD821A6)"},
+      {0, "simulate-rep", &simulate_rep, T_INT, "replicate number of --simulate-file (default 0)"},
+      {0, "bootstrap-file", &bootstrap_fname, T_STR, "parametric bootstrap: simulate under the planted sweeps, rescan, write every "
+                                                     "replicate's estimate and a quantile summary per sweep to this file"},
+      {0, "bootstrap-reps", &bootstrap_reps, T_INT, "replicates of --bootstrap-file (default 100)"},
+      {0, "bootstrap-window", &bootstrap_window, T_INT, "a replicate's estimate is its best scan point within this many bp of the planted "
+                                                        "position (default: the -G spacing)"},
+      {0, "bootstrap-sweep", &bootstrap_sweep, T_LIST, "chr:pos:alpha of a sweep to bootstrap (may be given several times; none: the "
+                                                       "--bootstrap-top scan points)"},
+      {0, "bootstrap-top", &bootstrap_top, T_INT, "without --bootstrap-sweep, bootstrap this many scan points of greatest CLR (default 3)"},
       {0, NULL, NULL, 0, NULL}};
 
   spline_pts = N_SPLINE_KNOTS;
@@ -135,6 +201,7 @@ int main(int argc, char **argv) {
     else if (opts[j].t == T_FLAG) *(int *)opts[j].v ^= 1;
     else if (!arg) { fprintf(stderr, "Option \"%s\" needs a value (--%s=value or -x value)\n", a, opts[j].l); return 255; }
     else if (opts[j].t == T_STR) *(char **)opts[j].v = strdup(arg);
+    else if (opts[j].t == T_LIST) list_add((strlist_t *)opts[j].v, arg);
     else if (opts[j].t == T_INT) *(int *)opts[j].v = atoi(arg);
     else *(double *)opts[j].v = atof(arg);
     i += (lng || (opts[j].v && opts[j].t == T_FLAG)) ? 1 : 2;
@@ -207,6 +274,26 @@ int main(int argc, char **argv) {
     stop = 1;
   }
   if (grid_mode && small_grid_sp < 1) { logmsg(MSG_ERROR, "Error: --scan-mode=grid needs a positive -g spacing.\n"); stop = 1; }
+  if (bootstrap_fname && dont_scan && bootstrap_sweep.n == 0) {
+    logmsg(MSG_ERROR, "Error: --bootstrap-file with --no-scan needs --bootstrap-sweep (no scan points to take).\n");
+    stop = 1;
+  }
+  if (bootstrap_fname && grid_mode) { logmsg(MSG_ERROR, "Error: --bootstrap-file rescans by bisection (not with --scan-mode=grid).\n"); stop = 1; }
+  if (bootstrap_fname && getenv("WORLD_SIZE") && getenv("RANK") && atoi(getenv("WORLD_SIZE")) > 1) {
+    logmsg(MSG_ERROR, "Error: --bootstrap-file runs in one process (not with WORLD_SIZE=%s ranks).\n", getenv("WORLD_SIZE"));
+    stop = 1;
+  }
+  if (bootstrap_fname && bootstrap_reps < 0) { logmsg(MSG_ERROR, "Error: --bootstrap-reps must be >= 0.\n"); stop = 1; }
+  if (bootstrap_fname && bootstrap_top < 0) { logmsg(MSG_ERROR, "Error: --bootstrap-top must be >= 0.\n"); stop = 1; }
+  if (bootstrap_window < 0) bootstrap_window = large_grid_sp;
+  for (i = 0; i < simulate_sweep.n + bootstrap_sweep.n; i++) { /* (the chromosome names are checked once the data is loaded) */
+    const char *t = i < simulate_sweep.n ? simulate_sweep.v[i] : bootstrap_sweep.v[i - simulate_sweep.n];
+    const char *c = strrchr(t, ':');
+    if (c && !(atof(c + 1) > 0.0)) {
+      logmsg(MSG_ERROR, "Error: --%s-sweep=%s: alpha must be positive.\n", i < simulate_sweep.n ? "simulate" : "bootstrap", t);
+      stop = 1;
+    }
+  }
   if (permute_seed && !(permute_mode && !strcmp(permute_mode, "throughput")))
     logmsg(MSG_WARN, "Warning: --permute-seed is used only with --permute-mode=throughput.\n");
   if (stop) {
@@ -218,8 +305,13 @@ int main(int argc, char **argv) {
                : load_snp_input(snp_fname, include_invariant, minimum_obs_depth);
   fsp = background_fsp(s, force_neutral, bs_fname, include_invariant);
   if (output_bs_fname) output_background_fs(output_bs_fname, s, fsp);
-  if (!dont_scan) {
+  need_tables = !dont_scan || simulate_fname || bootstrap_fname;
+  if (need_tables) {
     sm_ptable_t *sm;
+    const unsigned long long sim_seed = simulate_seed ? strtoull(simulate_seed, NULL, 0) : 0xFD821A6ull;
+    fscl_amd_sweep_t *sim_sw = parse_sweeps(s, &simulate_sweep, "simulate-sweep");
+    fscl_amd_sweep_t *boot_sw = parse_sweeps(s, &bootstrap_sweep, "bootstrap-sweep");
+    int n_boot = bootstrap_sweep.n;
     const char *ws = getenv("WORLD_SIZE"), *rk = getenv("RANK");
     if (ws && rk && atoi(ws) > 1) {
       /* one process per GPU (e.g. under torch.distributed.run): GPU $LOCAL_RANK (or
@@ -249,7 +341,25 @@ int main(int argc, char **argv) {
     }
     sm = compute_sweep_model_tables(s, fsp, asc_depth, asc_min_freq, bg_only, include_invariant);
     compute_snp_null_model(s, fsp);
-    if (grid_mode) {
+    if (simulate_fname && !(ws && rk && atoi(ws) > 1 && atoi(rk) != 0)) {
+      /* one replicate under the model, at the data's own sites (rank 0 alone); no rand() draw */
+      int *freq = malloc(sizeof(int) * (size_t)(s->n_snps > 0 ? s->n_snps : 1));
+      unsigned long long n_deg = 0;
+      scan_t *q;
+      int r;
+      if (!freq) logmsg(MSG_FATAL, "fscl: out of memory (simulation)");
+      r = fscl_amd_simulate(s, sm, sim_sw, simulate_sweep.n, sim_seed, simulate_rep, freq, &n_deg);
+      if (r != 0) logmsg(MSG_FATAL, "fscl: simulation failed (code %d)", r);
+      q = fscl_amd_simulate_scan(s, freq);
+      if (fscl_amd_simulate_output(simulate_fname, q) != 0) logmsg(MSG_FATAL, "fscl: cannot write %s", simulate_fname);
+      logmsg(MSG_STATUS, "Simulation: %d sites, %d sweeps, replicate %d, %llu degenerate sites, kernel %.3f ms\n", s->n_snps,
+             simulate_sweep.n, simulate_rep, n_deg, fscl_amd_simulate_last_ms());
+      fscl_amd_scan_free(q);
+      free(freq);
+    }
+    if (dont_scan) {
+      /* tables only: the simulation above, and a bootstrap of explicit sweeps below */
+    } else if (grid_mode) {
       logmsg(MSG_STATUS, "scan mode grid: each cell's statistic is its maximum over the %d bp grid positions, in the scan "
                          "and in every permutation trial\n", small_grid_sp);
       fscl_amd_scan_chromosome_grid(s, sm, eval_range, small_grid_sp, large_grid_sp);
@@ -289,13 +399,34 @@ int main(int argc, char **argv) {
              fscl_amd_sites_last_ms());
       fscl_amd_sites_free(&st);
     }
-    if (n_permute > 0 && grid_mode)
+    if (dont_scan) {
+      /* nothing to test or to write */
+    } else if (n_permute > 0 && grid_mode)
       fscl_amd_scan_permute_grid(s, sm, n_permute, permute_nbp, eval_range, small_grid_sp, large_grid_sp, scan_width_mb);
     else if (n_permute > 0)
       scan_permute(s, sm, n_permute, permute_nbp, alpha_factor, n_threads, eval_range, bp_resl, large_grid_sp,
                    scan_width_mb);
-    if (ms_fname && maximum_only) output_block_maxima(output_fname, s, prepend_label);
+    if (dont_scan) {
+    } else if (ms_fname && maximum_only) output_block_maxima(output_fname, s, prepend_label);
     else scan_output(output_fname, s, maximum_only, n_permute, prepend_label);
+    if (bootstrap_fname) {
+      /* the parametric bootstrap, last: simulate under the sweeps, rescan, summarise */
+      fscl_amd_boot_t *bt;
+      double tm[5];
+      int r;
+      if (n_boot == 0) { free(boot_sw); boot_sw = top_sweeps(s, bootstrap_top, bootstrap_window, &n_boot); }
+      bt = malloc(sizeof *bt * ((size_t)n_boot * (size_t)bootstrap_reps + 1));
+      if (!bt) logmsg(MSG_FATAL, "fscl: out of memory (bootstrap)");
+      r = fscl_amd_bootstrap(s, sm, fsp, boot_sw, n_boot, bootstrap_reps, sim_seed, bootstrap_window, eval_range, bp_resl,
+                             large_grid_sp, bt);
+      if (r != 0) logmsg(MSG_FATAL, "fscl: bootstrap failed (code %d)", r);
+      fscl_amd_bootstrap_output(bootstrap_fname, s, boot_sw, n_boot, bootstrap_reps, bt, prepend_label);
+      fscl_amd_bootstrap_times(tm);
+      logmsg(MSG_STATUS, "Bootstrap: %d sweeps, %d replicates, %.3f s (simulation %.3f s, null model %.3f s, upload %.3f s, "
+                         "scan %.3f s)\n", n_boot, bootstrap_reps, tm[0], tm[1], tm[2], tm[3], tm[4]);
+      free(bt);
+    }
+    free(sim_sw); free(boot_sw);
     if (verbosity >= MSG_DEBUG1) {
       fscl_amd_stats_t st;
       fscl_amd_get_stats(&st);

@@ -159,6 +159,13 @@ typedef struct {
 } dev_t_;
 static dev_t_ D = {.rank = 0, .world = 1};
 
+/* the sampler's tables (fscl_amd_simulate): the context they went to (NULL: none) and their key */
+static struct {
+  fsclg_ctx *ctx;
+  uint64_t hash;
+  int n_depths;
+} SMP;
+
 static void dev_close_all(void) {
   int l, k;
   for (l = 0; l < D.n_dev; l++) fsclg_close(D.ctx[l]);
@@ -166,6 +173,7 @@ static void dev_close_all(void) {
   D.stage_cap = 0;
   D.n_dev = 0;
   D.tab_key = NULL; D.snp_key = NULL;
+  SMP.ctx = NULL;
 }
 
 int fscl_amd_set_devices(const int *devices, int n) {
@@ -2941,6 +2949,124 @@ void fscl_amd_sites_output(const char *fname, const scan_t *s, const fscl_amd_si
   }
   free(sum);
   if (fname) fclose(f);
+}
+
+/* ------------------------------------------------------ sweep-model simulation, bootstrap
+   fscl_amd_simulate draws one replicate on the first device (fsclg_sample_submit); the
+   sampler's tables are kept per tables hash.  The host-only pieces are in simulate.c. */
+static double g_sample_ms;
+static double g_boot_s[5];
+double fscl_amd_simulate_last_ms(void) { return g_sample_ms; }
+void fscl_amd_bootstrap_times(double out[5]) { memcpy(out, g_boot_s, sizeof g_boot_s); }
+
+/* the first device holds these positions and chromosome limits already (a replicate's are its
+   original's): the sampler reads nothing else of the sites */
+static int same_geometry(const scan_t *s) {
+  int i;
+  if (!D.n_dev || !D.snp_key || D.n_snps_key != s->n_snps || D.n_chr != s->n_chromosomes) return 0;
+  for (i = 0; i < D.n_chr; i++)
+    if (D.chr_start[i] != s->chr_limits[i].start_index || D.chr_n[i] != s->chr_limits[i].n_snps) return 0;
+  for (i = 0; i < s->n_snps; i++)
+    if (D.pos[i] != s->snps[i].pos) return 0;
+  return 1;
+}
+
+int fscl_amd_simulate(scan_t *s, sm_ptable_t *sm, const fscl_amd_sweep_t *sweeps, int n_sweeps,
+                      unsigned long long seed, int rep, int *freq_out, unsigned long long *n_degenerate) {
+  fsclg_sweep_t *sw;
+  int32_t *depth;
+  uint64_t h;
+  int i, r;
+  if (!s || !sm || !freq_out || n_sweeps < 0 || (n_sweeps && !sweeps)) return FSCLG_E_ARG;
+  for (i = 0; i < n_sweeps; i++)
+    if (sweeps[i].chr < 0 || sweeps[i].chr >= s->n_chromosomes || !(sweeps[i].alpha > 0.0) ||
+        sweeps[i].alpha > 1.7976931348623157e308)
+      return FSCLG_E_ARG;
+  if (n_degenerate) *n_degenerate = 0;
+  if (D.world > 1 && D.rank != 0) return FSCLG_OK; /* rank 0 alone evaluates, as the other diagnostics */
+  if (!same_geometry(s)) prepare(s, sm);
+  h = tables_hash(sm, s->n_depths);
+  if (SMP.ctx != D.ctx[0] || SMP.hash != h || SMP.n_depths != s->n_depths) {
+    double *coef_t, *neutral;
+    int32_t *dn = fh_malloc(sizeof(int32_t) * (size_t)s->n_depths, "depths");
+    int n_iv;
+    fscl_amd_sample_tables_build(sm, s->n_depths, &coef_t, &neutral, dn, &n_iv);
+    for (i = 0; i < s->n_depths; i++)
+      if (dn[i] != s->sample_depths[i])
+        logmsg(MSG_FATAL, "fscl_amd: sweep-model table %d is for depth %d, data has %d", i, dn[i], s->sample_depths[i]);
+    SMP.ctx = NULL;
+    r = fsclg_sample_tables(D.ctx[0], coef_t, neutral, dn, s->n_depths, n_iv, (LOG_AD_MAX - LOG_AD_MIN) / (n_iv + 1.));
+    free(coef_t); free(neutral); free(dn);
+    if (r != FSCLG_OK) return r;
+    SMP.ctx = D.ctx[0]; SMP.hash = h; SMP.n_depths = s->n_depths;
+  }
+  depth = fh_malloc(sizeof(int32_t) * (size_t)(s->n_snps ? s->n_snps : 1), "site depths");
+  sw = fh_malloc(sizeof(fsclg_sweep_t) * (size_t)(n_sweeps ? n_sweeps : 1), "sweeps");
+  for (i = 0; i < s->n_snps; i++) depth[i] = s->snps[i].depth_p;
+  for (i = 0; i < n_sweeps; i++) { sw[i].chr = sweeps[i].chr; sw[i].pos = sweeps[i].pos; sw[i].lalpha = log(sweeps[i].alpha); }
+  r = fsclg_sample_submit(D.ctx[0], 0, depth, sw, n_sweeps, seed, rep);
+  if (r == FSCLG_OK) {
+    int32_t *f = fh_malloc(sizeof(int32_t) * (size_t)(s->n_snps ? s->n_snps : 1), "drawn counts");
+    unsigned long long deg = 0;
+    r = fsclg_sample_wait(D.ctx[0], 0, f, &deg);
+    /* a degenerate site keeps its observed count */
+    for (i = 0; r == FSCLG_OK && i < s->n_snps; i++) freq_out[i] = f[i] < 0 ? s->snps[i].obs_freq : f[i];
+    if (r == FSCLG_OK && n_degenerate) *n_degenerate = deg;
+    g_sample_ms = fsclg_sample_last_ms(D.ctx[0], 0);
+    free(f);
+  }
+  free(depth); free(sw);
+  return r;
+}
+
+int fscl_amd_bootstrap(scan_t *s, sm_ptable_t *sm, double **fsp, const fscl_amd_sweep_t *sweeps, int n_sweeps,
+                       int reps, unsigned long long seed, int window_bp, int eval_range, int bp_resl, int large_grid_sp,
+                       fscl_amd_boot_t *out) {
+  const double t_all = fh_now();
+  double nan_ = 0.0;
+  int *freq;
+  int rep, k, i, r = FSCLG_OK;
+  if (!s || !sm || !fsp || n_sweeps < 0 || reps < 0 || (n_sweeps && !sweeps) || (n_sweeps && reps && !out))
+    return FSCLG_E_ARG;
+  if (D.world > 1) return FSCLG_E_STATE;
+  nan_ = nan_ / nan_;
+  memset(g_boot_s, 0, sizeof g_boot_s);
+  freq = fh_malloc(sizeof(int) * (size_t)(s->n_snps ? s->n_snps : 1), "drawn counts");
+  for (rep = 0; rep < reps && r == FSCLG_OK; rep++) {
+    scan_t *q;
+    double t0 = fh_now(), t1;
+    r = fscl_amd_simulate(s, sm, sweeps, n_sweeps, seed, rep, freq, NULL);
+    t1 = fh_now(); g_boot_s[1] += t1 - t0; t0 = t1;
+    if (r != FSCLG_OK) break;
+    q = fscl_amd_simulate_scan(s, freq);
+    compute_snp_null_model(q, fsp);
+    t1 = fh_now(); g_boot_s[2] += t1 - t0; t0 = t1;
+    prepare(q, sm); /* (timed on its own; scan_chromosome finds the replicate uploaded) */
+    t1 = fh_now(); g_boot_s[3] += t1 - t0; t0 = t1;
+    scan_chromosome(q, sm, eval_range, bp_resl, large_grid_sp, 1);
+    g_boot_s[4] += fh_now() - t0;
+    for (k = 0; k < n_sweeps; k++) {
+      fscl_amd_boot_t *b = out + (size_t)k * (size_t)reps + rep;
+      const scan_pt_t *best = NULL;
+      for (i = 0; i < q->n_scan_pts; i++) {
+        const scan_pt_t *p = q->scan_pts + i;
+        long long d = (long long)p->sweep_pos - sweeps[k].pos;
+        if (d < 0) d = -d;
+        if (p->chr != sweeps[k].chr || d > window_bp) continue;
+        if (!best || p->clr > best->clr) best = p; /* the first point wins a tie */
+      }
+      memset(b, 0, sizeof *b);
+      b->sweep = k; b->rep = rep; b->chr = sweeps[k].chr; b->planted_pos = sweeps[k].pos;
+      b->planted_alpha = sweeps[k].alpha;
+      b->est_pos = best ? best->sweep_pos : -1;
+      b->est_lalpha = best ? best->lalpha : nan_;
+      b->clr = best ? best->clr : nan_;
+    }
+    fscl_amd_scan_free(q);
+  }
+  free(freq);
+  g_boot_s[0] = fh_now() - t_all;
+  return r;
 }
 
 /* the points fscl_amd_scan_chromosome_grid made last: fscl_amd_scan_permute_grid tests only

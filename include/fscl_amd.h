@@ -431,6 +431,85 @@ void fscl_amd_sites_output(const char *fname, const scan_t *scan_obj, const fscl
 /* the summed kernel milliseconds of the last evaluation (the slowest device's) */
 double fscl_amd_sites_last_ms(void);
 
+/* ---- sweep-model simulation and parametric bootstrap (--simulate-file, --bootstrap-file) ----
+   Data under the model the scan fits, at the loaded data's own positions, depths, folded flags
+   and chromosome limits (the reference's sm-sample.c draws uniform positions at one depth): per
+   site one derived count from the model spectrum of its nearest sweep, by the site semantics of
+   fsclg_sample_submit (include/fsclg.h) -- the scan's three-branch log distance, the tables as
+   built (ascertainment correction included), a strict choice rule that never draws a count of
+   probability 0, and a counter-based uniform that is a function of (seed, rep, site) alone.
+
+   A sweep is (chromosome index, position, alpha > 0).  fscl_amd_parse_sweep reads "name:pos:alpha"
+   (the name as in the input; the last two colons separate): 0, or -1 malformed, -2 unknown
+   chromosome, -3 alpha not positive or not finite.  fscl_amd_nearest_sweep: the index of the sweep
+   that governs a site at (chr, pos) -- least |pos - sweep pos|, a tie to the lower sweep position,
+   then to the first given -- or -1 when the chromosome has none (the rule the kernel applies).
+
+   fscl_amd_simulate: replicate `rep` of `seed` into freq_out[scan_obj->n_snps], the drawn derived
+   counts 1 .. n-1; a degenerate site (model spectrum summing to 0 or not finite) keeps its observed
+   count and is counted in *n_degenerate (may be NULL).  n_sweeps = 0 is a neutral replicate.  The
+   sampler's tables (every unfolded row of every depth, interval-major) are built on first use and
+   kept while the tables' hash stays; the sites go up as for a scan unless the device already holds
+   these positions and chromosome limits.  Runs on the first device; with several ranks, rank 0
+   alone evaluates (the others return FSCLG_OK and leave freq_out alone).  Neither scan_obj nor the
+   permutation stream is touched.  FSCLG_E_ARG: alpha <= 0 or not finite, a chromosome out of
+   range, n_sweeps < 0; otherwise a fsclg status code.
+   fscl_amd_simulate_scan: a new scan_t with the same positions, depths, folded flags, chromosome
+   limits and names, sharing nothing with the original, without scan points; obs_freq = freq[i], or
+   min(freq[i], n - freq[i]) at a folded site; null_logl 0 (the caller runs compute_snp_null_model
+   and scan_chromosome on it, as for loaded data).  fscl_amd_scan_free releases it.
+   fscl_amd_simulate_output: the SNP input format, one line per site "chr pos derived_count
+   sample_size folded", which load_snp_input reads back to the same sites; 0, or -1 if the file
+   cannot be written.
+
+   fscl_amd_bootstrap: for rep = 0 .. reps-1 -- simulate with every sweep planted, build the
+   replicate scan, recompute its null model from fsp, scan_chromosome it (bisection), and per
+   planted sweep record the replicate's scan point of greatest CLR with |sweep_pos - planted pos|
+   <= window_bp on that chromosome (the first on a tie; est_pos -1 and NaN values when there is
+   none) -- into out[sweep * reps + rep].  scan_obj, its scan points and its permutation counters
+   stay as they are; the next call on scan_obj uploads it again, as a fresh scan does.  One process
+   only (FSCLG_E_STATE with several ranks); FSCLG_E_ARG as fscl_amd_simulate, or reps < 0.
+   fscl_amd_bootstrap_times: wall seconds of the last bootstrap -- total, simulation, null model and
+   replicate building, upload of the replicates, scanning.
+   fscl_amd_bootstrap_output (fname NULL: stdout; host only), per sweep one row per replicate
+     [label TAB] chromosome TAB planted_pos TAB planted_alpha (%1.3e) TAB rep TAB est_pos TAB
+       est_alpha (%1.3e) TAB CLR (%1.2f)          (NA NA NA when the replicate found no point)
+   then one summary row
+     [label TAB] chromosome TAB planted_pos TAB summary TAB reps TAB n_found TAB pos_q025 TAB pos_q50
+       TAB pos_q975 TAB alpha_q025 TAB alpha_q50 TAB alpha_q975 TAB clr_q50
+   where quantile q of the n_found found values is sorted[floor(q * (n_found - 1))], each column
+   sorted on its own, and NA when n_found = 0. */
+typedef struct {
+  int chr;
+  int pos;
+  double alpha;
+} fscl_amd_sweep_t;
+typedef struct {
+  int32_t sweep, rep, chr, planted_pos;
+  double planted_alpha;
+  int32_t est_pos, pad;       /* -1: no scan point within the window */
+  double est_lalpha, clr;     /* NaN then */
+} fscl_amd_boot_t;
+int fscl_amd_parse_sweep(const scan_t *scan_obj, const char *text, fscl_amd_sweep_t *out);
+int fscl_amd_nearest_sweep(const fscl_amd_sweep_t *sweeps, int n_sweeps, int chr, int pos);
+int fscl_amd_simulate(scan_t *scan_obj, sm_ptable_t *sm_p, const fscl_amd_sweep_t *sweeps, int n_sweeps,
+                      unsigned long long seed, int rep, int *freq_out, unsigned long long *n_degenerate);
+scan_t *fscl_amd_simulate_scan(const scan_t *scan_obj, const int *freq);
+void fscl_amd_scan_free(scan_t *scan_obj);
+int fscl_amd_simulate_output(const char *fname, const scan_t *scan_obj);
+double fscl_amd_simulate_last_ms(void);
+int fscl_amd_bootstrap(scan_t *scan_obj, sm_ptable_t *sm_p, double **fsp, const fscl_amd_sweep_t *sweeps, int n_sweeps,
+                       int reps, unsigned long long seed, int window_bp, int eval_range, int bp_resl, int large_grid_sp,
+                       fscl_amd_boot_t *out);
+void fscl_amd_bootstrap_times(double out[5]);
+void fscl_amd_bootstrap_output(const char *fname, const scan_t *scan_obj, const fscl_amd_sweep_t *sweeps, int n_sweeps,
+                               int reps, const fscl_amd_boot_t *out, const char *prepend_label);
+/* the sampler's tables of n_depths depths, for fsclg_sample_tables: every unfolded row f = 1 .. n-1
+   interval-major ([depth][interval][f][c0..c3]) and the neutral probabilities fsp[1 .. n-1]; both
+   malloc'd, *n_iv the splines' interval count (host only) */
+void fscl_amd_sample_tables_build(const sm_ptable_t *sm_p, int n_depths, double **coef_t, double **neutral,
+                                  int32_t *depth_n, int *n_iv);
+
 /* release the device context (tables / snps) */
 void fscl_amd_shutdown(void);
 

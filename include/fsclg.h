@@ -322,6 +322,50 @@ int fsclg_sites_wait(fsclg_ctx *c, int batch, fsclg_site_hdr_t *hdr, double *ter
 double fsclg_sites_last_ms(fsclg_ctx *c, int batch);
 size_t fsclg_sites_cap(void);
 
+/* Sweep-model sampler: one replicate of derived counts under the model the scan fits, at the
+   positions and chromosome limits of fsclg_upload_snps.
+   fsclg_sample_tables uploads the sampler's own tables (the scan's hold only the rows some site
+   uses): coef_t, every unfolded row f = 1 .. n-1 of every depth, interval-major
+   [depth][interval][f][c0..c3] (depth d starts after the 4 * n_iv * (depth_n[e] - 1) doubles of
+   the depths e < d), and neutral, per depth the neutral probabilities fsp[1 .. n-1] one depth
+   after another (sum of depth_n[d] - 1 doubles).  n_iv and log_ad_step must be those of
+   fsclg_upload_tables, whose interval thresholds and log table the sampler shares (FSCLG_E_STATE
+   before it, FSCLG_E_ARG when they differ; a depth_n below 2 or above 8192 is FSCLG_E_ARG).
+   fsclg_sample_submit draws site i (the index of fsclg_upload_snps), of depth index
+   depth_of_site[i] and sample size n:
+     1. the nearest sweep among those of the site's chromosome: least |pos_i - sweep pos|, a tie to
+        the lower sweep position, then to the first in sweeps[];
+     2. log_ad = logt(|pos_i - sweep pos|) + lalpha with the search kernels' three-branch logt
+        (logt(0) = 0);
+     3. p_f = fsp[f] if the chromosome has no sweep or log_ad > LOG_AD_MAX, else exp(spline_f(log_ad))
+        with the scan's interval (clamped to 0 below LOG_AD_MIN, log_ad itself not clamped); a p_f
+        that is NaN, negative or infinite counts as 0;
+     4. u = (mix64(mix64(seed ^ 0x9E3779B97F4A7C15) ^ ((uint64)(uint32)rep << 32 | (uint32)i)) >> 11)
+        * 2^-53, mix64 splitmix64's output function: no state, a function of (seed, rep, i);
+     5. with S = sum p_f and t = u * S the least f whose cumulative sum C_f > t and whose p_f > 0
+        (the greatest f with p_f > 0 if rounding leaves none): an f of probability 0 is never drawn;
+     6. S zero or not finite: the site is degenerate, freq_out[i] = -1.
+   The cumulative sums are formed in a fixed order (a wave scan per 64 counts), with no atomics:
+   the same build, seed and rep give the same bytes; the neutral sites read a per-depth prefix table
+   summed sequentially on the host.  A site whose t lies within rounding of a C_f may differ from a
+   sequential restatement.  Asynchronous like fsclg_sites_submit / fsclg_sites_wait on any batch
+   (no slot: the positions are the uploaded ones); depth_of_site and sweeps are copied.
+   fsclg_sample_wait stores the n_snps derived counts (1 .. n-1, or -1) and the number of degenerate
+   sites.  Errors: FSCLG_E_ARG for a bad batch, a depth index outside the tables, n_sweeps < 0 or
+   above 4096, a sweep chromosome out of range, a lalpha that is NaN; FSCLG_E_STATE for tables or
+   SNPs not uploaded, a batch not waited for (submit), no sample submitted on it (wait).
+   fsclg_sample_last_ms: the kernel's own time (HIP events) of the batch's last sample. */
+typedef struct {
+  int32_t chr, pos;
+  double lalpha;
+} fsclg_sweep_t;
+int fsclg_sample_tables(fsclg_ctx *c, const double *coef_t, const double *neutral, const int32_t *depth_n, int n_depths,
+                        int n_iv, double log_ad_step);
+int fsclg_sample_submit(fsclg_ctx *c, int batch, const int32_t *depth_of_site, const fsclg_sweep_t *sweeps, int n_sweeps,
+                        unsigned long long seed, int rep);
+int fsclg_sample_wait(fsclg_ctx *c, int batch, int32_t *freq_out, unsigned long long *n_degenerate);
+double fsclg_sample_last_ms(fsclg_ctx *c, int batch);
+
 /* the exact interval thresholds the kernel uses in place of spline_interpolate's
    division (sm-spline.c:52): thr[j] = least double x with
    (int)((x - LOG_AD_MIN) / log_ad_step) >= j, for j = 1..n_iv (thr has n_iv+1 slots) */

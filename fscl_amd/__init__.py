@@ -34,6 +34,7 @@ __all__ = [
     "SITES_DTYPE", "SITE_REQ_DTYPE", "SITES_SUMMARY_DTYPE",
     "simulate", "simulate_scan", "simulate_output", "simulate_last_ms", "scan_free", "bootstrap", "bootstrap_output",
     "bootstrap_times", "parse_sweep", "nearest_sweep", "SWEEP_DTYPE", "BOOT_DTYPE",
+    "tail_fit", "tail_runs", "tail_output", "tail_last_ms", "tail_summary", "tail_records", "TAIL_DTYPE", "TAIL_FLAGS",
 ]
 
 ROOT = Path(__file__).resolve().parent
@@ -114,6 +115,12 @@ class SitesT(C.Structure):  # fscl_amd_sites_t
                 ("n_terms", C.c_size_t)]
 
 
+class TailT(C.Structure):  # fscl_amd_tail_t
+    _fields_ = [("n", C.c_int), ("df", C.c_int), ("min_n", C.c_int), ("pt", C.c_void_p), ("n_fit", C.c_int),
+                ("n_central", C.c_int), ("n_nofit", C.c_int), ("n_calibration", C.c_int), ("calibration", C.c_double),
+                ("kernel_ms", C.c_double), ("wall_s", C.c_double)]
+
+
 class PointT(C.Structure):  # fsclg_point_t
     _fields_ = [("chr", C.c_int32), ("nearest_snp", C.c_int32), ("sweep_pos", C.c_int32), ("n_snps", C.c_int32),
                 ("window_start", C.c_int32), ("window_end", C.c_int32), ("flags", C.c_int32), ("cost", C.c_uint32),
@@ -154,6 +161,9 @@ EXPORTS = [
     "fscl_amd_simulate", "fscl_amd_simulate_scan", "fscl_amd_scan_free", "fscl_amd_simulate_output",
     "fscl_amd_simulate_last_ms", "fscl_amd_bootstrap", "fscl_amd_bootstrap_times", "fscl_amd_bootstrap_output",
     "fscl_amd_parse_sweep", "fscl_amd_nearest_sweep", "fscl_amd_sample_tables_build",
+    "fsclg_tail_submit", "fsclg_tail_wait", "fsclg_tail_last_ms",
+    "fscl_amd_tail_fit", "fscl_amd_tail_runs", "fscl_amd_tail_last_ms", "fscl_amd_tail_free", "fscl_amd_tail_count",
+    "fscl_amd_tail_chunk", "fscl_amd_tail_pack", "fscl_amd_tail_log10p", "fscl_amd_tail_summary", "fscl_amd_tail_output",
 ]
 
 
@@ -242,6 +252,13 @@ def _load() -> C.CDLL:
                                          C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
         "fscl_amd_bootstrap_times": (None, [P(C.c_double)]),
         "fscl_amd_bootstrap_output": (None, [C.c_char_p, P(ScanT), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_char_p]),
+        "fscl_amd_tail_fit": (C.c_int, [P(ScanT), C.c_int, C.c_int, P(TailT)]),
+        "fscl_amd_tail_runs": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p]),
+        "fscl_amd_tail_last_ms": (C.c_double, []),
+        "fscl_amd_tail_free": (None, [P(TailT)]),
+        "fscl_amd_tail_summary": (None, [P(ScanT), P(TailT)]),
+        "fscl_amd_tail_output": (C.c_int, [C.c_char_p, P(ScanT), P(TailT), C.c_char_p]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -789,6 +806,99 @@ def bootstrap_output(path, scan, sweeps, reps: int, rows, label=None) -> None:
                                         b.ctypes.data if len(b) else None, _b(label))
 
 
+# fsclg_tail_t: one point's noncentral chi-square fit; flag 0 fit, 1 central (lambda = 0), 2 nofit (NaN lambda, logl,
+# log10_q)
+TAIL_DTYPE = np.dtype([("m", "i4"), ("m_pos", "i4"), ("mean", "f8"), ("variance", "f8"), ("lambda", "f8"), ("logl", "f8"),
+                       ("log10_q", "f8"), ("flag", "i4"), ("pad", "i4")])
+TAIL_FLAGS = ("fit", "central", "nofit")
+TAIL_SAVE = 10000  # FSCL_AMD_TAIL_SAVE: the null CLRs a point keeps
+assert TAIL_DTYPE.itemsize == 56
+
+
+def _tail_df(df) -> int:
+    if int(df) != df or int(df) < 2 or int(df) % 2:
+        raise ValueError("df must be an even integer >= 2")
+    return int(df)
+
+
+def tail_records(scan) -> list:
+    """The used prefix of every scan point's saved null CLRs (float32 copies, in the record's own order)."""
+    s = scan.contents
+    out = []
+    for i in range(s.n_scan_pts):
+        q = s.scan_pts[i]
+        m = min(q.permute_n, TAIL_SAVE) if q.permute_clr and q.permute_n > 0 else 0
+        out.append(np.ctypeslib.as_array(q.permute_clr, shape=(m,)).copy() if m else np.zeros(0, dtype=np.float32))
+    return out
+
+
+def tail_runs(samples, offsets, x0, df: int = 2, min_n: int = 20, counts=None) -> np.ndarray:
+    """The projected-tail fit of raw records (include/fscl_amd.h): point p holds the floats
+    samples[offsets[p]:offsets[p + 1]] (``offsets`` has one entry more than there are points; or give
+    ``counts``) and the observed value x0[p].  Needs no scan.  A TAIL_DTYPE array."""
+    df = _tail_df(df)
+    smp = np.ascontiguousarray(samples, dtype=np.float32)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    x = np.ascontiguousarray(x0, dtype=np.float64)
+    if counts is None:
+        if len(off) != len(x) + 1:
+            raise ValueError("offsets must hold one entry more than x0")
+        cnt = np.ascontiguousarray(np.diff(off.astype(np.int64)), dtype=np.int32)
+        off = np.ascontiguousarray(off[:-1])
+    else:
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    if len(cnt) != len(x) or len(off) != len(x):
+        raise ValueError("one offset, count and x0 per point")
+    out = np.zeros(max(len(x), 1), dtype=TAIL_DTYPE)
+    _curve_check(get_lib().fscl_amd_tail_runs(smp.ctypes.data if len(smp) else None, len(smp), off.ctypes.data, cnt.ctypes.data,
+                                              x.ctypes.data, len(x), df, int(min_n), out.ctypes.data), "fscl_amd_tail_runs")
+    return out[:len(x)]
+
+
+def tail_fit(scan, df: int = 2, min_n: int = 20) -> np.ndarray:
+    """The projected-tail fit of every scan point after scan_permute / scan_permute_grid: a TAIL_DTYPE array
+    in scan-point order."""
+    df = _tail_df(df)
+    t = TailT()
+    _curve_check(get_lib().fscl_amd_tail_fit(scan, df, int(min_n), C.byref(t)), "fscl_amd_tail_fit")
+    out = np.zeros(t.n, dtype=TAIL_DTYPE)
+    if t.n:
+        C.memmove(out.ctypes.data, t.pt, t.n * TAIL_DTYPE.itemsize)
+    get_lib().fscl_amd_tail_free(C.byref(t))
+    return out
+
+
+def _tail_struct(rows, df, min_n):
+    r = np.ascontiguousarray(rows, dtype=TAIL_DTYPE)
+    t = TailT()
+    t.n, t.df, t.min_n, t.pt = len(r), _tail_df(df), int(min_n), r.ctypes.data if len(r) else None
+    return t, r
+
+
+def tail_summary(scan, rows, df: int = 2, min_n: int = 20) -> dict:
+    """Counts of fit / central / nofit rows and the calibration figure (median of log10 p_tail - log10
+    p_empirical over the fitted points with permute_p >= 5).  Host only."""
+    if len(rows) != scan.contents.n_scan_pts:
+        raise ValueError("one row per scan point")
+    t, keep = _tail_struct(rows, df, min_n)
+    get_lib().fscl_amd_tail_summary(scan, C.byref(t))
+    return {"n_fit": t.n_fit, "n_central": t.n_central, "n_nofit": t.n_nofit, "n_calibration": t.n_calibration,
+            "calibration": t.calibration}
+
+
+def tail_output(path, scan, rows, df: int = 2, label=None) -> None:
+    """The --tail-file format (include/fscl_amd.h), one row per scan point.  Host only."""
+    if len(rows) != scan.contents.n_scan_pts:
+        raise ValueError("one row per scan point")
+    t, keep = _tail_struct(rows, df, 0)
+    if get_lib().fscl_amd_tail_output(_b(path), scan, C.byref(t), _b(label)) != 0:
+        raise OSError(f"cannot write {path}")
+
+
+def tail_last_ms() -> float:
+    return float(get_lib().fscl_amd_tail_last_ms())
+
+
 def get_stats() -> dict:
     st = Stats()
     get_lib().fscl_amd_get_stats(C.byref(st))
@@ -875,7 +985,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         label=None, eval_range=81920, bp_resl=128, verbosity=1, permute_mode="parity", permute_seed=0xFD821A6,
         profile_file=None, small_grid_sp=1000, scan_mode="bisection", alpha_file=None, alpha_drop=2.0,
         sites_file=None, sites_top=10, simulate_file=None, simulate_sweeps=(), simulate_seed=0xFD821A6, simulate_rep=0,
-        bootstrap_file=None, bootstrap_reps=100, bootstrap_window=None, bootstrap_sweeps=(), bootstrap_top=3):
+        bootstrap_file=None, bootstrap_reps=100, bootstrap_window=None, bootstrap_sweeps=(), bootstrap_top=3,
+        tail_file=None, tail_df=2, tail_min_n=20):
     """The fscl main() pipeline (fscl.c:316-337) in-process; returns the scan_t
     pointer (points(scan) reads the results).  permute_mode "throughput": the
     counter-based permutation test (set_permute_mode).  scan_mode "grid": the CLI's
@@ -890,6 +1001,12 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         raise ValueError("the bootstrap rescans by bisection (not with scan_mode grid)")
     if bootstrap_file is not None and (int(bootstrap_reps) < 0 or int(bootstrap_top) < 0):
         raise ValueError("bootstrap_reps and bootstrap_top must be >= 0")
+    if tail_file is not None:
+        _tail_df(tail_df)
+        if int(n_permute) <= 0:
+            raise ValueError("tail_file needs the permutation test (n_permute > 0)")
+        if int(tail_min_n) < 1:
+            raise ValueError("tail_min_n must be >= 1")
     get_lib().configure_logmsg(int(verbosity))
     set_permute_mode(permute_mode, permute_seed)
     init_log_table()
@@ -923,6 +1040,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         scan_permute(scan, tab, n_permute, permute_nbp, 1.0, 1, eval_range, bp_resl, large_grid_sp, scan_width_mb)
     if output is not None:
         scan_output(output, scan, max_only, n_permute, label)
+    if tail_file is not None:  # the CLI's --tail-file: after the permutation test and the output
+        tail_output(tail_file, scan, tail_fit(scan, tail_df, tail_min_n), tail_df, label)
     if bootstrap_file is not None:  # the CLI's --bootstrap-file, last
         win = int(large_grid_sp if bootstrap_window is None else bootstrap_window)
         if not boot_sw:  # the scan points of greatest CLR, none within the window of one already chosen

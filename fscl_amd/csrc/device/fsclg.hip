@@ -2713,6 +2713,192 @@ sample_kernel(SampleParams P) {
   if (lane == 0) P.out[i] = f_out;
 }
 
+// ------------------------------------------------------------ projected tail
+// A noncentral chi-square fit of every point's null record and its upper tail at the observed
+// value (fsclg_tail_submit).  One wave per point, TAIL_WAVES points per workgroup; the waves share
+// nothing, so there is no LDS and no barrier.
+// Fit: lanes stride over the point's samples.  A lane sums its sample's Poisson-mixture series
+// t_j = a^j b^(h+j-1) / (j! (h+j-1)!) outward from the largest term j* (j* (j* + h - 1) ~ a b),
+// scaled by it: t_{j+1} / t_j = a b / ((j+1) (j+h)), one division per term and no exp or log.
+// With S0 = sum t_j and S1 = sum j t_j the score term is f_{df+2} / f_df - 1 = S1 / (a S0) - 1
+// (t_j b / (h+j) = t_{j+1} (j+1) / a).  Every search step ends in an xor-butterfly wave sum, whose
+// result is the same bits in every lane, so the bisection's branches are wave-uniform.  The final
+// pass adds log t_j* (one log and two lgamma per sample) for logl.
+// Tail: lanes over i = 64 trip + lane.  d_i = b0^i / i! is formed as exp(ld_i - sigma), sigma the
+// running maximum of ld; an inclusive wave scan on top of the carry of the trips before gives
+// C_{i+1} = sum_{i' <= i} d_i' (scaled), and with j = i + 1 - h the term log T_j = log w_j + sigma
+// + log C, w_j = a^j / j!.  The T_j go into a running-maximum sum per lane.  No exponent exceeds
+// log(h + j), so nothing overflows, and nothing that matters underflows.
+constexpr int TAIL_WAVES = 4;
+constexpr int TAIL_SERIES_CAP = 4096;     // terms either way from the largest term of a density series
+constexpr int TAIL_TRIP_CAP = 1 << 14;    // trips of 64 terms of the tail sum
+constexpr int TAIL_BISECT = 60;
+constexpr int TAIL_DOUBLE = 64;           // doublings of the bracket
+struct TailParams {
+  const float* samples;
+  const unsigned long long* off;   // (host memory)
+  const int32_t* cnt;              // (host memory)
+  const double* x0;                // (host memory)
+  fsclg_tail_t* out;               // (host memory)
+  int n_points, h, min_n;
+};
+
+__device__ __forceinline__ double tail_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double tail_wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ bool tail_positive(float x) { return x > 0.f && x <= 3.402823466e38f; }
+
+// S0 = sum_j t_j / t_j*, S1 = sum_j j t_j / t_j* of one sample; returns j*.  S0 is NaN when a
+// direction needs more than TAIL_SERIES_CAP terms.
+__device__ __forceinline__ double tail_series(double a, double b, double hm1, double& S0, double& S1) {
+  const double P = a * b;
+  double js = floor(0.5 * (sqrt(hm1 * hm1 + 4.0 * P) - hm1));
+  if (!(js >= 0.0)) js = 0.0;
+  double s0 = 1.0, s1 = js, t = 1.0, j = js;
+  int n;
+  for (n = 0; n < TAIL_SERIES_CAP; n++) {
+    t *= P / ((j + 1.0) * (j + 1.0 + hm1));
+    j += 1.0;
+    if (!(t > s0 * 0x1p-64)) break;
+    s0 += t; s1 += j * t;
+  }
+  bool capped = n == TAIL_SERIES_CAP;
+  t = 1.0; j = js;
+  for (n = 0; n < TAIL_SERIES_CAP && j > 0.0; n++) {
+    t *= j * (j + hm1) / P;
+    j -= 1.0;
+    if (!(t > s0 * 0x1p-64)) break;
+    s0 += t; s1 += j * t;
+  }
+  capped = capped || (n == TAIL_SERIES_CAP && j > 0.0);
+  S0 = capped ? __builtin_nan("") : s0;
+  S1 = s1;
+  return js;
+}
+
+// sum over the point's positive samples of f_{df+2} / f_df - 1 at lambda = 2 a (twice the score)
+__device__ __forceinline__ double tail_score(const float* __restrict__ x, int m, int lane, double a, double h) {
+  double acc = 0.0;
+  for (int i = lane; i < m; i += 64) {
+    const float xf = x[i];
+    if (!tail_positive(xf)) continue;
+    const double b = 0.5 * (double)xf;
+    double S0, S1;
+    tail_series(a, b, h - 1.0, S0, S1);
+    acc += (a > 0.0 ? S1 / (a * S0) : b / h) - 1.0;
+  }
+  return tail_wave_sum(acc);
+}
+
+__global__ void __launch_bounds__(64 * TAIL_WAVES)
+tail_kernel(TailParams P) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const long long pt = (long long)blockIdx.x * TAIL_WAVES + wave;
+  if (pt >= P.n_points) return;
+  const float* __restrict__ x = P.samples + P.off[pt];
+  const int m = P.cnt[pt];
+  const double h = (double)P.h, df = 2.0 * h, hm1 = h - 1.0;
+  const double nan_ = __builtin_nan(""), ninf = -__builtin_inf();
+  // the positive samples: their number, mean and variance (two passes)
+  double cnt = 0.0, sum = 0.0;
+  for (int i = lane; i < m; i += 64) {
+    const float xf = x[i];
+    if (tail_positive(xf)) { cnt += 1.0; sum += (double)xf; }
+  }
+  const int m_pos = (int)tail_wave_sum(cnt);
+  const double mean = m_pos > 0 ? tail_wave_sum(sum) / (double)m_pos : nan_;
+  double ss = 0.0;
+  for (int i = lane; i < m; i += 64) {
+    const float xf = x[i];
+    if (tail_positive(xf)) { const double d = (double)xf - mean; ss += d * d; }
+  }
+  const double var = m_pos > 1 ? tail_wave_sum(ss) / (double)(m_pos - 1) : nan_;
+  fsclg_tail_t R;
+  R.m = m; R.m_pos = m_pos; R.mean = mean; R.variance = var;
+  R.lambda = nan_; R.logl = nan_; R.log10_q = nan_; R.flag = FSCLG_TAIL_NOFIT; R.pad = 0;
+  if (m_pos >= max(P.min_n, 1)) {
+    double lam = 0.0;
+    R.flag = FSCLG_TAIL_CENTRAL;
+    if (mean > df) {
+      R.flag = FSCLG_TAIL_FIT;
+      double lo = 0.0, hi = fmax(1.0, 2.0 * (mean - df));
+      for (int k = 0; k < TAIL_DOUBLE; k++) {
+        if (!(tail_score(x, m, lane, 0.5 * hi, h) > 0.0)) break;
+        lo = hi; hi *= 2.0;
+      }
+      for (int k = 0; k < TAIL_BISECT; k++) {
+        const double mid = 0.5 * (lo + hi);
+        if (!(mid > lo && mid < hi)) break;
+        if (tail_score(x, m, lane, 0.5 * mid, h) > 0.0) lo = mid; else hi = mid;
+      }
+      lam = 0.5 * (lo + hi);
+    }
+    // logl at lambda
+    const double a = 0.5 * lam, la = a > 0.0 ? log(a) : 0.0;
+    double acc = 0.0;
+    for (int i = lane; i < m; i += 64) {
+      const float xf = x[i];
+      if (!tail_positive(xf)) continue;
+      const double b = 0.5 * (double)xf;
+      double S0, S1;
+      const double js = tail_series(a, b, hm1, S0, S1);
+      const double lt = (js > 0.0 ? js * la : 0.0) + (hm1 + js) * log(b) - lgamma(js + 1.0) - lgamma(h + js);
+      acc += ((lt + log(S0)) - a - b) - 0.6931471805599453;
+    }
+    R.lambda = lam;
+    R.logl = tail_wave_sum(acc);
+    // the tail at x0
+    const double x0 = P.x0[pt];
+    double lq = 0.0;
+    if (x0 > 0.0) {
+      const double b0 = 0.5 * x0, lb = log(b0);
+      double jst = floor(0.5 * (sqrt(hm1 * hm1 + 4.0 * a * b0) - hm1));
+      if (!(jst >= 0.0)) jst = 0.0;
+      const double jstop = 2.0 * fmax(a, jst) + 2.0;
+      double sigma = ninf, carry = 0.0, M = ninf, tacc = 0.0;
+      bool done = false;
+      for (int trip = 0; trip < TAIL_TRIP_CAP; trip++) {
+        const double i = 64.0 * (double)trip + (double)lane;
+        const double ld = (i > 0.0 ? i * lb : 0.0) - lgamma(i + 1.0);
+        const double sn = fmax(sigma, tail_wave_max(ld));   // finite: ld of lane 0 of trip 0 is 0
+        carry = sigma > ninf ? carry * exp(sigma - sn) : 0.0;
+        sigma = sn;
+        double v = exp(ld - sigma);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const double u = __shfl_up(v, o, 64);
+          if (lane >= o) v += u;
+        }
+        v += carry;
+        carry = __shfl(v, 63, 64);
+        const double j = i - hm1;
+        double lT = ninf;
+        if (j >= 0.0) {
+          const double lw = j > 0.0 ? (a > 0.0 ? j * la - lgamma(j + 1.0) : ninf) : 0.0;
+          lT = lw + sigma + log(v);
+        }
+        const double tmax = tail_wave_max(lT);
+        const double Mn = fmax(M, tmax);
+        if (Mn > ninf) {
+          tacc = (M > ninf ? tacc * exp(M - Mn) : 0.0) + (lT > ninf ? exp(lT - Mn) : 0.0);
+          M = Mn;
+        }
+        if (64.0 * (double)(trip + 1) - hm1 > jstop && tmax < M - 50.0) { done = true; break; }
+      }
+      lq = done ? fmin(((M + log(tail_wave_sum(tacc))) - a) - b0, 0.0) : nan_;
+    }
+    R.log10_q = lq * 0.4342944819032518;
+  }
+  if (lane == 0) P.out[pt] = R;
+}
+
 // ------------------------------------------------------------ window null sums
 // init_scan_result's window sum (scan-chromosome.c:92-94) for every window start of the
 // chromosomes longer than the window: acc = 0.0; acc += null_logl[i] for i = ws..ws+W-1,
@@ -3333,6 +3519,19 @@ struct Batch {
   int sm_n = 0;                     // sites of the submitted sample
   bool sm_pending = false;
   double sm_ms = 0.0;               // kernel time of the batch's last sample
+  // fsclg_tail_submit: the samples (pinned staging, copied to d_tsamples on the batch's stream); offsets,
+  // counts, observed values and results (pinned; read / written by the kernel)
+  float* p_tsamples = nullptr;
+  float* d_tsamples = nullptr;
+  unsigned long long* p_toff = nullptr;
+  int32_t* p_tcnt = nullptr;
+  double* p_tx0 = nullptr;
+  fsclg_tail_t* p_tout = nullptr;
+  int tsamp_cap = 0, toff_cap = 0, tcnt_cap = 0, tx0_cap = 0, tout_cap = 0;
+  size_t dtsamp_cap = 0;
+  int tl_n = 0;                     // points of the submitted tail call
+  bool tl_pending = false;
+  double tl_ms = 0.0;               // kernel time of the batch's last tail call
 };
 
 struct fsclg_ctx {
@@ -3549,9 +3748,11 @@ int fsclg_close(fsclg_ctx* c) {
     if (B.d_xacc) hipFree(B.d_xacc);
     if (B.d_xcnt) hipFree(B.d_xcnt);
     if (B.d_sweeps) hipFree(B.d_sweeps);
+    if (B.d_tsamples) hipFree(B.d_tsamples);
     for (void* p : {(void*)B.p_cells, (void*)B.p_out, (void*)B.p_epos, (void*)B.p_cell_ep, (void*)B.p_ctrace,
                     (void*)B.p_cmchunks, (void*)B.p_curve, (void*)B.p_sreq, (void*)B.p_shdr, (void*)B.p_stasks,
-                    (void*)B.p_sterms, (void*)B.p_sdepth, (void*)B.p_sfreq, (void*)B.p_ssweeps})
+                    (void*)B.p_sterms, (void*)B.p_sdepth, (void*)B.p_sfreq, (void*)B.p_ssweeps,
+                    (void*)B.p_tsamples, (void*)B.p_toff, (void*)B.p_tcnt, (void*)B.p_tx0, (void*)B.p_tout})
       if (p) hipHostFree(p);
     hipEventDestroy(B.ev0);
     hipEventDestroy(B.ev1);
@@ -4872,6 +5073,7 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
   if (B.cv_pending) return set_err(FSCLG_E_STATE, "the batch holds curves (fsclg_curve_wait)");
   if (B.st_pending) return set_err(FSCLG_E_STATE, "the batch holds site terms (fsclg_sites_wait)");
   if (B.sm_pending) return set_err(FSCLG_E_STATE, "the batch holds a sample (fsclg_sample_wait)");
+  if (B.tl_pending) return set_err(FSCLG_E_STATE, "the batch holds a tail fit (fsclg_tail_wait)");
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   B.pending = false;
@@ -5684,6 +5886,83 @@ int fsclg_sample_wait(fsclg_ctx* c, int batch, int32_t* freq_out, unsigned long 
 
 double fsclg_sample_last_ms(fsclg_ctx* c, int batch) {
   return c && batch >= 0 && batch < NBATCH ? c->batch[batch].sm_ms : 0.0;
+}
+
+// ------------------------------------------------------------ projected tail (host side)
+int fsclg_tail_submit(fsclg_ctx* c, int batch, const float* samples, size_t n_samples, const unsigned long long* offsets,
+                      const int32_t* counts, const double* x0, int n_points, int df, int min_n) {
+  if (!c || n_points < 0 || (n_points && (!offsets || !counts || !x0)) || (n_samples && !samples))
+    return set_err(FSCLG_E_ARG, "tail");
+  if (df < 2 || (df & 1)) return set_err(FSCLG_E_ARG, "tail: df must be an even integer >= 2");
+  if (batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
+  if (n_samples > (size_t)0x7fffffff) return set_err(FSCLG_E_ARG, "tail: more than 2^31 - 1 samples in one call");
+  Batch& B = c->batch[batch];
+  if (B.pending) return set_err(FSCLG_E_STATE, "batch not waited for");
+  for (int p = 0; p < n_points; p++)
+    if (counts[p] < 0 || offsets[p] > n_samples || (size_t)counts[p] > n_samples - offsets[p])
+      return set_err(FSCLG_E_ARG, "tail: a point's samples lie outside the array");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  int r;
+  if ((r = ensure_pinned(&B.p_tsamples, &B.tsamp_cap, (int)n_samples))) return r;
+  if ((r = ensure_pinned(&B.p_toff, &B.toff_cap, n_points))) return r;
+  if ((r = ensure_pinned(&B.p_tcnt, &B.tcnt_cap, n_points))) return r;
+  if ((r = ensure_pinned(&B.p_tx0, &B.tx0_cap, n_points))) return r;
+  if ((r = ensure_pinned(&B.p_tout, &B.tout_cap, n_points))) return r;
+  if (B.dtsamp_cap < std::max(n_samples, (size_t)1)) {
+    if (B.d_tsamples) hipFree(B.d_tsamples);
+    B.d_tsamples = nullptr; B.dtsamp_cap = 0;
+    const size_t k = std::max(n_samples, (size_t)1024);
+    HIPCHK(hipMalloc((void**)&B.d_tsamples, sizeof(float) * k), "hipMalloc tail samples");
+    B.dtsamp_cap = k;
+  }
+  if (n_samples) {
+    memcpy(B.p_tsamples, samples, sizeof(float) * n_samples);
+    HIPCHK(hipMemcpyAsync(B.d_tsamples, B.p_tsamples, sizeof(float) * n_samples, hipMemcpyHostToDevice, B.stream),
+           "hipMemcpyAsync tail samples");
+  }
+  if (n_points) {
+    memcpy(B.p_toff, offsets, sizeof(unsigned long long) * (size_t)n_points);
+    memcpy(B.p_tcnt, counts, sizeof(int32_t) * (size_t)n_points);
+    memcpy(B.p_tx0, x0, sizeof(double) * (size_t)n_points);
+  }
+  TailParams P;
+  P.samples = B.d_tsamples; P.off = B.p_toff; P.cnt = B.p_tcnt; P.x0 = B.p_tx0; P.out = B.p_tout;
+  P.n_points = n_points; P.h = df / 2; P.min_n = min_n;
+  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = -1; B.ivhist = nullptr; B.traced = false;
+  B.tl_n = n_points; B.tl_ms = 0.0;
+  HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
+  if (n_points) {
+    hipLaunchKernelGGL(tail_kernel, dim3((unsigned)((n_points + TAIL_WAVES - 1) / TAIL_WAVES)), dim3(64 * TAIL_WAVES), 0,
+                       B.stream, P);
+    HIPCHK(hipGetLastError(), "launch tail_kernel");
+  }
+  HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+  B.pending = true; B.tl_pending = true;
+  return FSCLG_OK;
+}
+
+int fsclg_tail_wait(fsclg_ctx* c, int batch, fsclg_tail_t* out) {
+  if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
+  Batch& B = c->batch[batch];
+  if (!B.pending || !B.tl_pending) return set_err(FSCLG_E_STATE, "no tail fit submitted on the batch");
+  if (!out && B.tl_n) return set_err(FSCLG_E_ARG, "out");  // (the batch stays submitted)
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  B.pending = false; B.tl_pending = false;
+  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  float ms = 0.f, t0 = 0.f, t1 = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
+  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
+  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
+  B.tl_ms = ms;
+  c->kernel_ms += ms;
+  c->launches++;
+  c->busy.emplace_back((double)t0, (double)t1);
+  if (B.tl_n) memcpy(out, B.p_tout, sizeof(fsclg_tail_t) * (size_t)B.tl_n);
+  return FSCLG_OK;
+}
+
+double fsclg_tail_last_ms(fsclg_ctx* c, int batch) {
+  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].tl_ms : 0.0;
 }
 
 int fsclg_interval_thresholds(double log_ad_step, int n_iv, double* thr) {

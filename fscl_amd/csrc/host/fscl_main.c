@@ -112,6 +112,8 @@ int main(int argc, char **argv) {
   char *simulate_fname = NULL, *simulate_seed = NULL, *bootstrap_fname = NULL;
   strlist_t simulate_sweep = {NULL, 0}, bootstrap_sweep = {NULL, 0};
   int simulate_rep = 0, bootstrap_reps = 100, bootstrap_window = -1, bootstrap_top = 3, need_tables;
+  char *tail_fname = NULL, *tail_df_str = NULL;
+  int tail_df = 2, tail_min_n = 20;
   scan_t *s;
   double **fsp;
   opt_t opts[] = {
@@ -169,6 +171,10 @@ int main(int argc, char **argv) {
       {0, "bootstrap-sweep", &bootstrap_sweep, T_LIST, "chr:pos:alpha of a sweep to bootstrap (may be given several times; none: the "
                                                        "--bootstrap-top scan points)"},
       {0, "bootstrap-top", &bootstrap_top, T_INT, "without --bootstrap-sweep, bootstrap this many scan points of greatest CLR (default 3)"},
+      {0, "tail-file", &tail_fname, T_STR, "after the permutation test, write every scan point's p-value projected from a noncentral "
+                                           "chi-square fit of its null CLRs (below 1/n-permute) to this file"},
+      {0, "tail-df", &tail_df_str, T_STR, "degrees of freedom of the --tail-file fit: an even integer >= 2 (default 2)"},
+      {0, "tail-min-n", &tail_min_n, T_INT, "--tail-file fits a point with at least this many positive null CLRs (default 20)"},
       {0, NULL, NULL, 0, NULL}};
 
   spline_pts = N_SPLINE_KNOTS;
@@ -294,6 +300,21 @@ int main(int argc, char **argv) {
       stop = 1;
     }
   }
+  if (tail_df_str) {
+    char *end;
+    const long v = strtol(tail_df_str, &end, 10);
+    if (end == tail_df_str || *end || v < 2 || v > 1000000 || (v & 1)) {
+      logmsg(MSG_ERROR, "Error: --tail-df must be an even integer >= 2 (not \"%s\").\n", tail_df_str);
+      stop = 1;
+    } else tail_df = (int)v;
+  }
+  if (tail_fname && n_permute <= 0) { logmsg(MSG_ERROR, "Error: --tail-file needs the permutation test (--n-permute > 0).\n"); stop = 1; }
+  if (tail_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --tail-file needs the scan (not with --no-scan).\n"); stop = 1; }
+  if (tail_fname && getenv("WORLD_SIZE") && getenv("RANK") && atoi(getenv("WORLD_SIZE")) > 1) {
+    logmsg(MSG_ERROR, "Error: --tail-file runs in one process (not with WORLD_SIZE=%s ranks).\n", getenv("WORLD_SIZE"));
+    stop = 1;
+  }
+  if (tail_fname && tail_min_n < 1) { logmsg(MSG_ERROR, "Error: --tail-min-n must be >= 1.\n"); stop = 1; }
   if (permute_seed && !(permute_mode && !strcmp(permute_mode, "throughput")))
     logmsg(MSG_WARN, "Warning: --permute-seed is used only with --permute-mode=throughput.\n");
   if (stop) {
@@ -409,6 +430,17 @@ int main(int argc, char **argv) {
     if (dont_scan) {
     } else if (ms_fname && maximum_only) output_block_maxima(output_fname, s, prepend_label);
     else scan_output(output_fname, s, maximum_only, n_permute, prepend_label);
+    if (tail_fname) {
+      /* the projected p-values, from the null CLRs the permutation test saved; no rand() draw */
+      fscl_amd_tail_t tl;
+      const int r = fscl_amd_tail_fit(s, tail_df, tail_min_n, &tl);
+      if (r != 0) logmsg(MSG_FATAL, "fscl: tail fit failed (code %d)", r);
+      if (fscl_amd_tail_output(tail_fname, s, &tl, prepend_label) != 0) logmsg(MSG_FATAL, "fscl: cannot write %s", tail_fname);
+      logmsg(MSG_STATUS, "Tail fit: df %d, %d fit, %d central, %d nofit, kernel %.3f ms (%.3f s in all); calibration over %d points "
+                         "with permute_p >= 5: median log10(p_tail / p_empirical) = %.3f\n", tail_df, tl.n_fit, tl.n_central,
+             tl.n_nofit, tl.kernel_ms, tl.wall_s, tl.n_calibration, tl.calibration);
+      fscl_amd_tail_free(&tl);
+    }
     if (bootstrap_fname) {
       /* the parametric bootstrap, last: simulate under the sweeps, rescan, summarise */
       fscl_amd_boot_t *bt;

@@ -3069,6 +3069,86 @@ int fscl_amd_bootstrap(scan_t *s, sm_ptable_t *sm, double **fsp, const fscl_amd_
   return r;
 }
 
+/* ------------------------------------------------------ projected p-values (--tail-file)
+   The device side of the noncentral chi-square fit: the points' records go to the first device
+   chunk by chunk (fsclg_tail_submit).  The host-only pieces are in tail.c. */
+static double g_tail_ms;
+double fscl_amd_tail_last_ms(void) { return g_tail_ms; }
+
+static int tail_drive(const float *const *src, const int32_t *counts, const double *x0, int n_points, int df, int min_n,
+                      fsclg_tail_t *out) {
+  const char *e = getenv("FSCL_AMD_TAIL_CAP");
+  size_t cap = e && atof(e) >= 1.0 ? (size_t)atof(e) : (size_t)1 << 24, need = 1;
+  unsigned long long *off;
+  float *buf;
+  int first = 0, r = FSCLG_OK, p;
+  g_tail_ms = 0.0;
+  if (df < 2 || (df & 1)) return FSCLG_E_ARG;
+  if (n_points <= 0) return FSCLG_OK;
+  dev_open();
+  if (cap > 0x7fffffffu) cap = 0x7fffffffu;
+  for (p = 0; p < n_points; p++) { /* (a point larger than the cap is a chunk of its own) */
+    if (counts[p] < 0) return FSCLG_E_ARG;
+    if ((size_t)counts[p] > need) need = (size_t)counts[p];
+  }
+  buf = fh_malloc(sizeof(float) * (need > cap ? need : cap), "tail samples");
+  off = fh_malloc(sizeof *off * (size_t)n_points, "tail offsets");
+  while (first < n_points && r == FSCLG_OK) {
+    const int n = fscl_amd_tail_chunk(counts, n_points, first, cap);
+    const size_t tot = fscl_amd_tail_pack(src, counts, first, n, buf, off);
+    r = fsclg_tail_submit(D.ctx[0], 0, buf, tot, off, counts + first, x0 + first, n, df, min_n);
+    if (r == FSCLG_OK) r = fsclg_tail_wait(D.ctx[0], 0, out + first);
+    g_tail_ms += fsclg_tail_last_ms(D.ctx[0], 0);
+    first += n;
+  }
+  free(buf); free(off);
+  return r;
+}
+
+int fscl_amd_tail_runs(const float *samples, size_t n_samples, const unsigned long long *offsets, const int32_t *counts,
+                       const double *x0, int n_points, int df, int min_n, fsclg_tail_t *out) {
+  const float **src;
+  int p, r;
+  if (n_points < 0 || (n_points && (!offsets || !counts || !x0 || !out)) || (n_samples && !samples)) return FSCLG_E_ARG;
+  for (p = 0; p < n_points; p++)
+    if (counts[p] < 0 || offsets[p] > n_samples || (size_t)counts[p] > n_samples - offsets[p]) return FSCLG_E_ARG;
+  src = fh_malloc(sizeof *src * (size_t)(n_points ? n_points : 1), "tail records");
+  for (p = 0; p < n_points; p++) src[p] = samples + offsets[p];
+  r = tail_drive(src, counts, x0, n_points, df, min_n, out);
+  free(src);
+  return r;
+}
+
+int fscl_amd_tail_fit(scan_t *s, int df, int min_n, fscl_amd_tail_t *out) {
+  const double t0 = fh_now();
+  const float **src;
+  int32_t *counts;
+  double *x0;
+  int i, r, n;
+  if (!s || !out) return FSCLG_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (df < 2 || (df & 1)) return FSCLG_E_ARG;
+  if (D.world > 1) return FSCLG_E_STATE;
+  n = s->n_scan_pts > 0 ? s->n_scan_pts : 0;
+  out->n = n; out->df = df; out->min_n = min_n;
+  out->pt = fh_calloc((size_t)(n ? n : 1), sizeof *out->pt, "tail rows");
+  src = fh_malloc(sizeof *src * (size_t)(n ? n : 1), "tail records");
+  counts = fh_malloc(sizeof *counts * (size_t)(n ? n : 1), "tail counts");
+  x0 = fh_malloc(sizeof *x0 * (size_t)(n ? n : 1), "tail observed");
+  for (i = 0; i < n; i++) {
+    src[i] = s->scan_pts[i].permute_clr;
+    counts[i] = fscl_amd_tail_count(s->scan_pts + i);
+    x0[i] = s->scan_pts[i].clr;
+  }
+  r = tail_drive(src, counts, x0, n, df, min_n, out->pt);
+  free(src); free(counts); free(x0);
+  out->kernel_ms = g_tail_ms;
+  if (r == FSCLG_OK) fscl_amd_tail_summary(s, out);
+  else fscl_amd_tail_free(out);
+  out->wall_s = fh_now() - t0;
+  return r;
+}
+
 /* the points fscl_amd_scan_chromosome_grid made last: fscl_amd_scan_permute_grid tests only
    those, with the same spacings, on the same data (D.key) */
 static struct {

@@ -510,6 +510,66 @@ void fscl_amd_bootstrap_output(const char *fname, const scan_t *scan_obj, const 
 void fscl_amd_sample_tables_build(const sm_ptable_t *sm_p, int n_depths, double **coef_t, double **neutral,
                                   int32_t *depth_n, int *n_iv);
 
+/* ---- projected p-values from a noncentral chi-square fit (--tail-file) ----
+   The permutation test's empirical p-value cannot go below 1 / permute_n.  Per scan point, the
+   saved null CLRs x_1 .. x_m (m = min(permute_n, FSCL_AMD_TAIL_SAVE), the used prefix of
+   permute_clr, in its own order; the record is not touched) are fitted by the model of
+   fsclg_tail_submit (include/fsclg.h): the positive ones as noncentral chi-square with df degrees
+   of freedom (even, >= 2) and a noncentrality lambda >= 0 found by maximum likelihood, the others
+   as a point mass at "no sweep found".  The projected p-value at the observed CLR is
+     p_tail = (m_pos / m) * Q(CLR; df, lambda),
+   Q the fitted upper tail, carried as log10 so that it stays finite far below 1e-308; CLR <= 0
+   gives Q = 1.  Points with fewer than min_n positive samples are not fitted (FSCLG_TAIL_NOFIT).
+   The projection assumes one noncentral chi-square per point, a df fixed by the caller, and it
+   treats twice a composite log-likelihood ratio as if it were a likelihood ratio; var_ratio --
+   the positive samples' variance over the model's 2 (df + 2 lambda) -- and the calibration figure
+   are the guards.
+
+   fscl_amd_tail_fit: every scan point of scan_obj after scan_permute or
+   fscl_amd_scan_permute_grid, into out->pt[n_scan_pts] (malloc'd; fscl_amd_tail_free), with the
+   summary filled in.  Runs on the first device, in launches of at most $FSCL_AMD_TAIL_CAP floats
+   (default 2^24).  One process only (FSCLG_E_STATE with several ranks); FSCLG_E_ARG for an odd df
+   or one below 2; otherwise a fsclg status code.  Neither scan_obj nor the permutation stream is
+   touched.
+   fscl_amd_tail_runs: the same fit of raw records -- point p holds counts[p] floats at
+   samples[offsets[p]], observed value x0[p] -- into out[n_points]; needs no scan.
+   fscl_amd_tail_last_ms: the summed kernel milliseconds of the last of either.
+   Host only: fscl_amd_tail_count (the used prefix of a point's record), fscl_amd_tail_chunk (how
+   many points from `first` go into one launch of at most cap floats; at least one),
+   fscl_amd_tail_pack (those points' samples into buf, their offsets into offsets[n]; returns the
+   floats written), fscl_amd_tail_log10p (log10 p_tail of a row, NaN when not fitted),
+   fscl_amd_tail_summary (n_fit, n_central, n_nofit and the calibration: over the fitted points
+   with permute_p >= 5 the median of log10 p_tail - log10 p_empirical, p_empirical the -o column's
+   ratio; NaN without such a point) and fscl_amd_tail_output (fname NULL: stdout; 0, or -1 if the
+   file cannot be written), one row per scan point in -o order:
+     [label TAB] chromosome TAB position TAB CLR (%1.2f) TAB permute_p TAB permute_n TAB m_pos TAB
+       lambda (%1.4f) TAB var_ratio (%1.3f) TAB -log10 p_empirical (%1.3f) TAB -log10 p_tail (%1.3f)
+       TAB flag (fit, central, nofit)
+   with NA for lambda, var_ratio and -log10 p_tail of a nofit point, and for a var_ratio that is
+   not finite. */
+#define FSCL_AMD_TAIL_SAVE 10000 /* CLR_NULL_DIST_SAVE: the null CLRs a point keeps */
+typedef struct {
+  int n;              /* scan points */
+  int df, min_n;
+  fsclg_tail_t *pt;   /* [n] */
+  int n_fit, n_central, n_nofit;
+  int n_calibration;  /* points behind the calibration figure */
+  double calibration;
+  double kernel_ms, wall_s;
+} fscl_amd_tail_t;
+int fscl_amd_tail_fit(scan_t *scan_obj, int df, int min_n, fscl_amd_tail_t *out);
+int fscl_amd_tail_runs(const float *samples, size_t n_samples, const unsigned long long *offsets, const int32_t *counts,
+                       const double *x0, int n_points, int df, int min_n, fsclg_tail_t *out);
+double fscl_amd_tail_last_ms(void);
+void fscl_amd_tail_free(fscl_amd_tail_t *t);
+int fscl_amd_tail_count(const scan_pt_t *scan_pt);
+int fscl_amd_tail_chunk(const int32_t *counts, int n_points, int first, size_t cap);
+size_t fscl_amd_tail_pack(const float *const *src, const int32_t *counts, int first, int n, float *buf,
+                          unsigned long long *offsets);
+double fscl_amd_tail_log10p(const fsclg_tail_t *row);
+void fscl_amd_tail_summary(const scan_t *scan_obj, fscl_amd_tail_t *t);
+int fscl_amd_tail_output(const char *fname, const scan_t *scan_obj, const fscl_amd_tail_t *t, const char *prepend_label);
+
 /* release the device context (tables / snps) */
 void fscl_amd_shutdown(void);
 

@@ -366,6 +366,43 @@ int fsclg_sample_submit(fsclg_ctx *c, int batch, const int32_t *depth_of_site, c
 int fsclg_sample_wait(fsclg_ctx *c, int batch, int32_t *freq_out, unsigned long long *n_degenerate);
 double fsclg_sample_last_ms(fsclg_ctx *c, int batch);
 
+/* Projected tail of a null record: a noncentral chi-square fit per point.
+   Point p holds the counts[p] floats samples[offsets[p] ..]; m = counts[p].  Its positive
+   samples -- x > 0 and finite; zero, negative, NaN and infinite ones count in m alone -- are
+   modelled as noncentral chi-square with df = 2 h degrees of freedom (df even, >= 2) and
+   noncentrality lambda >= 0, the density being the Poisson mixture
+     f(x) = sum_j e^-a a^j / j! * b^(h+j-1) e^-b / (2 (h+j-1)!),   a = lambda / 2, b = x / 2,
+   summed outward from its largest term (j (j + h - 1) ~ a b), scaled by that term.
+     m_pos < max(min_n, 1):   flag FSCLG_TAIL_NOFIT; lambda, logl, log10_q are NaN;
+     mean of the positive samples <= df:  flag FSCLG_TAIL_CENTRAL, lambda = 0;
+     otherwise FSCLG_TAIL_FIT: lambda is the root of the score 1/2 sum (f_{df+2} / f_df - 1), by
+       60 bisection steps in a bracket [0, hi], hi = max(1, 2 (mean - df)) doubled until the score
+       there is not positive.
+   logl = sum log f(x_i; df, lambda) over the positive samples; mean and variance (n - 1 in the
+   denominator; NaN below two positive samples) are theirs too.  log10_q = log10 Q(x0[p]), Q the
+   upper tail of the fitted distribution at x0, for even df the Poisson double sum
+     Q = e^(-a - b0) sum_j a^j / j! sum_{i < h + j} b0^i / i!,   b0 = x0 / 2,
+   formed in the log domain throughout (finite where e^-b0 underflows); x0 <= 0 or NaN gives 0.
+   Every sum has a fixed order (lanes stride over the samples, one wave per point): the same
+   build and input give the same bytes.  Log-factorials are lgamma calls.  A density series that
+   needs more than 4096 terms either way from its largest term (a b beyond about 1e10), or a
+   tail sum of more than 2^20 terms, gives NaN in logl or log10_q.
+   Asynchronous like fsclg_sample_submit / fsclg_sample_wait on any batch, and needs neither
+   tables nor sites; the arrays are copied.  Errors: FSCLG_E_ARG for a bad batch, n_points < 0, an
+   odd df or one below 2, a negative count, offsets + counts past n_samples; FSCLG_E_STATE for a
+   batch not waited for (submit), no tail submitted on it (wait).
+   fsclg_tail_last_ms: the kernel's own time (HIP events) of the batch's last tail call. */
+enum { FSCLG_TAIL_FIT = 0, FSCLG_TAIL_CENTRAL = 1, FSCLG_TAIL_NOFIT = 2 };
+typedef struct {
+  int32_t m, m_pos;
+  double mean, variance, lambda, logl, log10_q;
+  int32_t flag, pad;
+} fsclg_tail_t;
+int fsclg_tail_submit(fsclg_ctx *c, int batch, const float *samples, size_t n_samples, const unsigned long long *offsets,
+                      const int32_t *counts, const double *x0, int n_points, int df, int min_n);
+int fsclg_tail_wait(fsclg_ctx *c, int batch, fsclg_tail_t *out);
+double fsclg_tail_last_ms(fsclg_ctx *c, int batch);
+
 /* the exact interval thresholds the kernel uses in place of spline_interpolate's
    division (sm-spline.c:52): thr[j] = least double x with
    (int)((x - LOG_AD_MIN) / log_ad_step) >= j, for j = 1..n_iv (thr has n_iv+1 slots) */

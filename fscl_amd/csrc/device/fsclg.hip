@@ -3451,8 +3451,12 @@ struct Slot {
   int ctab_emin = 0, ctab_ne = 0;
 };
 
-// one search_maxpos launch group (fsclg_search_submit / fsclg_search_wait): its stream,
-// events, device and pinned host buffers, and the host-side dedup / ordering of its cells
+// what a batch holds between a submit and its wait
+enum BatchKind { BK_NONE, BK_SEARCH, BK_PROFILE, BK_CELLMAX, BK_CURVE, BK_SITES, BK_SAMPLE, BK_TAIL };
+
+// one call of any kind in flight (a submit / wait pair: search, profile, cell maxima, curves, site
+// terms, sample, tail fit): its stream and events, the device and pinned host buffers of each kind,
+// and a search's host-side dedup / ordering of its cells
 struct Batch {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;  // bracket the kernels
@@ -3478,7 +3482,7 @@ struct Batch {
   std::vector<fsclg_cell_t> ucells;
   std::vector<int2> epos, ucell_ep;
   int n_cells = 0, nu = 0, nlaunch = 0, slot = -1;
-  bool pending = false;
+  BatchKind holds = BK_NONE;        // the kind of the call submitted and not yet waited for
   int split_max = 1;                // fsclg_set_batch_split
   int split = 1;                    // members per cell of the current launch
   int eval_range = 0, bp_resl = 0;  // of the submitted launch (a split launch re-run unsplit)
@@ -3486,17 +3490,16 @@ struct Batch {
   unsigned int* d_xcnt = nullptr;
   size_t xacc_cap = 0;
   int xcnt_cap = 0;
-  // fsclg_cellmax_submit: the launch's chunks (pinned, read by the kernel), the chunks of each run
+  // fsclg_profile_submit (batch 0), fsclg_cellmax_submit: the launch's chunks (pinned, read by the
+  // kernel), the chunks of each run
   ProfChunk* p_cmchunks = nullptr;
   int cmchunk_cap = 0;
   std::vector<int> cm_nchunk;
-  bool cm_pending = false;
   double cm_ms = 0.0;               // kernel time of the batch's last cell-maximum launch
   // fsclg_curve_submit: the records (pinned, written by the kernel; the chunks are p_cmchunks)
   fsclg_curve_t* p_curve = nullptr;
   int curve_cap = 0;
   int cv_n = 0;                     // records of the submitted launch
-  bool cv_pending = false;
   double cv_ms = 0.0;               // kernel time of the batch's last curve launch
   // fsclg_sites_submit: requests and headers (pinned; read / written by pass 0), the tasks and the
   // staging area of one term launch (pinned; read / written by pass 1)
@@ -3506,7 +3509,6 @@ struct Batch {
   double* p_sterms = nullptr;
   int sreq_cap = 0, shdr_cap = 0, stask_cap = 0, sterm_cap = 0;
   int st_n = 0;                     // requests of the submitted call
-  bool st_pending = false;
   bool st_synced = false;           // the header launch has been waited for (a wait that only sized the buffer)
   double st_ms = 0.0;               // kernel time of the batch's last sites call
   // fsclg_sample_submit: the depth of every site and the drawn counts (pinned; read / written by the
@@ -3517,7 +3519,6 @@ struct Batch {
   fsclg_sweep_t* d_sweeps = nullptr;
   int sdepth_cap = 0, sfreq_cap = 0, ssweep_cap = 0, dsweep_cap = 0;
   int sm_n = 0;                     // sites of the submitted sample
-  bool sm_pending = false;
   double sm_ms = 0.0;               // kernel time of the batch's last sample
   // fsclg_tail_submit: the samples (pinned staging, copied to d_tsamples on the batch's stream); offsets,
   // counts, observed values and results (pinned; read / written by the kernel)
@@ -3530,7 +3531,6 @@ struct Batch {
   int tsamp_cap = 0, toff_cap = 0, tcnt_cap = 0, tx0_cap = 0, tout_cap = 0;
   size_t dtsamp_cap = 0;
   int tl_n = 0;                     // points of the submitted tail call
-  bool tl_pending = false;
   double tl_ms = 0.0;               // kernel time of the batch's last tail call
 };
 
@@ -3611,10 +3611,7 @@ struct fsclg_ctx {
   int ci_guess = 5;                       // of split cells' speculative refine walks (Params::ci_guess)
   double kernel_ms = 0.0;
   unsigned long long launches = 0;
-  ProfChunk* p_pchunks = nullptr;  // fsclg_profile: the launch's chunks (pinned, read by the kernel)
-  int pchunk_cap = 0;
-  int prof_n = 0;                  // points of the submitted profile (batch 0 pending)
-  bool prof_pending = false;
+  int prof_n = 0;                  // points of the submitted profile (batch 0 holds it)
   double prof_ms = 0.0;            // kernel time of the last profile (fsclg_profile_last_ms)
   std::vector<std::pair<double, double>> busy;  // [start, end) ms of each batch's kernels since ev_ref
 };
@@ -3734,7 +3731,6 @@ int fsclg_close(fsclg_ctx* c) {
                   c->d_stats, c->d_dfail, c->d_dband, c->d_tpos, c->d_plan_tmp, c->d_lx,
                   c->d_smp_coef, c->d_smp_prefix, c->d_smp_depth, c->d_smp_chr};
   for (void* p : ptrs) if (p) hipFree(p);
-  if (c->p_pchunks) hipHostFree(c->p_pchunks);
   for (Slot& S : c->slot) {
     for (void* p : {(void*)S.d_pr, (void*)S.d_chr_null, (void*)S.d_win_null, (void*)S.d_ctab, (void*)S.d_ctree})
       if (p) hipFree(p);
@@ -3768,7 +3764,7 @@ int fsclg_close(fsclg_ctx* c) {
 }
 
 static bool any_pending(const fsclg_ctx* c) {
-  for (const Batch& B : c->batch) if (B.pending) return true;
+  for (const Batch& B : c->batch) if (B.holds) return true;
   return false;
 }
 
@@ -4050,7 +4046,7 @@ int fsclg_slot_swap(fsclg_ctx* c, int a, int b) {
 int fsclg_search_done(fsclg_ctx* c, int batch) {
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
-  if (!B.pending || B.n_cells == 0) return 1;
+  if (!B.holds || B.n_cells == 0) return 1;
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   const hipError_t q = hipEventQuery(B.ev2);
   if (q == hipErrorNotReady) return 0;
@@ -4603,6 +4599,7 @@ static int slot_windows_impl(fsclg_ctx* c, int slot, const fsclg_cell_t* cells, 
 // prefix (a per-lane miss rate) would miss in nearly every wave, while an interval window
 // misses in whole waves (neighbouring sites have nearly equal log distance).
 constexpr int BAND_LDS_BYTES = (int)((sizeof(BandLds) + 15) / 16 * 16);
+constexpr int STAT_M = (int)((sizeof(Smem) + 15) / 16 * 16);  // the static LDS of the unsplit kernels
 static void choose_window(fsclg_ctx* c, const std::vector<double>& hist) {
   c->c_ivc0 = 0; c->c_civ = 0; c->c_crow = 0; c->c_cover = 0.0;
   c->c_ivc0_b = 0; c->c_civ_b = 0; c->c_cover_b = 0.0;
@@ -4681,6 +4678,42 @@ static void plan_cache(fsclg_ctx* c) {
 // HISTORY §R6.3); FSCLG_BAND_TH=16 turns it on
 static int band_default(const fsclg_ctx* c) { (void)c; return -1; }
 
+// Params' dynamic LDS layout: the coefficient window (intervals [ivc0, ivc0 + n_civ) of every row), the
+// thresholds, the null rows, logt3's branch-2 entries [256, lt_hi) (entry i at off_lt + 8 i), then, 16 B
+// aligned, logx_mid's table and band mode's BandLds.  The window is band mode's, the walk path's or none
+// (split launches and points); P.stride, P.lt_hi and P.lx_on are set before
+enum LdsWindow { WIN_NONE, WIN_WALK, WIN_BAND };
+static int lds_lt_end(const Params& P) { return P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0); }
+static void lds_layout(const fsclg_ctx* c, Params& P, LdsWindow w) {
+  P.ivc0 = w == WIN_BAND ? c->c_ivc0_b : (w == WIN_WALK ? c->c_ivc0 : 0);
+  P.n_civ = w == WIN_BAND ? c->c_civ_b : (w == WIN_WALK ? c->c_civ : 0);
+  P.civ_max = std::max(P.n_civ - 1, 0);
+  P.n_cache = P.n_civ * P.stride;
+  P.off_thr = P.n_cache * 32; P.off_nul = P.off_thr + (c->n_iv + 1) * 8;
+  P.off_lt = P.off_nul + (c->n_rows + 1) * 8 - 256 * 8;
+  P.off_lx = (lds_lt_end(P) + 15) & ~15;
+  P.off_bd = ((P.lx_on ? P.off_lx + LX_BYTES : lds_lt_end(P)) + 15) & ~15;
+}
+// the bytes of that layout a launch asks for
+static int lds_dyn_bytes(const Params& P) {
+  if (P.band_th >= 0 && P.n_civ > 0 && P.split <= 1) return P.off_bd + BAND_LDS_BYTES;
+  return P.lx_on ? P.off_lx + LX_BYTES : lds_lt_end(P);
+}
+
+extern "C++" {
+// a kernel's hipFuncAttributeMaxDynamicSharedMemorySize, set once per device (bit = device id; a
+// device id of 64 or more: on every call)
+template <auto K>
+static int allow_dyn_lds(int dev, int bytes) {
+  static unsigned long long attr_set = 0;
+  if (dev < 64 && (attr_set >> dev & 1ull)) return FSCLG_OK;
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, bytes),
+         "hipFuncSetAttribute");
+  if (dev < 64) attr_set |= 1ull << dev;
+  return FSCLG_OK;
+}
+}
+
 static Params make_params(fsclg_ctx* c, Batch& B, int slot, int n, int mode, int eval_range, int bp_resl) {
   const Slot& S = c->slot[slot];
   Params P;
@@ -4701,16 +4734,10 @@ static Params make_params(fsclg_ctx* c, Batch& B, int slot, int n, int mode, int
     const int band_minp = getenv("FSCLG_BAND_MINP") ? atoi(getenv("FSCLG_BAND_MINP")) : 8;
     P.band_minp = band_minp;
   }
-  if (P.band_th >= 0) { P.ivc0 = c->c_ivc0_b; P.n_civ = c->c_civ_b; }
-  else { P.ivc0 = c->c_ivc0; P.n_civ = c->c_civ; }
-  P.civ_max = std::max(P.n_civ - 1, 0);
-  P.n_cache = P.n_civ * P.stride;
-  P.off_thr = P.n_cache * 32; P.off_nul = P.off_thr + (c->n_iv + 1) * 8;
-  P.off_lt = P.off_nul + (c->n_rows + 1) * 8 - 256 * 8; P.lt_hi = c->lt_hi;  // entry i at off_lt + 8 i
+  P.lt_hi = c->lt_hi;
   P.lt_span = c->lt_hi > 256 ? ((uint32_t)c->lt_hi << 16) - 0x1000000u : 0u;  // lt_hi <= 32768
   P.lx = c->d_lx; P.lx_on = FSCLG_LOG_CALC >= 2 ? c->lx_on : 0;  // FSCLG_LOG_CALC=1: set for split launches
-  P.off_lx = (P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0) + 15) & ~15;
-  P.off_bd = ((P.lx_on ? P.off_lx + LX_BYTES : P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0)) + 15) & ~15;
+  lds_layout(c, P, P.band_th >= 0 ? WIN_BAND : WIN_WALK);
   P.chr_start = c->d_chr_start; P.chr_n = c->d_chr_n; P.chr_null = S.d_chr_null; P.win_null = S.d_win_null;
   P.la_coarse = c->d_la_coarse; P.la_refine = c->d_la_refine; P.n_refine = c->d_n_refine;
   P.dfail = c->d_dfail;
@@ -4775,23 +4802,14 @@ static int launch_blocks(hipStream_t stream, const Params& P, int n) {
 }
 static int launch_blocks_impl(hipStream_t stream, const Params& P, int n) {
   const int grid = n;
-  const int dyn = (P.band_th >= 0 && P.n_civ > 0 && P.split <= 1)
-                      ? P.off_bd + BAND_LDS_BYTES
-                      : (P.lx_on ? P.off_lx + LX_BYTES : P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0));
-  const int stat_m = (int)((sizeof(Smem) + 15) / 16 * 16), stat_s = (int)((sizeof(SmemSplit) + 15) / 16 * 16);
-  if ((P.split > 1 ? stat_s : stat_m) + dyn <= LDS_WG) {
-    static unsigned long long attr_set = 0;  // per device (bit = device id)
-    int dev = 0;
+  const int dyn = lds_dyn_bytes(P);
+  const int stat_s = (int)((sizeof(SmemSplit) + 15) / 16 * 16);
+  if ((P.split > 1 ? stat_s : STAT_M) + dyn <= LDS_WG) {
+    int dev = 0, r;
     HIPCHK(hipGetDevice(&dev), "hipGetDevice");
-    if (dev >= 64 || !(attr_set >> dev & 1ull)) {
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&search_maxpos_kernel<true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WG - stat_m), "hipFuncSetAttribute");
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&search_maxpos_kernel<true, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WG - stat_m), "hipFuncSetAttribute");
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&search_maxpos_split_kernel<true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WG - stat_s), "hipFuncSetAttribute");
-      if (dev < 64) attr_set |= 1ull << dev;
-    }
+    if ((r = allow_dyn_lds<&search_maxpos_kernel<true>>(dev, LDS_WG - STAT_M))) return r;
+    if ((r = allow_dyn_lds<&search_maxpos_kernel<true, true>>(dev, LDS_WG - STAT_M))) return r;
+    if ((r = allow_dyn_lds<&search_maxpos_split_kernel<true>>(dev, LDS_WG - stat_s))) return r;
     if (P.split > 1) hipLaunchKernelGGL((search_maxpos_split_kernel<true>), dim3(grid), dim3(WG), dyn, stream, P);
     else if (P.band_th >= 0 && P.n_civ > 0) hipLaunchKernelGGL((search_maxpos_kernel<true, true>), dim3(grid), dim3(WG), dyn, stream, P);
     else hipLaunchKernelGGL((search_maxpos_kernel<true>), dim3(grid), dim3(WG), dyn, stream, P);
@@ -4825,6 +4843,27 @@ static int ensure_pinned(T** h, int* cap, int n) {
 }
 }
 
+// the time of the n launches bracketed by the batch's events (both reached), added to the context's
+// totals; *ms: that time
+static int batch_time(fsclg_ctx* c, const Batch& B, int n, double* ms = nullptr) {
+  float t = 0.f, t0 = 0.f, t1 = 0.f;
+  HIPCHK(hipEventElapsedTime(&t, B.ev0, B.ev1), "hipEventElapsedTime");
+  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
+  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
+  if (ms) *ms = t;
+  c->kernel_ms += t;
+  c->launches += (unsigned long long)n;
+  c->busy.emplace_back((double)t0, (double)t1);
+  return FSCLG_OK;
+}
+
+// the flags of a call's points (their OR) as its return code
+static int flags_err(int flags, const char* timeout_msg = "device flag") {
+  if (!flags) return FSCLG_OK;
+  return set_err(flags & PF_UNSUPPORTED ? FSCLG_E_UNSUPPORTED : FSCLG_E_KERNEL,
+                 flags & PF_SPLIT_TIMEOUT ? timeout_msg : "device flag");
+}
+
 // the key of a cell's remembered cost (cell_cost), used only to order a launch longest first:
 // distinct below 2^29 bp and 64 chromosomes, and a collision past that misorders, never miscomputes
 static unsigned long long cell_key(const fsclg_cell_t& x) {
@@ -4847,7 +4886,7 @@ static int search_submit_impl(fsclg_ctx* c, int batch, int slot, const fsclg_cel
   if (batch < 0 || batch >= NBATCH || slot < 0 || slot >= NSLOT) return set_err(FSCLG_E_ARG, "batch/slot");
   if (!c->d_pr0 || !c->d_coef || !c->d_la_coarse) return set_err(FSCLG_E_STATE, "tables/snps/alpha grid not set");
   Batch& B = c->batch[batch];
-  if (B.pending) return set_err(FSCLG_E_STATE, "batch not waited for");
+  if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
   // host-side shape checks before any launch
   if (eval_range < 0 || bp_resl < 0) return set_err(FSCLG_E_ARG, "eval_range/bp_resl");
   for (int i = 0; i < n_cells; i++) {
@@ -4860,7 +4899,7 @@ static int search_submit_impl(fsclg_ctx* c, int batch, int slot, const fsclg_cel
   B.n_cells = n_cells; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
   B.eval_range = eval_range; B.bp_resl = bp_resl;
   if (n_cells == 0) {
-    B.pending = true;
+    B.holds = BK_SEARCH;
     c->slot[slot].users++;
     return FSCLG_OK;
   }
@@ -5047,11 +5086,8 @@ static int search_submit_impl(fsclg_ctx* c, int batch, int slot, const fsclg_cel
     P.spec_refine = spec_refine_on();
     // latency: no LDS coefficient windows (their loads, repeated by every member for every
     // phase, cost more than the global gathers of a lightly loaded device)
-    P.ivc0 = 0; P.n_civ = 0; P.civ_max = 0; P.n_cache = 0;
-    P.off_thr = 0; P.off_nul = (c->n_iv + 1) * 8;
-    P.off_lt = P.off_nul + (c->n_rows + 1) * 8 - 256 * 8;
-    P.off_lx = (P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0) + 15) & ~15;
     P.lx_on = FSCLG_LOG_CALC >= 1 ? c->lx_on : 0;
+    lds_layout(c, P, WIN_NONE);
   }
   if ((r = launch_blocks(B.stream, P, G > 1 ? (nl + 7) / 8 * 8 * G : nl))) return r;
   HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
@@ -5060,7 +5096,7 @@ static int search_submit_impl(fsclg_ctx* c, int batch, int slot, const fsclg_cel
   B.trace_n = nl;
   B.nu = nl;
   B.nlaunch = use_ep ? 2 : 1;
-  B.pending = true;
+  B.holds = BK_SEARCH;
   c->slot[slot].users++;
   return FSCLG_OK;
 }
@@ -5068,27 +5104,22 @@ static int search_submit_impl(fsclg_ctx* c, int batch, int slot, const fsclg_cel
 int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
-  if (!B.pending) return set_err(FSCLG_E_STATE, "batch not submitted");
-  if (B.cm_pending) return set_err(FSCLG_E_STATE, "the batch holds cell maxima (fsclg_cellmax_wait)");
-  if (B.cv_pending) return set_err(FSCLG_E_STATE, "the batch holds curves (fsclg_curve_wait)");
-  if (B.st_pending) return set_err(FSCLG_E_STATE, "the batch holds site terms (fsclg_sites_wait)");
-  if (B.sm_pending) return set_err(FSCLG_E_STATE, "the batch holds a sample (fsclg_sample_wait)");
-  if (B.tl_pending) return set_err(FSCLG_E_STATE, "the batch holds a tail fit (fsclg_tail_wait)");
+  static const char* const other[] = {  // by BatchKind
+      "batch not submitted", nullptr, "the batch holds a profile (fsclg_profile_wait)",
+      "the batch holds cell maxima (fsclg_cellmax_wait)", "the batch holds curves (fsclg_curve_wait)",
+      "the batch holds site terms (fsclg_sites_wait)", "the batch holds a sample (fsclg_sample_wait)",
+      "the batch holds a tail fit (fsclg_tail_wait)"};
+  if (B.holds != BK_SEARCH) return set_err(FSCLG_E_STATE, other[B.holds]);
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.pending = false;
+  B.holds = BK_NONE;
   c->slot[B.slot].users--;
   if (B.n_cells == 0) return FSCLG_OK;
   const int nu = B.nu;
   // the batch's own completion (its stream may hold later batches): the D2H after ev1
   HIPCHK(hipEventSynchronize(B.ev2), "hipEventSynchronize");
-  float ms = 0.f, t0 = 0.f, t1 = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
-  c->kernel_ms += ms;
-  c->launches += (unsigned long long)B.nlaunch;
-  c->busy.emplace_back((double)t0, (double)t1);
+  int r;
+  if ((r = batch_time(c, B, B.nlaunch))) return r;
   if (B.ivhist) {  // re-plan the LDS window from the measured histogram
     const int nkey = c->n_coarse + 2;
     std::vector<unsigned long long> hk((size_t)nkey * c->n_iv), h(c->n_iv, 0);
@@ -5139,17 +5170,15 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
     const int saved = B.split_max;
     c->n_split_retry++;
     B.split_max = 1;
-    int r = fsclg_search_submit(c, batch, B.slot, cells.data(), B.n_cells, B.eval_range, B.bp_resl);
+    r = fsclg_search_submit(c, batch, B.slot, cells.data(), B.n_cells, B.eval_range, B.bp_resl);
     B.split_max = saved;
     if (r) return r;
     return fsclg_search_wait(c, batch, out);
   }
   note_alphas(c, out, B.n_cells);
   for (int i = 0; i < B.n_cells; i++)
-    if (out[i].flags)
-      return set_err(out[i].flags & PF_UNSUPPORTED ? FSCLG_E_UNSUPPORTED : FSCLG_E_KERNEL,
-                     out[i].flags & PF_SPLIT_TIMEOUT ? "device flag: a split cell's members were not resident together"
-                                                     : "device flag");
+    if (out[i].flags)  // the first flagged point's
+      return flags_err(out[i].flags, "device flag: a split cell's members were not resident together");
   return FSCLG_OK;
 }
 
@@ -5174,7 +5203,7 @@ int fsclg_search_points(fsclg_ctx* c, fsclg_point_t* pts, int n_pts) {
   if (!c->d_pr0 || !c->d_coef || !c->d_la_coarse) return set_err(FSCLG_E_STATE, "tables/snps/alpha grid not set");
   if (n_pts == 0) return FSCLG_OK;
   Batch& B = c->batch[0];
-  if (B.pending) return set_err(FSCLG_E_STATE, "batch 0 not waited for");
+  if (B.holds) return set_err(FSCLG_E_STATE, "batch 0 not waited for");
   for (int i = 0; i < n_pts; i++) {
     const fsclg_point_t& p = pts[i];
     if (p.window_start < 0 || p.window_end >= c->n_snps || p.window_start > p.window_end ||
@@ -5207,10 +5236,7 @@ int fsclg_search_points(fsclg_ctx* c, fsclg_point_t* pts, int n_pts) {
     HIPCHK(hipMemsetAsync(B.d_xcnt, 0, sizeof(unsigned int) * nl, B.stream), "hipMemsetAsync");
     P.split = G; P.xacc = B.d_xacc; P.xcnt = B.d_xcnt;
     P.spec_refine = spec_refine_on();
-    P.ivc0 = 0; P.n_civ = 0; P.civ_max = 0; P.n_cache = 0;  // as a split batch: no LDS coefficient windows
-    P.off_thr = 0; P.off_nul = (c->n_iv + 1) * 8;
-    P.off_lt = P.off_nul + (c->n_rows + 1) * 8 - 256 * 8;
-    P.off_lx = (P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0) + 15) & ~15;
+    lds_layout(c, P, WIN_NONE);  // as a split batch: no LDS coefficient windows
   }
   HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
   if ((r = launch_blocks(B.stream, P, G > 1 ? (n_pts + 7) / 8 * 8 * G : n_pts))) return r;
@@ -5220,17 +5246,9 @@ int fsclg_search_points(fsclg_ctx* c, fsclg_point_t* pts, int n_pts) {
   note_alphas(c, pts, n_pts);
   for (int i = 0; i < n_pts; i++)
     if (pts[i].flags & (PF_UNSUPPORTED | PF_SPLIT_TIMEOUT))
-      return set_err(pts[i].flags & PF_UNSUPPORTED ? FSCLG_E_UNSUPPORTED : FSCLG_E_KERNEL,
-                     pts[i].flags & PF_SPLIT_TIMEOUT ? "device flag: a point's members were not resident together"
-                                                     : "device flag");
-  float ms = 0.f, t0 = 0.f, t1 = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
-  c->kernel_ms += ms;
-  c->launches++;
-  c->busy.emplace_back((double)t0, (double)t1);
-  return FSCLG_OK;
+      return flags_err(pts[i].flags & (PF_UNSUPPORTED | PF_SPLIT_TIMEOUT),
+                       "device flag: a point's members were not resident together");
+  return batch_time(c, B, 1);
 }
 
 // Chunk length of the profile kernel: positions per workgroup, i.e. per LDS prologue
@@ -5246,13 +5264,10 @@ int fsclg_profile_chunk(void) {
   return v < 1 ? 1 : (v > 4096 ? 4096 : v);
 }
 
-int fsclg_profile_submit(fsclg_ctx* c, const fsclg_run_t* runs, int n_runs, int eval_range) {
-  if (!c || (!runs && n_runs) || n_runs < 0 || eval_range < 0) return set_err(FSCLG_E_ARG, "runs");
-  if (!c->d_pr0 || !c->d_coef || !c->d_la_coarse) return set_err(FSCLG_E_STATE, "tables/snps/alpha grid not set");
-  Batch& B = c->batch[0];
-  if (B.pending) return set_err(FSCLG_E_STATE, "batch 0 not waited for");
-  const int CH = fsclg_profile_chunk();
-  long long total = 0, nchunk = 0;
+// the checks of a run-chunk call's runs; *total: their positions, *nchunk: their chunks of CH positions
+static int validate_runs(const fsclg_ctx* c, const fsclg_run_t* runs, int n_runs, int eval_range, int CH,
+                         long long* total, long long* nchunk) {
+  *total = 0; *nchunk = 0;
   for (int i = 0; i < n_runs; i++) {
     const fsclg_run_t& r = runs[i];
     if (r.step < 1 || r.count < 0) return set_err(FSCLG_E_ARG, "run step/count");
@@ -5262,61 +5277,103 @@ int fsclg_profile_submit(fsclg_ctx* c, const fsclg_run_t* runs, int n_runs, int 
       return set_err(FSCLG_E_ARG, "run position overflow");
     const long long nwin = std::min((long long)c->h_chr_n[r.chr], 2ll * eval_range + 1);
     if (nwin / SEG_SPLIT + 4 > (long long)MAXSEG_W) return set_err(FSCLG_E_UNSUPPORTED, "window above the segment table");
-    total += r.count;
-    nchunk += (r.count + CH - 1) / CH;
+    *total += r.count;
+    *nchunk += (r.count + CH - 1) / CH;
   }
+  return FSCLG_OK;
+}
+
+// the window null sums of every window the covering cells touch, for the slot's rows (a slot another
+// batch already runs on: only what is still missing)
+static int cover_windows(fsclg_ctx* c, Batch& B, int slot, const std::vector<fsclg_cell_t>& cover, int eval_range) {
+  if (c->slot[slot].users == 0) return fsclg_slot_windows(c, slot, cover.data(), (int)cover.size(), eval_range);
+  return ensure_windows(c, slot, eval_range, cover.data(), (int)cover.size(), &B.wr_memo);
+}
+
+// One launch of a run-chunk kernel (profile_body's wrappers) on the batch's stream, for the slot's rows:
+// the runs' window null sums (one covering cell per run), their chunks of CH positions in p_cmchunks
+// (out0: the chunk's first position among all, or by_chunk: its index), then the kernel between ev0 and
+// ev1, on the walk-window path (band mode has its own kernel) with the tables in LDS where they fit
+enum RunKernel { RUN_PROFILE, RUN_CELLMAX, RUN_CURVE };
+extern "C++" {
+template <bool LDS>
+static int launch_run_kernel(fsclg_ctx* c, Batch& B, RunKernel k, const Params& P, int dyn) {
+  const dim3 grid(P.n_cells), wg(WG);
+  const ProfChunk* ch = B.p_cmchunks;
+  int r = FSCLG_OK;
+  switch (k) {
+    case RUN_PROFILE:
+      if (LDS && (r = allow_dyn_lds<&profile_kernel<true>>(c->device, LDS_WG - STAT_M))) return r;
+      hipLaunchKernelGGL((profile_kernel<LDS>), grid, wg, dyn, B.stream, P, ch);
+      break;
+    case RUN_CELLMAX:
+      if (LDS && (r = allow_dyn_lds<&cellmax_kernel<true>>(c->device, LDS_WG - STAT_M))) return r;
+      hipLaunchKernelGGL((cellmax_kernel<LDS>), grid, wg, dyn, B.stream, P, ch);
+      break;
+    case RUN_CURVE:
+      if (LDS && (r = allow_dyn_lds<&curve_kernel<true>>(c->device, LDS_WG - STAT_M))) return r;
+      hipLaunchKernelGGL((curve_kernel<LDS>), grid, wg, dyn, B.stream, P, ch, B.p_curve, c->d_stats + 24);
+      break;
+  }
+  return FSCLG_OK;
+}
+}
+static int launch_runs(fsclg_ctx* c, Batch& B, int slot, const fsclg_run_t* runs, int n_runs, int eval_range, int CH,
+                       int nchunk, RunKernel k, bool by_chunk) {
+  int r;
+  std::vector<fsclg_cell_t> cover;
+  for (int i = 0; i < n_runs; i++)
+    if (runs[i].count > 0)
+      cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos, runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
+  if ((r = cover_windows(c, B, slot, cover, eval_range))) return r;
+  if ((r = ensure_pinned(&B.p_cmchunks, &B.cmchunk_cap, nchunk))) return r;
+  int nc = 0, o = 0;
+  for (int i = 0; i < n_runs; i++)
+    for (int j = 0; j < runs[i].count; j += CH) {
+      const int cnt = std::min(CH, runs[i].count - j);
+      B.p_cmchunks[nc] = ProfChunk{runs[i].chr, runs[i].start_pos + j * runs[i].step, runs[i].step, cnt, by_chunk ? nc : o,
+                                   {0, 0, 0}};
+      nc++;
+      o += cnt;
+    }
+  HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
+  Params P = make_params(c, B, slot, nc, 3, eval_range, 0);
+  P.band_th = -1;
+  lds_layout(c, P, WIN_WALK);
+  P.ctrace = nullptr;
+  const int dyn = lds_dyn_bytes(P);
+  HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
+  // (tables too large for the LDS copies: every coefficient from the global table, as the cell path)
+  if ((r = STAT_M + dyn <= LDS_WG ? launch_run_kernel<true>(c, B, k, P, dyn) : launch_run_kernel<false>(c, B, k, P, 0)))
+    return r;
+  static const char* const what[] = {"launch profile_kernel", "launch cellmax_kernel", "launch curve_kernel"};
+  HIPCHK(hipGetLastError(), what[k]);
+  HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+  return FSCLG_OK;
+}
+
+int fsclg_profile_submit(fsclg_ctx* c, const fsclg_run_t* runs, int n_runs, int eval_range) {
+  if (!c || (!runs && n_runs) || n_runs < 0 || eval_range < 0) return set_err(FSCLG_E_ARG, "runs");
+  if (!c->d_pr0 || !c->d_coef || !c->d_la_coarse) return set_err(FSCLG_E_STATE, "tables/snps/alpha grid not set");
+  Batch& B = c->batch[0];
+  if (B.holds) return set_err(FSCLG_E_STATE, "batch 0 not waited for");
+  const int CH = fsclg_profile_chunk();
+  long long total, nchunk;
+  int r;
+  if ((r = validate_runs(c, runs, n_runs, eval_range, CH, &total, &nchunk))) return r;
   if (total > 0x7FFFFFFFll / (long long)sizeof(fsclg_point_t)) return set_err(FSCLG_E_ARG, "too many profile points");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   c->prof_n = (int)total; c->prof_ms = 0.0;
   B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = 0; B.ivhist = nullptr; B.traced = false;
-  int r;
   if (total > 0) {
     // the profile is of the data as uploaded: the unpermuted rows into slot 0 (its whole-chromosome
-    // null sums are the caller's, fsclg_set_chr_null, as for fsclg_search_maxpos)
+    // null sums are the caller's, fsclg_set_chr_null, as for fsclg_search_maxpos); no batch runs on
+    // the slot then, so its window null sums are made by fsclg_slot_windows
     if ((r = fsclg_slot_set_rows(c, 0, nullptr, nullptr))) return r;
-    {  // the window null sums of every window the runs' positions touch: one covering cell per run
-      std::vector<fsclg_cell_t> cover;
-      for (int i = 0; i < n_runs; i++)
-        if (runs[i].count > 0)
-          cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos,
-                                       runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
-      if ((r = fsclg_slot_windows(c, 0, cover.data(), (int)cover.size(), eval_range))) return r;
-    }
     if ((r = ensure_io(B, (int)total))) return r;
-    if ((r = ensure_pinned(&c->p_pchunks, &c->pchunk_cap, (int)nchunk))) return r;
-    int nc = 0, o = 0;
-    for (int i = 0; i < n_runs; i++)
-      for (int k = 0; k < runs[i].count; k += CH) {
-        const int cnt = std::min(CH, runs[i].count - k);
-        c->p_pchunks[nc++] = ProfChunk{runs[i].chr, runs[i].start_pos + k * runs[i].step, runs[i].step, cnt, o, {0, 0, 0}};
-        o += cnt;
-      }
-    HIPCHK(hipStreamWaitEvent(B.stream, c->slot[0].ready, 0), "hipStreamWaitEvent");
-    Params P = make_params(c, B, 0, nc, 3, eval_range, 0);
-    P.band_th = -1; P.ivc0 = c->c_ivc0; P.n_civ = c->c_civ;  // the walk-window path (band mode has its own kernel)
-    P.civ_max = std::max(P.n_civ - 1, 0); P.n_cache = P.n_civ * P.stride;
-    P.off_thr = P.n_cache * 32; P.off_nul = P.off_thr + (c->n_iv + 1) * 8;
-    P.off_lt = P.off_nul + (c->n_rows + 1) * 8 - 256 * 8;
-    P.off_lx = (P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0) + 15) & ~15;
-    P.ctrace = nullptr;
-    const int dyn = P.lx_on ? P.off_lx + LX_BYTES : P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0);
-    const int stat_m = (int)((sizeof(Smem) + 15) / 16 * 16);
-    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
-    if (stat_m + dyn <= LDS_WG) {
-      static unsigned long long attr_set = 0;  // per device (bit = device id)
-      if (c->device >= 64 || !(attr_set >> c->device & 1ull)) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&profile_kernel<true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WG - stat_m), "hipFuncSetAttribute");
-        if (c->device < 64) attr_set |= 1ull << c->device;
-      }
-      hipLaunchKernelGGL((profile_kernel<true>), dim3(nc), dim3(WG), dyn, B.stream, P, (const ProfChunk*)c->p_pchunks);
-    } else {  // tables too large for the LDS copies: every coefficient from the global table, as the cell path
-      hipLaunchKernelGGL((profile_kernel<false>), dim3(nc), dim3(WG), 0, B.stream, P, (const ProfChunk*)c->p_pchunks);
-    }
-    HIPCHK(hipGetLastError(), "launch profile_kernel");
-    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+    if ((r = launch_runs(c, B, 0, runs, n_runs, eval_range, CH, (int)nchunk, RUN_PROFILE, false))) return r;
   }
-  B.pending = true; c->prof_pending = true;
+  B.holds = BK_PROFILE;
   c->slot[0].users++;
   return FSCLG_OK;
 }
@@ -5324,27 +5381,20 @@ int fsclg_profile_submit(fsclg_ctx* c, const fsclg_run_t* runs, int n_runs, int 
 int fsclg_profile_wait(fsclg_ctx* c, fsclg_point_t* out) {
   if (!c) return set_err(FSCLG_E_ARG, "context");
   Batch& B = c->batch[0];
-  if (!B.pending || !c->prof_pending) return set_err(FSCLG_E_STATE, "no profile submitted");
+  if (B.holds != BK_PROFILE) return set_err(FSCLG_E_STATE, "no profile submitted");
   if (!out && c->prof_n) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.pending = false; c->prof_pending = false;
+  B.holds = BK_NONE;
   c->slot[0].users--;
   const int n = c->prof_n;
   if (n == 0) return FSCLG_OK;
   HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
   memcpy(out, B.p_out, sizeof(fsclg_point_t) * (size_t)n);
-  float ms = 0.f, t0 = 0.f, t1 = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
-  c->prof_ms = ms;
-  c->kernel_ms += ms;
-  c->launches++;
-  c->busy.emplace_back((double)t0, (double)t1);
+  int r;
+  if ((r = batch_time(c, B, 1, &c->prof_ms))) return r;
   note_alphas(c, out, n);
   for (int i = 0; i < n; i++)
-    if (out[i].flags)
-      return set_err(out[i].flags & PF_UNSUPPORTED ? FSCLG_E_UNSUPPORTED : FSCLG_E_KERNEL, "device flag");
+    if (out[i].flags) return flags_err(out[i].flags);  // the first flagged point's
   return FSCLG_OK;
 }
 
@@ -5368,76 +5418,22 @@ int fsclg_cellmax_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* r
   if (batch < 0 || batch >= NBATCH || slot < 0 || slot >= NSLOT) return set_err(FSCLG_E_ARG, "batch/slot");
   if (!c->d_pr0 || !c->d_coef || !c->d_la_coarse) return set_err(FSCLG_E_STATE, "tables/snps/alpha grid not set");
   Batch& B = c->batch[batch];
-  if (B.pending) return set_err(FSCLG_E_STATE, "batch not waited for");
+  if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
   const int CH = fsclg_profile_chunk();
-  long long nchunk = 0;
-  for (int i = 0; i < n_runs; i++) {
-    const fsclg_run_t& r = runs[i];
-    if (r.step < 1 || r.count < 0) return set_err(FSCLG_E_ARG, "run step/count");
-    if (r.chr < 0 || r.chr >= c->n_chr) return set_err(FSCLG_E_ARG, "run chromosome");
-    // (the last position + 64: init_scan_result's de-collision may move a point past it)
-    if (r.count > 0 && (long long)r.start_pos + (long long)(r.count - 1) * r.step > 0x7FFFFFFFll - 64)
-      return set_err(FSCLG_E_ARG, "run position overflow");
-    const long long nwin = std::min((long long)c->h_chr_n[r.chr], 2ll * eval_range + 1);
-    if (nwin / SEG_SPLIT + 4 > (long long)MAXSEG_W) return set_err(FSCLG_E_UNSUPPORTED, "window above the segment table");
-    nchunk += (r.count + CH - 1) / CH;
-  }
+  long long total, nchunk;
+  int r;
+  if ((r = validate_runs(c, runs, n_runs, eval_range, CH, &total, &nchunk))) return r;
   if (nchunk > 0x7FFFFFFFll / (long long)sizeof(fsclg_point_t)) return set_err(FSCLG_E_ARG, "too many chunks");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.n_cells = n_runs; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
+  B.n_cells = n_runs; B.nu = (int)nchunk; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
   B.eval_range = eval_range; B.bp_resl = 0; B.cm_ms = 0.0;
   B.cm_nchunk.resize((size_t)n_runs);
-  int r;
+  for (int i = 0; i < n_runs; i++) B.cm_nchunk[i] = (runs[i].count + CH - 1) / CH;
   if (nchunk > 0) {
-    {  // the window null sums of every window the runs' positions touch, for the slot's rows: one
-       // covering cell per run (a slot another batch already runs on: only what is still missing)
-      std::vector<fsclg_cell_t> cover;
-      for (int i = 0; i < n_runs; i++)
-        if (runs[i].count > 0)
-          cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos,
-                                       runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
-      if (c->slot[slot].users == 0) r = fsclg_slot_windows(c, slot, cover.data(), (int)cover.size(), eval_range);
-      else r = ensure_windows(c, slot, eval_range, cover.data(), (int)cover.size(), &B.wr_memo);
-      if (r) return r;
-    }
     if ((r = ensure_io(B, (int)nchunk))) return r;
-    if ((r = ensure_pinned(&B.p_cmchunks, &B.cmchunk_cap, (int)nchunk))) return r;
+    if ((r = launch_runs(c, B, slot, runs, n_runs, eval_range, CH, (int)nchunk, RUN_CELLMAX, true))) return r;
   }
-  int nc = 0;
-  for (int i = 0; i < n_runs; i++) {
-    B.cm_nchunk[i] = (runs[i].count + CH - 1) / CH;
-    for (int k = 0; k < runs[i].count; k += CH, nc++)
-      B.p_cmchunks[nc] = ProfChunk{runs[i].chr, runs[i].start_pos + k * runs[i].step, runs[i].step,
-                                   std::min(CH, runs[i].count - k), nc, {0, 0, 0}};
-  }
-  if (nc > 0) {
-    HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
-    Params P = make_params(c, B, slot, nc, 3, eval_range, 0);
-    P.band_th = -1; P.ivc0 = c->c_ivc0; P.n_civ = c->c_civ;  // the walk-window path, as the profile kernel
-    P.civ_max = std::max(P.n_civ - 1, 0); P.n_cache = P.n_civ * P.stride;
-    P.off_thr = P.n_cache * 32; P.off_nul = P.off_thr + (c->n_iv + 1) * 8;
-    P.off_lt = P.off_nul + (c->n_rows + 1) * 8 - 256 * 8;
-    P.off_lx = (P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0) + 15) & ~15;
-    P.ctrace = nullptr;
-    const int dyn = P.lx_on ? P.off_lx + LX_BYTES : P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0);
-    const int stat_m = (int)((sizeof(Smem) + 15) / 16 * 16);
-    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
-    if (stat_m + dyn <= LDS_WG) {
-      static unsigned long long attr_set = 0;  // per device (bit = device id)
-      if (c->device >= 64 || !(attr_set >> c->device & 1ull)) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cellmax_kernel<true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WG - stat_m), "hipFuncSetAttribute");
-        if (c->device < 64) attr_set |= 1ull << c->device;
-      }
-      hipLaunchKernelGGL((cellmax_kernel<true>), dim3(nc), dim3(WG), dyn, B.stream, P, (const ProfChunk*)B.p_cmchunks);
-    } else {  // tables too large for the LDS copies: every coefficient from the global table
-      hipLaunchKernelGGL((cellmax_kernel<false>), dim3(nc), dim3(WG), 0, B.stream, P, (const ProfChunk*)B.p_cmchunks);
-    }
-    HIPCHK(hipGetLastError(), "launch cellmax_kernel");
-    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
-  }
-  B.nu = nc;
-  B.pending = true; B.cm_pending = true;
+  B.holds = BK_CELLMAX;
   c->slot[slot].users++;
   return FSCLG_OK;
 }
@@ -5445,22 +5441,16 @@ int fsclg_cellmax_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* r
 int fsclg_cellmax_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
-  if (!B.pending || !B.cm_pending) return set_err(FSCLG_E_STATE, "no cell maxima submitted on the batch");
+  if (B.holds != BK_CELLMAX) return set_err(FSCLG_E_STATE, "no cell maxima submitted on the batch");
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.pending = false; B.cm_pending = false;
+  B.holds = BK_NONE;
   c->slot[B.slot].users--;
   const int n_runs = B.n_cells, nc = B.nu;
   if (nc > 0) {
+    int r;
     HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
-    float ms = 0.f, t0 = 0.f, t1 = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
-    B.cm_ms = ms;
-    c->kernel_ms += ms;
-    c->launches++;
-    c->busy.emplace_back((double)t0, (double)t1);
+    if ((r = batch_time(c, B, 1, &B.cm_ms))) return r;
   }
   // a run's chunk maxima in chunk order, strict >: the first position of the greatest clr
   int flags = 0;
@@ -5481,8 +5471,7 @@ int fsclg_cellmax_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
     flags |= fl;
   }
   if (n_runs) note_alphas(c, out, n_runs);
-  if (flags) return set_err(flags & PF_UNSUPPORTED ? FSCLG_E_UNSUPPORTED : FSCLG_E_KERNEL, "device flag");
-  return FSCLG_OK;
+  return flags_err(flags);
 }
 
 double fsclg_cellmax_last_ms(fsclg_ctx* c, int batch) {
@@ -5497,79 +5486,21 @@ int fsclg_curve_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* run
   if (!c->d_pr0 || !c->d_coef || !c->d_la_coarse) return set_err(FSCLG_E_STATE, "tables/snps/alpha grid not set");
   if (c->n_coarse > NCOARSE_REF) return set_err(FSCLG_E_ARG, "alpha grid above the curve record");
   Batch& B = c->batch[batch];
-  if (B.pending) return set_err(FSCLG_E_STATE, "batch not waited for");
+  if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
   const int CH = fsclg_profile_chunk();
-  long long total = 0, nchunk = 0;
-  for (int i = 0; i < n_runs; i++) {
-    const fsclg_run_t& r = runs[i];
-    if (r.step < 1 || r.count < 0) return set_err(FSCLG_E_ARG, "run step/count");
-    if (r.chr < 0 || r.chr >= c->n_chr) return set_err(FSCLG_E_ARG, "run chromosome");
-    // (the last position + 64: init_scan_result's de-collision may move a point past it)
-    if (r.count > 0 && (long long)r.start_pos + (long long)(r.count - 1) * r.step > 0x7FFFFFFFll - 64)
-      return set_err(FSCLG_E_ARG, "run position overflow");
-    const long long nwin = std::min((long long)c->h_chr_n[r.chr], 2ll * eval_range + 1);
-    if (nwin / SEG_SPLIT + 4 > (long long)MAXSEG_W) return set_err(FSCLG_E_UNSUPPORTED, "window above the segment table");
-    total += r.count;
-    nchunk += (r.count + CH - 1) / CH;
-  }
+  long long total, nchunk;
+  int r;
+  if ((r = validate_runs(c, runs, n_runs, eval_range, CH, &total, &nchunk))) return r;
   if (total > 0x7FFFFFFFll / (long long)sizeof(fsclg_curve_t)) return set_err(FSCLG_E_ARG, "too many curve positions");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
+  B.n_cells = 0; B.nu = (int)nchunk; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
   B.eval_range = eval_range; B.bp_resl = 0; B.cv_ms = 0.0; B.cv_n = (int)total;
-  int r;
-  int nc = 0;
   if (total > 0) {
-    {  // the window null sums of every window the runs' positions touch, for the slot's rows: one
-       // covering cell per run (a slot another batch already runs on: only what is still missing)
-      std::vector<fsclg_cell_t> cover;
-      for (int i = 0; i < n_runs; i++)
-        if (runs[i].count > 0)
-          cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos,
-                                       runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
-      if (c->slot[slot].users == 0) r = fsclg_slot_windows(c, slot, cover.data(), (int)cover.size(), eval_range);
-      else r = ensure_windows(c, slot, eval_range, cover.data(), (int)cover.size(), &B.wr_memo);
-      if (r) return r;
-    }
     if ((r = ensure_io(B, 1))) return r;  // (make_params' cells and points: unused by this kernel)
     if ((r = ensure_pinned(&B.p_curve, &B.curve_cap, (int)total))) return r;
-    if ((r = ensure_pinned(&B.p_cmchunks, &B.cmchunk_cap, (int)nchunk))) return r;
-    int o = 0;
-    for (int i = 0; i < n_runs; i++)
-      for (int k = 0; k < runs[i].count; k += CH) {
-        const int cnt = std::min(CH, runs[i].count - k);
-        B.p_cmchunks[nc++] = ProfChunk{runs[i].chr, runs[i].start_pos + k * runs[i].step, runs[i].step, cnt, o, {0, 0, 0}};
-        o += cnt;
-      }
-    HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
-    Params P = make_params(c, B, slot, nc, 3, eval_range, 0);
-    P.band_th = -1; P.ivc0 = c->c_ivc0; P.n_civ = c->c_civ;  // the walk-window path, as the profile kernel
-    P.civ_max = std::max(P.n_civ - 1, 0); P.n_cache = P.n_civ * P.stride;
-    P.off_thr = P.n_cache * 32; P.off_nul = P.off_thr + (c->n_iv + 1) * 8;
-    P.off_lt = P.off_nul + (c->n_rows + 1) * 8 - 256 * 8;
-    P.off_lx = (P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0) + 15) & ~15;
-    P.ctrace = nullptr;
-    const int dyn = P.lx_on ? P.off_lx + LX_BYTES : P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0);
-    const int stat_m = (int)((sizeof(Smem) + 15) / 16 * 16);
-    unsigned long long* forced = c->d_stats + 24;
-    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
-    if (stat_m + dyn <= LDS_WG) {
-      static unsigned long long attr_set = 0;  // per device (bit = device id)
-      if (c->device >= 64 || !(attr_set >> c->device & 1ull)) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&curve_kernel<true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WG - stat_m), "hipFuncSetAttribute");
-        if (c->device < 64) attr_set |= 1ull << c->device;
-      }
-      hipLaunchKernelGGL((curve_kernel<true>), dim3(nc), dim3(WG), dyn, B.stream, P, (const ProfChunk*)B.p_cmchunks,
-                         B.p_curve, forced);
-    } else {  // tables too large for the LDS copies: every coefficient from the global table
-      hipLaunchKernelGGL((curve_kernel<false>), dim3(nc), dim3(WG), 0, B.stream, P, (const ProfChunk*)B.p_cmchunks,
-                         B.p_curve, forced);
-    }
-    HIPCHK(hipGetLastError(), "launch curve_kernel");
-    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+    if ((r = launch_runs(c, B, slot, runs, n_runs, eval_range, CH, (int)nchunk, RUN_CURVE, false))) return r;
   }
-  B.nu = nc;
-  B.pending = true; B.cv_pending = true;
+  B.holds = BK_CURVE;
   c->slot[slot].users++;
   return FSCLG_OK;
 }
@@ -5577,27 +5508,19 @@ int fsclg_curve_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* run
 int fsclg_curve_wait(fsclg_ctx* c, int batch, fsclg_curve_t* out) {
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
-  if (!B.pending || !B.cv_pending) return set_err(FSCLG_E_STATE, "no curves submitted on the batch");
+  if (B.holds != BK_CURVE) return set_err(FSCLG_E_STATE, "no curves submitted on the batch");
   if (!out && B.cv_n) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.pending = false; B.cv_pending = false;
+  B.holds = BK_NONE;
   c->slot[B.slot].users--;
   const int n = B.cv_n;
   if (n == 0) return FSCLG_OK;
   HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
   memcpy(out, B.p_curve, sizeof(fsclg_curve_t) * (size_t)n);
-  float ms = 0.f, t0 = 0.f, t1 = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
-  B.cv_ms = ms;
-  c->kernel_ms += ms;
-  c->launches++;
-  c->busy.emplace_back((double)t0, (double)t1);
-  int flags = 0;
+  int r, flags = 0;
+  if ((r = batch_time(c, B, 1, &B.cv_ms))) return r;
   for (int i = 0; i < n; i++) flags |= out[i].pt.flags;
-  if (flags) return set_err(flags & PF_UNSUPPORTED ? FSCLG_E_UNSUPPORTED : FSCLG_E_KERNEL, "device flag");
-  return FSCLG_OK;
+  return flags_err(flags);
 }
 
 double fsclg_curve_last_ms(fsclg_ctx* c, int batch) {
@@ -5629,7 +5552,7 @@ int fsclg_sites_submit(fsclg_ctx* c, int batch, int slot, const fsclg_site_req_t
   if (batch < 0 || batch >= NBATCH || slot < 0 || slot >= NSLOT) return set_err(FSCLG_E_ARG, "batch/slot");
   if (!c->d_pr0 || !c->d_coef) return set_err(FSCLG_E_STATE, "tables/snps not set");
   Batch& B = c->batch[batch];
-  if (B.pending) return set_err(FSCLG_E_STATE, "batch not waited for");
+  if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
   for (int i = 0; i < n_req; i++) {
     if (req[i].chr < 0 || req[i].chr >= c->n_chr) return set_err(FSCLG_E_ARG, "request chromosome");
     // (+ 64: init_scan_result's de-collision may move a point past its position)
@@ -5642,12 +5565,10 @@ int fsclg_sites_submit(fsclg_ctx* c, int batch, int slot, const fsclg_site_req_t
   B.eval_range = eval_range; B.bp_resl = 0; B.st_ms = 0.0; B.st_n = n_req; B.st_synced = false;
   int r;
   if (n_req > 0) {
-    {  // the window null sums for the slot's rows: one covering cell per request
+    {  // one covering cell per request
       std::vector<fsclg_cell_t> cover((size_t)n_req);
       for (int i = 0; i < n_req; i++) cover[i] = fsclg_cell_t{req[i].chr, req[i].pos, req[i].pos, 0};
-      if (c->slot[slot].users == 0) r = fsclg_slot_windows(c, slot, cover.data(), n_req, eval_range);
-      else r = ensure_windows(c, slot, eval_range, cover.data(), n_req, &B.wr_memo);
-      if (r) return r;
+      if ((r = cover_windows(c, B, slot, cover, eval_range))) return r;
     }
     if ((r = ensure_io(B, 1))) return r;  // (make_params' cells and points: unused by this kernel)
     if ((r = ensure_pinned(&B.p_sreq, &B.sreq_cap, n_req))) return r;
@@ -5661,21 +5582,8 @@ int fsclg_sites_submit(fsclg_ctx* c, int batch, int slot, const fsclg_site_req_t
     HIPCHK(hipGetLastError(), "launch sites_kernel");
     HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
   }
-  B.pending = true; B.st_pending = true;
+  B.holds = BK_SITES;
   c->slot[slot].users++;
-  return FSCLG_OK;
-}
-
-// the time of the launch bracketed by the batch's events, added to the context's totals
-static int sites_time(fsclg_ctx* c, Batch& B) {
-  float ms = 0.f, t0 = 0.f, t1 = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
-  B.st_ms += ms;
-  c->kernel_ms += ms;
-  c->launches++;
-  c->busy.emplace_back((double)t0, (double)t1);
   return FSCLG_OK;
 }
 
@@ -5686,7 +5594,7 @@ static int sites_wait_impl(fsclg_ctx* c, Batch& B, fsclg_site_hdr_t* hdr, double
   if ((r = ensure_pinned(&B.p_sterms, &B.sterm_cap, (int)cap))) return r;
   for (int i = 0; i < n; i++) flags |= B.p_shdr[i].pt.flags;
   memcpy(hdr, B.p_shdr, sizeof(fsclg_site_hdr_t) * (size_t)n);
-  if (flags) return set_err(flags & PF_UNSUPPORTED ? FSCLG_E_UNSUPPORTED : FSCLG_E_KERNEL, "device flag");
+  if (flags) return flags_err(flags);
   const Params P0 = make_params(c, B, B.slot, 0, 3, B.eval_range, 0);
   std::vector<SiteTask> tasks;
   int i = 0, k = 0;  // the next term: term k of walk i
@@ -5716,7 +5624,9 @@ static int sites_wait_impl(fsclg_ctx* c, Batch& B, fsclg_site_hdr_t* hdr, double
     HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
     memcpy(terms + done, B.p_sterms, sizeof(double) * fill);
     done += fill;
-    if ((r = sites_time(c, B))) return r;
+    double ms = 0.0;
+    if ((r = batch_time(c, B, 1, &ms))) return r;
+    B.st_ms += ms;
   }
   return FSCLG_OK;
 }
@@ -5724,7 +5634,7 @@ static int sites_wait_impl(fsclg_ctx* c, Batch& B, fsclg_site_hdr_t* hdr, double
 int fsclg_sites_wait(fsclg_ctx* c, int batch, fsclg_site_hdr_t* hdr, double* terms, size_t terms_cap, size_t* n_terms) {
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
-  if (!B.pending || !B.st_pending) return set_err(FSCLG_E_STATE, "no site terms submitted on the batch");
+  if (B.holds != BK_SITES) return set_err(FSCLG_E_STATE, "no site terms submitted on the batch");
   const int n = B.st_n;
   if (!hdr && n) return set_err(FSCLG_E_ARG, "hdr");  // (the batch stays submitted)
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
@@ -5733,11 +5643,13 @@ int fsclg_sites_wait(fsclg_ctx* c, int batch, fsclg_site_hdr_t* hdr, double* ter
   if (n > 0 && !B.st_synced) {
     hipError_t e = hipEventSynchronize(B.ev1);
     if (e != hipSuccess) {  // the batch ends here
-      B.pending = false; B.st_pending = false; c->slot[B.slot].users--;
+      B.holds = BK_NONE; c->slot[B.slot].users--;
       return set_err(FSCLG_E_HIP, "hipEventSynchronize");
     }
     B.st_synced = true;
-    r = sites_time(c, B);
+    double ms = 0.0;
+    r = batch_time(c, B, 1, &ms);
+    B.st_ms += ms;
     uint64_t off = 0;  // the offsets: a running sum in request order
     for (int i = 0; i < n && r == FSCLG_OK; i++) { B.p_shdr[i].off = off; off += (uint64_t)B.p_shdr[i].len; }
   }
@@ -5746,7 +5658,7 @@ int fsclg_sites_wait(fsclg_ctx* c, int batch, fsclg_site_hdr_t* hdr, double* ter
   if (r == FSCLG_OK && (terms_cap < total || (!terms && total)))  // (the batch stays submitted)
     return set_err(FSCLG_E_ARG, "terms_cap below the walks' terms");
   if (r == FSCLG_OK && n > 0) r = sites_wait_impl(c, B, hdr, terms);
-  B.pending = false; B.st_pending = false;
+  B.holds = BK_NONE;
   c->slot[B.slot].users--;
   return r;
 }
@@ -5805,7 +5717,7 @@ int fsclg_sample_submit(fsclg_ctx* c, int batch, const int32_t* depth_of_site, c
   if (!c->d_pr0 || !c->d_thr) return set_err(FSCLG_E_STATE, "tables/snps not set");
   if (!c->smp_n_depths || c->smp_n_iv != c->n_iv) return set_err(FSCLG_E_STATE, "sample tables not set for these tables");
   Batch& B = c->batch[batch];
-  if (B.pending) return set_err(FSCLG_E_STATE, "batch not waited for");
+  if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
   const int n = c->n_snps;
   for (int i = 0; i < n; i++)
     if (depth_of_site[i] < 0 || depth_of_site[i] >= c->smp_n_depths) return set_err(FSCLG_E_ARG, "depth of a site");
@@ -5855,26 +5767,20 @@ int fsclg_sample_submit(fsclg_ctx* c, int batch, const int32_t* depth_of_site, c
   hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((n + nw - 1) / nw)), dim3(64 * nw), lds, B.stream, P);
   HIPCHK(hipGetLastError(), "launch sample_kernel");
   HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
-  B.pending = true; B.sm_pending = true;
+  B.holds = BK_SAMPLE;
   return FSCLG_OK;
 }
 
 int fsclg_sample_wait(fsclg_ctx* c, int batch, int32_t* freq_out, unsigned long long* n_degenerate) {
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
-  if (!B.pending || !B.sm_pending) return set_err(FSCLG_E_STATE, "no sample submitted on the batch");
+  if (B.holds != BK_SAMPLE) return set_err(FSCLG_E_STATE, "no sample submitted on the batch");
   if (!freq_out) return set_err(FSCLG_E_ARG, "freq_out");  // (the batch stays submitted)
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.pending = false; B.sm_pending = false;
+  B.holds = BK_NONE;
   HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
-  float ms = 0.f, t0 = 0.f, t1 = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
-  B.sm_ms = ms;
-  c->kernel_ms += ms;
-  c->launches++;
-  c->busy.emplace_back((double)t0, (double)t1);
+  int r;
+  if ((r = batch_time(c, B, 1, &B.sm_ms))) return r;
   unsigned long long deg = 0;
   for (int i = 0; i < B.sm_n; i++) {
     freq_out[i] = B.p_sfreq[i];
@@ -5897,7 +5803,7 @@ int fsclg_tail_submit(fsclg_ctx* c, int batch, const float* samples, size_t n_sa
   if (batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   if (n_samples > (size_t)0x7fffffff) return set_err(FSCLG_E_ARG, "tail: more than 2^31 - 1 samples in one call");
   Batch& B = c->batch[batch];
-  if (B.pending) return set_err(FSCLG_E_STATE, "batch not waited for");
+  if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
   for (int p = 0; p < n_points; p++)
     if (counts[p] < 0 || offsets[p] > n_samples || (size_t)counts[p] > n_samples - offsets[p])
       return set_err(FSCLG_E_ARG, "tail: a point's samples lie outside the array");
@@ -5937,26 +5843,20 @@ int fsclg_tail_submit(fsclg_ctx* c, int batch, const float* samples, size_t n_sa
     HIPCHK(hipGetLastError(), "launch tail_kernel");
   }
   HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
-  B.pending = true; B.tl_pending = true;
+  B.holds = BK_TAIL;
   return FSCLG_OK;
 }
 
 int fsclg_tail_wait(fsclg_ctx* c, int batch, fsclg_tail_t* out) {
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
-  if (!B.pending || !B.tl_pending) return set_err(FSCLG_E_STATE, "no tail fit submitted on the batch");
+  if (B.holds != BK_TAIL) return set_err(FSCLG_E_STATE, "no tail fit submitted on the batch");
   if (!out && B.tl_n) return set_err(FSCLG_E_ARG, "out");  // (the batch stays submitted)
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.pending = false; B.tl_pending = false;
+  B.holds = BK_NONE;
   HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
-  float ms = 0.f, t0 = 0.f, t1 = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, B.ev0, B.ev1), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
-  HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
-  B.tl_ms = ms;
-  c->kernel_ms += ms;
-  c->launches++;
-  c->busy.emplace_back((double)t0, (double)t1);
+  int r;
+  if ((r = batch_time(c, B, 1, &B.tl_ms))) return r;
   if (B.tl_n) memcpy(out, B.p_tout, sizeof(fsclg_tail_t) * (size_t)B.tl_n);
   return FSCLG_OK;
 }

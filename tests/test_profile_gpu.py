@@ -16,6 +16,7 @@ import pytest
 
 from util import CLI, ROOT, read_dump, run_oracle, same_bits
 import fscl_amd
+import walk_ref as wr
 from fscl_amd import synth
 
 sys.path.insert(0, str(ROOT / "oracle"))
@@ -122,6 +123,82 @@ def test_tiny_chromosomes_whole_chromosome_windows(built, tmp):
     # (the chromosomes and -g 1000 -G 20000 as specified: 6.19 Mb in all, 6 197 points, most of them on
     # chromosomes of a few SNPs whose points cost the oracle nothing: 0.65 s for the whole case)
     check_profile(snp, 1000, 20000, what="tiny", limit=6200)
+
+
+def test_a_batch_holds_one_kind_of_call(built, tmp):
+    """On a context of its own with the tiny chromosomes' tables, one run of two positions: a batch that
+    holds a profile is rejected by the search's and the cell maxima's wait (FSCLG_E_STATE) and stays
+    submitted; its own wait then returns the points of a plain fsclg_profile call, and a search on
+    batch 0 runs after it.  Then the accounting of three calls of different kinds: one launch each, and
+    their kernel times added to kernel_ms in call order."""
+    chrs = []
+    for i, (k, length) in enumerate(((1, 50_000), (2, 90_000), (3, 150_000), (64, 700_000), (65, 900_000),
+                                     (130, 1_300_000))):
+        chrs += synth.generate(n_chr=1, chr_len=length, snps_per_chr=k, n=16, seed=170 + i, chr_names=[f"t{i}"],
+                               sweeps_per_chr=1 if k >= 64 else 0, folded=0.3 if k >= 64 else 0.0,
+                               missing=0.2 if k >= 64 else 0.0, max_missing=2)
+    snp = tmp / "tiny6.snp"
+    synth.write_snp_file(str(snp), chrs)
+    ot = wr.OracleTables(snp)
+    s = ot.o.s.contents
+    lim = C.cast(s.chr, C.POINTER(OrcChr))
+    chr_start, chr_n = [lim[c].start_index for c in range(6)], [lim[c].n_snps for c in range(6)]
+    assert chr_n == [1, 2, 3, 64, 65, 130]
+    E_STATE, er, vp = -3, 81920, C.c_void_p
+    RunT, PointT = fscl_amd.RunT, fscl_amd.PointT
+    shim = wr.Shim()
+    try:
+        L, ctx = shim.L, shim.ctx
+        for name, res, args in (("fsclg_profile_submit", C.c_int, [vp, C.POINTER(RunT), C.c_int, C.c_int]),
+                                ("fsclg_profile_wait", C.c_int, [vp, C.POINTER(PointT)]),
+                                ("fsclg_search_wait", C.c_int, [vp, C.c_int, C.POINTER(PointT)]),
+                                ("fsclg_search_maxpos", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PointT)]),
+                                ("fsclg_cellmax_submit", C.c_int, [vp, C.c_int, C.c_int, C.POINTER(RunT), C.c_int, C.c_int]),
+                                ("fsclg_cellmax_wait", C.c_int, [vp, C.c_int, C.POINTER(PointT)]),
+                                ("fsclg_curve_submit", C.c_int, [vp, C.c_int, C.c_int, C.POINTER(RunT), C.c_int, C.c_int]),
+                                ("fsclg_curve_wait", C.c_int, [vp, C.c_int, vp]),
+                                ("fsclg_profile_last_ms", C.c_double, [vp]),
+                                ("fsclg_cellmax_last_ms", C.c_double, [vp, C.c_int]),
+                                ("fsclg_curve_last_ms", C.c_double, [vp, C.c_int])):
+            getattr(L, name).restype, getattr(L, name).argtypes = res, args
+        shim.upload(ot.tables, chr_start, chr_n)
+        shim.set_chr_null(-123.25, 6)
+        runs = (RunT * 1)(RunT(5, 400_000, 1000, 2))
+        want, got, other = (PointT * 2)(), (PointT * 2)(), (PointT * 2)()
+        shim._ok(L.fsclg_profile(ctx, runs, 1, er, want), "fsclg_profile")
+        assert [q.sweep_pos > 0 and q.flags == 0 and math.isfinite(q.clr) for q in want] == [True, True]
+
+        shim._ok(L.fsclg_profile_submit(ctx, runs, 1, er), "fsclg_profile_submit")
+        assert L.fsclg_search_wait(ctx, 0, other) == E_STATE
+        assert L.fsclg_cellmax_wait(ctx, 0, other) == E_STATE
+        assert bytes(other) == bytes(2 * C.sizeof(PointT)), "a rejected wait wrote points"
+        shim._ok(L.fsclg_profile_wait(ctx, got), "fsclg_profile_wait")
+        assert bytes(got) == bytes(want)
+        cell = np.array([5, 380_000, 420_000, 0], dtype=np.int32)  # fsclg_cell_t
+        shim._ok(L.fsclg_search_maxpos(ctx, cell.ctypes.data, 1, er, 100, other), "fsclg_search_maxpos")
+        assert other[0].flags == 0 and other[0].chr == 5
+
+        st0, st1 = wr.StatsT(), wr.StatsT()
+        shim._ok(L.fsclg_get_stats(ctx, C.byref(st0)), "fsclg_get_stats")
+        shim._ok(L.fsclg_profile(ctx, runs, 1, er, got), "fsclg_profile")
+        shim._ok(L.fsclg_cellmax_submit(ctx, 1, 0, runs, 1, er), "fsclg_cellmax_submit")
+        shim._ok(L.fsclg_cellmax_wait(ctx, 1, other), "fsclg_cellmax_wait")
+        curves = np.zeros(2, dtype=fscl_amd.CURVE_DTYPE)
+        shim._ok(L.fsclg_curve_submit(ctx, 2, 0, runs, 1, er), "fsclg_curve_submit")
+        shim._ok(L.fsclg_curve_wait(ctx, 2, curves.ctypes.data), "fsclg_curve_wait")
+        shim._ok(L.fsclg_get_stats(ctx, C.byref(st1)), "fsclg_get_stats")
+        ms = [L.fsclg_profile_last_ms(ctx), L.fsclg_cellmax_last_ms(ctx, 1), L.fsclg_curve_last_ms(ctx, 2)]
+        print(f"launches {st0.n_launches} -> {st1.n_launches}, kernel_ms {st0.kernel_ms!r} -> {st1.kernel_ms!r}, "
+              f"last_ms {ms!r}")
+        assert all(m > 0.0 for m in ms)
+        assert st1.n_launches - st0.n_launches == 3
+        acc = st0.kernel_ms
+        for m in ms:
+            acc += m
+        assert abs(st1.kernel_ms - acc) <= 1e-9
+        assert bytes(got) == bytes(want)
+    finally:
+        shim.close()
 
 
 def test_positions_on_snps(built, tmp):

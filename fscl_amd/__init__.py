@@ -121,6 +121,11 @@ class TailT(C.Structure):  # fscl_amd_tail_t
                 ("kernel_ms", C.c_double), ("wall_s", C.c_double)]
 
 
+class SurfacesT(C.Structure):  # fscl_amd_surfaces_t
+    _fields_ = [("n", C.c_int), ("hdr", C.c_void_p), ("pts", C.c_void_p), ("sm", C.c_void_p), ("n_pos", C.c_size_t),
+                ("n_cells", C.c_size_t), ("n_terms", C.c_ulonglong)]
+
+
 class PointT(C.Structure):  # fsclg_point_t
     _fields_ = [("chr", C.c_int32), ("nearest_snp", C.c_int32), ("sweep_pos", C.c_int32), ("n_snps", C.c_int32),
                 ("window_start", C.c_int32), ("window_end", C.c_int32), ("flags", C.c_int32), ("cost", C.c_uint32),
@@ -164,6 +169,10 @@ EXPORTS = [
     "fsclg_tail_submit", "fsclg_tail_wait", "fsclg_tail_last_ms",
     "fscl_amd_tail_fit", "fscl_amd_tail_runs", "fscl_amd_tail_last_ms", "fscl_amd_tail_free", "fscl_amd_tail_count",
     "fscl_amd_tail_chunk", "fscl_amd_tail_pack", "fscl_amd_tail_log10p", "fscl_amd_tail_summary", "fscl_amd_tail_output",
+    "fsclg_surface_submit", "fsclg_surface_wait", "fsclg_surface_last_ms",
+    "fscl_amd_surface_alphas", "fscl_amd_surface_run", "fscl_amd_scan_surface", "fscl_amd_scan_point_surfaces",
+    "fscl_amd_surfaces_free", "fscl_amd_surface_region", "fscl_amd_surface_output", "fscl_amd_surface_runs",
+    "fscl_amd_surface_last_ms",
 ]
 
 
@@ -259,6 +268,17 @@ def _load() -> C.CDLL:
         "fscl_amd_tail_free": (None, [P(TailT)]),
         "fscl_amd_tail_summary": (None, [P(ScanT), P(TailT)]),
         "fscl_amd_tail_output": (C.c_int, [C.c_char_p, P(ScanT), P(TailT), C.c_char_p]),
+        "fscl_amd_surface_alphas": (C.c_int, [C.c_double, C.c_double, C.c_int, C.c_double, C.c_void_p]),
+        "fscl_amd_surface_run": (C.c_int, [P(ScanT), C.c_void_p, P(RunT)]),
+        "fscl_amd_scan_surface": (C.c_int, [P(ScanT), P(SmPtableT), C.c_int, C.c_void_p, C.c_int, P(SurfacesT)]),
+        "fscl_amd_scan_point_surfaces": (C.c_int, [P(ScanT), P(SmPtableT), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                   C.c_double, C.c_int, P(SurfacesT)]),
+        "fscl_amd_surfaces_free": (None, [P(SurfacesT)]),
+        "fscl_amd_surface_region": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
+        "fscl_amd_surface_output": (C.c_int, [C.c_char_p, P(ScanT), P(SurfacesT), C.c_double, C.c_char_p]),
+        "fscl_amd_surface_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(RunT), C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+        "fscl_amd_surface_last_ms": (C.c_double, []),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -710,6 +730,199 @@ def sites_cap() -> int:
     return int(get_lib().fsclg_sites_cap())
 
 
+SURFACE_MAX_LA = 64  # FSCL_AMD_SURFACE_MAX_LA: alphas per list at most
+LOG_AD_MIN, LOG_AD_MAX = -20.0, 4.0
+# fscl_amd_surface_req_t: chromosome index, centre position, half-width and step in bp, the list's length,
+# the scan point the request is centred on (-1: none), the ascending log alphas
+SURFACE_REQ_DTYPE = np.dtype([("chr", "i4"), ("centre_pos", "i4"), ("halfwidth", "i4"), ("step", "i4"), ("n_la", "i4"),
+                              ("point", "i4"), ("la", "f8", (SURFACE_MAX_LA,))])
+# fscl_amd_surface_hdr_t: the request, the run evaluated (start_pos + p * step, p < n_pos) and where the
+# surface's points and values start in the result's flat arrays
+SURFACE_DTYPE = np.dtype([("chr", "i4"), ("centre_pos", "i4"), ("halfwidth", "i4"), ("step", "i4"), ("n_la", "i4"),
+                          ("point", "i4"), ("start_pos", "i4"), ("n_pos", "i4"), ("pos_off", "u8"), ("cell_off", "u8"),
+                          ("la", "f8", (SURFACE_MAX_LA,))])
+assert SURFACE_REQ_DTYPE.itemsize == 24 + 8 * SURFACE_MAX_LA and SURFACE_DTYPE.itemsize == 48 + 8 * SURFACE_MAX_LA
+# fscl_amd_surface_region_t: indices into the surface's positions and alphas (-1: every cell NaN)
+SURFACE_REGION_DTYPE = np.dtype([(k, "i4") for k in ("n_pos", "n_la", "max_ipos", "max_ila", "ipos_lo", "ipos_hi", "ila_lo",
+                                                      "ila_hi", "open_pos_lo", "open_pos_hi", "open_la_lo", "open_la_hi",
+                                                      "n_region", "pad")] + [("max_v", "f8")])
+
+
+class Surface:
+    """One position-by-alpha surface: ``hdr`` (a SURFACE_DTYPE record), ``la`` (the n_la log alphas),
+    ``pts`` (the n_pos points, fsclg_point_t fields) and ``sm`` (float64 [n_pos][n_la], what
+    sm_likelihood returns at each position and alpha)."""
+
+    def __init__(self, hdr, pts, sm):
+        self.hdr, self.pts, self.sm = hdr, pts, sm
+        self.la = np.array(hdr["la"][:int(hdr["n_la"])], dtype=np.float64)
+
+    @property
+    def null_logl(self):
+        return np.ascontiguousarray(self.pts["null_logl"], dtype=np.float64)
+
+
+def surface_alphas(lo: float = LOG_AD_MIN, hi: float = LOG_AD_MAX, n: int = 33, fitted: float = float("nan")) -> np.ndarray:
+    """The grid lo + i (hi - lo) / (n - 1), i < n, with ``fitted`` inserted in order (not when it equals a
+    grid value, is NaN or lies outside [-20, 4]).  Host only."""
+    out = np.zeros(SURFACE_MAX_LA, dtype=np.float64)
+    m = get_lib().fscl_amd_surface_alphas(float(lo), float(hi), int(n), float(fitted), out.ctypes.data)
+    if m < 1:
+        raise ValueError("surface alphas: -20 <= lo <= hi <= 4, 1 <= n <= 63, lo < hi unless n is 1")
+    return out[:m].copy()
+
+
+_surface_grid = surface_alphas  # (run() has a keyword of that name)
+
+
+def _surface_requests(requests) -> np.ndarray:
+    req = np.zeros(len(requests), dtype=SURFACE_REQ_DTYPE)
+    for q, r in zip(req, requests):
+        la = np.asarray(r[4], dtype=np.float64).reshape(-1)
+        if not 1 <= len(la) <= SURFACE_MAX_LA:
+            raise ValueError("a surface takes 1 to 64 alphas")
+        q["chr"], q["centre_pos"], q["halfwidth"], q["step"] = (int(v) for v in r[:4])
+        q["n_la"], q["point"] = len(la), int(r[5]) if len(r) > 5 else -1
+        q["la"][:len(la)] = la
+    return req
+
+
+def surface_run(scan, request):
+    """(chr, start_pos, step, count): the positions of one request (chr, centre, halfwidth, step, alphas)
+    clipped to the chromosome's span.  Host only."""
+    req = _surface_requests([request])
+    run = RunT()
+    if get_lib().fscl_amd_surface_run(scan, req.ctypes.data, C.byref(run)) != 0:
+        raise ValueError("surface request: a chromosome of the scan, step >= 1, halfwidth >= 0")
+    return int(run.chr), int(run.start_pos), int(run.step), int(run.count)
+
+
+def _surfaces_take(res: SurfacesT) -> list:
+    """The surfaces copied out of a native result, which is released."""
+    n, npos, nc = int(res.n), int(res.n_pos), int(res.n_cells)
+    hdr = np.zeros(n, dtype=SURFACE_DTYPE)
+    pts = np.zeros(npos, dtype=_POINT_RAW)
+    sm = np.zeros(nc, dtype=np.float64)
+    if n:
+        C.memmove(hdr.ctypes.data, res.hdr, n * SURFACE_DTYPE.itemsize)
+    if npos:
+        C.memmove(pts.ctypes.data, res.pts, npos * _POINT_RAW.itemsize)
+    if nc:
+        C.memmove(sm.ctypes.data, res.sm, nc * 8)
+    terms = int(res.n_terms)
+    get_lib().fscl_amd_surfaces_free(C.byref(res))
+    out = []
+    for h in hdr:
+        p0, c0, m, k = int(h["pos_off"]), int(h["cell_off"]), int(h["n_pos"]), int(h["n_la"])
+        out.append(Surface(h, pts[p0:p0 + m].copy(), sm[c0:c0 + m * k].reshape(m, k).copy()))
+    _surface_terms[0] = terms
+    return out
+
+
+_surface_terms = [0]
+
+
+def surface_last_terms() -> int:
+    """The terms of the walks of the last scan_surface / scan_point_surfaces call."""
+    return _surface_terms[0]
+
+
+def scan_surface(scan, tables, requests, eval_range: int = 81920) -> list:
+    """The likelihood surface of each request (chromosome index, centre position, half-width bp, step bp,
+    ascending log alphas[, scan point index]), on the data as loaded (include/fscl_amd.h): a list of
+    Surface in the given order."""
+    req = _surface_requests(requests)
+    res = SurfacesT()
+    _curve_check(get_lib().fscl_amd_scan_surface(scan, tables, int(eval_range), req.ctypes.data if len(req) else None,
+                                                 len(req), C.byref(res)), "fscl_amd_scan_surface")
+    return _surfaces_take(res)
+
+
+def scan_point_surfaces(scan, tables, top: int = 3, halfwidth: int = 100000, step: int = 1000, alphas=(LOG_AD_MIN, LOG_AD_MAX, 33),
+                        eval_range: int = 81920) -> list:
+    """The surfaces around the ``top`` scan points of greatest CLR (none within ``halfwidth`` of one already
+    chosen), each centred on its sweep_pos, on the grid ``alphas`` = (lo, hi, n) with the point's fitted
+    lalpha inserted: a list of Surface in descending CLR order."""
+    res = SurfacesT()
+    _curve_check(get_lib().fscl_amd_scan_point_surfaces(scan, tables, int(eval_range), int(top), int(halfwidth), int(step),
+                                                        float(alphas[0]), float(alphas[1]), int(alphas[2]), C.byref(res)),
+                 "fscl_amd_scan_point_surfaces")
+    return _surfaces_take(res)
+
+
+def surface_runs(scan, tables, runs, alphas, eval_range: int = 81920, rows=None, batch: int = 0, pts=None, sm=None):
+    """fsclg_surface_submit / fsclg_surface_wait on the scan's first device (the shim-level handle, next to
+    curve_runs): ``alphas`` holds one ascending list per run, all of one length.  Returns (points
+    [sum(count)], values [sum(count)][n_la]); ``pts`` / ``sm``: arrays to fill (tests pre-fill them)."""
+    arr = (RunT * max(len(runs), 1))(*[RunT(*[int(v) for v in r]) for r in runs])
+    la = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(runs), -1) if len(runs) else np.zeros((0, 1))
+    n, k = sum(max(int(r[3]), 0) for r in runs), la.shape[1]
+    if pts is None:
+        pts = np.zeros(max(n, 1), dtype=_POINT_RAW)
+    if sm is None:
+        sm = np.zeros(max(n, 1) * k, dtype=np.float64)
+    if pts.dtype != _POINT_RAW or len(pts) < n or sm.dtype != np.float64 or sm.size < n * k or \
+            not (pts.flags.c_contiguous and sm.flags.c_contiguous):
+        raise ValueError("pts / sm must be contiguous arrays of sum(count) points and sum(count) * n_la values")
+    rp = None
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        if len(rows) != scan.contents.n_snps:
+            raise ValueError("rows must hold one row per site")
+        rp = rows.ctypes.data
+    _curve_check(get_lib().fscl_amd_surface_runs(scan, tables, arr, len(runs), la.ctypes.data, k, int(eval_range), rp,
+                                                 int(batch), pts.ctypes.data, sm.ctypes.data), "fscl_amd_surface_runs")
+    return pts[:n], sm.reshape(-1)[:n * k].reshape(n, k)
+
+
+def surface_region(surface, drop: float = 2.0, null_logl=None):
+    """The region summary of a Surface, or of a float64 [n_pos][n_la] array with the positions' null sums
+    ``null_logl`` (default 0): (SURFACE_REGION_DTYPE record, uint8 marks [n_pos][n_la]: 2 the argmax, 1 the
+    joint region, 0 elsewhere), or (record, marks) with indices -1 when every cell is NaN.  Host only.  The
+    likelihood is composite: the region describes the surface, it is not a calibrated confidence region."""
+    if isinstance(surface, Surface):
+        sm, nul = surface.sm, surface.null_logl
+    else:
+        sm = np.asarray(surface, dtype=np.float64)
+        nul = np.zeros(sm.shape[0]) if null_logl is None else np.asarray(null_logl, dtype=np.float64)
+    sm = np.ascontiguousarray(sm, dtype=np.float64)
+    nul = np.ascontiguousarray(nul, dtype=np.float64)
+    if sm.ndim != 2 or sm.shape[0] < 1 or sm.shape[1] < 1 or nul.shape != (sm.shape[0],):
+        raise ValueError("a surface is a non-empty [n_pos][n_la] array with one null sum per position")
+    out = np.zeros(1, dtype=SURFACE_REGION_DTYPE)
+    mark = np.zeros(sm.shape, dtype=np.uint8)
+    r = get_lib().fscl_amd_surface_region(sm.ctypes.data, nul.ctypes.data, sm.shape[0], sm.shape[1], float(drop),
+                                          out.ctypes.data, mark.ctypes.data)
+    if r < 0:
+        raise ValueError("drop must be >= 0")
+    return out[0], mark
+
+
+def surface_output(path, scan, surfaces, drop: float = 2.0, label=None) -> None:
+    """The --surface-file format (include/fscl_amd.h, README): per surface one row per cell,
+    position-major, then one summary row.  Host only."""
+    n = len(surfaces)
+    hdr = np.zeros(max(n, 1), dtype=SURFACE_DTYPE)
+    po = co = 0
+    for i, sf in enumerate(surfaces):
+        hdr[i] = sf.hdr
+        if sf.sm.shape != (len(sf.pts), int(sf.hdr["n_la"])):
+            raise ValueError("a surface's values must be [n_pos][n_la]")
+        hdr["n_pos"][i], hdr["pos_off"][i], hdr["cell_off"][i] = len(sf.pts), po, co
+        po += len(sf.pts)
+        co += sf.sm.size
+    pts = np.concatenate([np.ascontiguousarray(sf.pts, dtype=_POINT_RAW) for sf in surfaces]) if n else np.zeros(0, _POINT_RAW)
+    sm = np.concatenate([np.ascontiguousarray(sf.sm, dtype=np.float64).reshape(-1) for sf in surfaces]) if n else np.zeros(0)
+    res = SurfacesT(n, hdr.ctypes.data, pts.ctypes.data if len(pts) else None, sm.ctypes.data if len(sm) else None,
+                    len(pts), len(sm), 0)
+    if get_lib().fscl_amd_surface_output(_b(path), scan, C.byref(res), float(drop), _b(label)) != 0:
+        raise ValueError(f"surface_output: drop must be >= 0 and {path} writable")
+
+
+def surface_last_ms() -> float:
+    return float(get_lib().fscl_amd_surface_last_ms())
+
+
 # fscl_amd_sweep_t: chromosome index, position, alpha (> 0)
 SWEEP_DTYPE = np.dtype([("chr", "i4"), ("pos", "i4"), ("alpha", "f8")])
 # fscl_amd_boot_t: one planted sweep in one replicate; est_pos -1 (and NaN est_lalpha / clr) when the
@@ -986,7 +1199,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         profile_file=None, small_grid_sp=1000, scan_mode="bisection", alpha_file=None, alpha_drop=2.0,
         sites_file=None, sites_top=10, simulate_file=None, simulate_sweeps=(), simulate_seed=0xFD821A6, simulate_rep=0,
         bootstrap_file=None, bootstrap_reps=100, bootstrap_window=None, bootstrap_sweeps=(), bootstrap_top=3,
-        tail_file=None, tail_df=2, tail_min_n=20):
+        tail_file=None, tail_df=2, tail_min_n=20, surface_file=None, surface_top=3, surface_halfwidth=None,
+        surface_step=None, surface_alphas=(LOG_AD_MIN, LOG_AD_MAX, 33), surface_drop=2.0):
     """The fscl main() pipeline (fscl.c:316-337) in-process; returns the scan_t
     pointer (points(scan) reads the results).  permute_mode "throughput": the
     counter-based permutation test (set_permute_mode).  scan_mode "grid": the CLI's
@@ -1001,6 +1215,14 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         raise ValueError("the bootstrap rescans by bisection (not with scan_mode grid)")
     if bootstrap_file is not None and (int(bootstrap_reps) < 0 or int(bootstrap_top) < 0):
         raise ValueError("bootstrap_reps and bootstrap_top must be >= 0")
+    if surface_file is not None:
+        if int(surface_top) < 0 or not float(surface_drop) >= 0.0:
+            raise ValueError("surface_top and surface_drop must be >= 0")
+        if int(small_grid_sp if surface_step is None else surface_step) < 1:
+            raise ValueError("surface_step must be at least 1")
+        if int(large_grid_sp if surface_halfwidth is None else surface_halfwidth) < 0:
+            raise ValueError("surface_halfwidth must be >= 0")
+        _surface_grid(*surface_alphas)  # (raises ValueError)
     if tail_file is not None:
         _tail_df(tail_df)
         if int(n_permute) <= 0:
@@ -1034,6 +1256,11 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         curve_output(alpha_file, scan, scan_point_curves(scan, tab, eval_range), alpha_drop, label)
     if sites_file is not None:  # the CLI's --sites-file: the per-site terms of the scan points' walks
         sites_output(sites_file, scan, *scan_point_sites(scan, tab, sites_top, eval_range), label)
+    if surface_file is not None:  # the CLI's --surface-file: the surfaces around the points of greatest CLR
+        surface_output(surface_file, scan,
+                       scan_point_surfaces(scan, tab, surface_top, int(large_grid_sp if surface_halfwidth is None else surface_halfwidth),
+                                           int(small_grid_sp if surface_step is None else surface_step), surface_alphas,
+                                           eval_range), surface_drop, label)
     if n_permute > 0 and scan_mode == "grid":
         scan_permute_grid(scan, tab, n_permute, permute_nbp, eval_range, small_grid_sp, large_grid_sp, scan_width_mb)
     elif n_permute > 0:

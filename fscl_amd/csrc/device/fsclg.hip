@@ -2591,6 +2591,153 @@ sites_kernel(Params P, int pass, const fsclg_site_req_t* __restrict__ req, fsclg
   }
 }
 
+// ------------------------------------------------------------ likelihood surface
+// The position-by-alpha surface of dense runs (fsclg_surface_submit): no alpha search, every run with an
+// ascending list of n_la log alphas of its own.  A workgroup takes a chunk of consecutive positions of
+// one run; its waves do init_scan_result for the chunk's positions, then deal themselves the chunk's
+// items, one item = one position and a block of SURF_B neighbouring alphas of the list: item it is
+// (position it / nblk, block it % nblk), so the waves running together hold the other alpha blocks of
+// the same position (the same sites and log-table entries in the vector L1), the further waves the next
+// positions.  A wave walks its item in the walk order of sm-search.c:105-150 -- the nearest SNP and the
+// sites to its left, 64 per trip, then the sites to its right -- over the trip range of the block's
+// smallest alpha, whose walk is the longest (log(alpha d) is nondecreasing in alpha).  Per trip a lane
+// loads its site (position and row) once and gathers logt(|d|) once; per alpha of the block it forms
+// log(alpha d), takes the interval and the coefficients and evaluates the term.  A lane whose site is
+// past an alpha's own cut, log(alpha d) > LOG_AD_MAX, holds no term for that alpha: logt is
+// nondecreasing in |d| and |d| nondecreasing along either part once the nearest SNP is inside (the sites
+// init_scan_result's de-collision stepped over lie nearer than the nearest SNP), so the lanes inside are
+// a prefix of the trip and their count is the walk bound of that alpha (sites_kernel's argument).  The
+// trip's terms are folded into the alpha's running sum in lane order by exact_chunk_add, i.e. the
+// strictly sequential sum in walk order (one wave reduction where the chunk stays in the binade with no
+// tie, term by term otherwise): every value is exact whatever N is, there is no integer-ulp fast path
+// to fall back from and no argmax to settle.  The values of a chunk meet in LDS; after one barrier the
+// workgroup stores them with plain vector stores (host memory), and one thread per position takes the
+// row's first strict maximum in list order from the reference's (-DBL_MAX, LOG_AD_MAX) state and
+// stores the point.  No atomics on the result path, no workgroup waits for another.
+#ifndef FSCLG_SURF_B
+#define FSCLG_SURF_B 4  // alphas per wave item (1: no sharing, the A/B build)
+#endif
+constexpr int SURF_B = FSCLG_SURF_B;
+constexpr int SURF_WAVES = 8;       // waves per workgroup
+constexpr int SURF_CH = 16;         // positions per chunk at most
+constexpr int SURF_MAX_LA = 64;     // alphas per list at most
+static_assert(SURF_B >= 1 && SURF_B <= SURF_MAX_LA, "alphas per item");
+struct SurfChunk {
+  int32_t chr, start_pos, step, count;  // positions start_pos + k * step, k < count <= SURF_CH
+  int32_t out0, run, pad[2];            // the chunk's first position among all; its run (the alpha list)
+};
+struct SurfSmem {
+  Pt pt[SURF_CH];
+  double sm[SURF_CH][SURF_MAX_LA];
+  uint32_t len[SURF_CH][SURF_MAX_LA];  // terms of each walk
+};
+
+// snp_likelihood at log(alpha d) = x for a site of device row r: term_dev's expression
+template <class SM>
+__device__ __forceinline__ double surf_term(double x, uint32_t r, const SM& S, const Params& P) {
+  const int iv = interval_of<false>(x, S, P);
+  double2 a, b;
+  coef_fetch<false>(r, iv, S, P, a, b);
+  const double y = x * (a.x * x * x + a.y * x + b.x) + b.y;
+  return y - null_of<false>(r, S, P);
+}
+
+// one item: the walks of nb <= SURF_B alphas la[0] < la[1] < ... at one position, by one wave
+__device__ __forceinline__ void surface_block(SurfSmem& S, const Params& P, int pi, const double* __restrict__ lap,
+                                              int k0, int nb, int lane) {
+  const Pt& pt = S.pt[pi];
+  const int near = pt.nearest;
+  const uint32_t usweep = (uint32_t)pt.sweep ^ POS_BIAS;
+  double la[SURF_B], acc[SURF_B];
+  uint32_t len[SURF_B];
+  bool alive[SURF_B];
+  const double lt0 = logt_dev(absdist(P.pr[phys(near)].x, usweep), P.logt3);
+#pragma unroll
+  for (int b = 0; b < SURF_B; b++) {
+    la[b] = lap[k0 + min(b, nb - 1)];
+    acc[b] = pt.N;
+    len[b] = 0;
+    alive[b] = b < nb && !(lt0 + la[b] > LOG_AD_MAX);  // the nearest SNP outside: an empty walk
+  }
+  if (alive[0]) {  // (la[0] is the block's smallest: no walk of the block otherwise)
+    const double la0 = la[0];
+    auto outside = [&](int i) { return logt_dev(absdist(P.pr[phys(i)].x, usweep), P.logt3) + la0 > LOG_AD_MAX; };
+    const int e = group_search<64>(pt.wstart - 1, near, lane, [&](int m) { return outside(m); });
+    const int nl = near - e;
+    const bool ok1 = near + 1 <= pt.wend && !outside(near + 1);
+    const int f = group_search<64>(ok1 ? near + 1 : 0, ok1 ? pt.wend + 1 : 1, lane, [&](int m) { return !outside(m); });
+    const int nr = ok1 ? f - 1 - near : 0;
+    // one trip: site i of this lane (valid: inside the smallest alpha's walk)
+    auto trip = [&](int i, bool valid) {
+      uint2 s = make_uint2(usweep, 0u);
+      double lt = 0.0;
+      if (valid) {
+        s = P.pr[phys(i)];
+        lt = logt_dev(absdist(s.x, usweep), P.logt3);
+      }
+#pragma unroll
+      for (int b = 0; b < SURF_B; b++) {
+        if (!alive[b]) continue;  // (wave-uniform)
+        const double x = lt + la[b];
+        const bool in = valid && !(x > LOG_AD_MAX);
+        const unsigned long long m = __ballot(in);
+        if (m == 0ull) continue;
+        double t = 0.0;
+        if (in) t = surf_term(x, s.y, S, P);
+        const int lim = __popcll(m);  // the lanes inside are the first lim
+        acc[b] = exact_chunk_add(acc[b], t, lim);
+        len[b] += (uint32_t)lim;
+      }
+    };
+    for (int j0 = 0; j0 <= nl; j0 += 64) trip(near - (j0 + lane), j0 + lane <= nl);
+    for (int j0 = 1; j0 <= nr; j0 += 64) trip(near + j0 + lane, j0 + lane <= nr);
+  }
+#pragma unroll
+  for (int b = 0; b < SURF_B; b++)
+    if (lane == b && b < nb) { S.sm[pi][k0 + b] = acc[b]; S.len[pi][k0 + b] = len[b]; }
+}
+
+__global__ void __launch_bounds__(64 * SURF_WAVES)
+surface_kernel(Params P, const SurfChunk* __restrict__ chunks, const double* __restrict__ la_all, int n_la,
+               double* __restrict__ sm_out) {
+  __shared__ SurfSmem S;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int k = (int)blockIdx.x;
+  if (k >= P.n_cells) return;
+  const SurfChunk c = chunks[k];
+  for (int i = wave; i < c.count; i += SURF_WAVES) init_point_wave(S.pt[i], c.chr, c.start_pos + i * c.step, P, lane);
+  __syncthreads();
+  const double* __restrict__ lap = la_all + (size_t)c.run * (size_t)n_la;
+  const int nblk = (n_la + SURF_B - 1) / SURF_B;
+  for (int it = wave; it < c.count * nblk; it += SURF_WAVES) {
+    const int pi = it / nblk, k0 = (it - pi * nblk) * SURF_B;
+    surface_block(S, P, pi, lap, k0, min(SURF_B, n_la - k0), lane);
+  }
+  __syncthreads();
+  for (int t = tid; t < c.count * n_la; t += 64 * SURF_WAVES) {  // consecutive lanes, consecutive doubles
+    const int pi = t / n_la;
+    sm_out[(size_t)c.out0 * (size_t)n_la + (size_t)t] = S.sm[pi][t - pi * n_la];
+  }
+  if (tid < c.count) {  // one store per point (P.out is host memory: no read-modify-write)
+    Pt& pt = S.pt[tid];
+    double best = -1.7976931348623157e308, bla = LOG_AD_MAX;
+    unsigned long long terms = 0;
+    for (int j = 0; j < n_la; j++) {
+      const double v = S.sm[tid][j];
+      if (v > best) { best = v; bla = lap[j]; }
+      terms += S.len[tid][j];
+    }
+    pt.la = bla; pt.sm = best; pt.clr = 2.0 * (best - pt.N);
+    fsclg_point_t o;
+    write_point(o, pt);
+    o.cost = (uint32_t)min(terms >> 10, 0xFFFFFFFFull);  // the position's terms / 1024
+    P.out[c.out0 + tid] = o;
+    atomicAdd(&P.stats[0], terms);                                   // the device counters, as any launch:
+    atomicAdd(&P.stats[1], (unsigned long long)pt.n_snps);           // terms, null-sum elements, walks
+    atomicAdd(&P.stats[2], (unsigned long long)n_la);
+  }
+}
+
 // ------------------------------------------------------------ sweep-model sampler
 // One replicate of derived counts under the model (fsclg_sample_submit; the idea of the reference's
 // sm-sample.c:164-212).  One wave per site, SAMPLE_WAVES sites per workgroup.  The site's set-up --
@@ -3452,7 +3599,7 @@ struct Slot {
 };
 
 // what a batch holds between a submit and its wait
-enum BatchKind { BK_NONE, BK_SEARCH, BK_PROFILE, BK_CELLMAX, BK_CURVE, BK_SITES, BK_SAMPLE, BK_TAIL };
+enum BatchKind { BK_NONE, BK_SEARCH, BK_PROFILE, BK_CELLMAX, BK_CURVE, BK_SITES, BK_SAMPLE, BK_TAIL, BK_SURFACE };
 
 // one call of any kind in flight (a submit / wait pair: search, profile, cell maxima, curves, site
 // terms, sample, tail fit): its stream and events, the device and pinned host buffers of each kind,
@@ -3532,6 +3679,14 @@ struct Batch {
   size_t dtsamp_cap = 0;
   int tl_n = 0;                     // points of the submitted tail call
   double tl_ms = 0.0;               // kernel time of the batch's last tail call
+  // fsclg_surface_submit: the chunks and the runs' alpha lists (pinned, read by the kernel), the values
+  // (pinned, written by the kernel; the points are p_out)
+  SurfChunk* p_sfchunks = nullptr;
+  double* p_sfla = nullptr;
+  double* p_sfsm = nullptr;
+  int sfchunk_cap = 0, sfla_cap = 0, sfsm_cap = 0;
+  int sf_n = 0, sf_nla = 0;         // positions and alphas per position of the submitted surfaces
+  double sf_ms = 0.0;               // kernel time of the batch's last surface launch
 };
 
 struct fsclg_ctx {
@@ -3748,7 +3903,8 @@ int fsclg_close(fsclg_ctx* c) {
     for (void* p : {(void*)B.p_cells, (void*)B.p_out, (void*)B.p_epos, (void*)B.p_cell_ep, (void*)B.p_ctrace,
                     (void*)B.p_cmchunks, (void*)B.p_curve, (void*)B.p_sreq, (void*)B.p_shdr, (void*)B.p_stasks,
                     (void*)B.p_sterms, (void*)B.p_sdepth, (void*)B.p_sfreq, (void*)B.p_ssweeps,
-                    (void*)B.p_tsamples, (void*)B.p_toff, (void*)B.p_tcnt, (void*)B.p_tx0, (void*)B.p_tout})
+                    (void*)B.p_tsamples, (void*)B.p_toff, (void*)B.p_tcnt, (void*)B.p_tx0, (void*)B.p_tout,
+                    (void*)B.p_sfchunks, (void*)B.p_sfla, (void*)B.p_sfsm})
       if (p) hipHostFree(p);
     hipEventDestroy(B.ev0);
     hipEventDestroy(B.ev1);
@@ -5108,7 +5264,7 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
       "batch not submitted", nullptr, "the batch holds a profile (fsclg_profile_wait)",
       "the batch holds cell maxima (fsclg_cellmax_wait)", "the batch holds curves (fsclg_curve_wait)",
       "the batch holds site terms (fsclg_sites_wait)", "the batch holds a sample (fsclg_sample_wait)",
-      "the batch holds a tail fit (fsclg_tail_wait)"};
+      "the batch holds a tail fit (fsclg_tail_wait)", "the batch holds surfaces (fsclg_surface_wait)"};
   if (B.holds != BK_SEARCH) return set_err(FSCLG_E_STATE, other[B.holds]);
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
@@ -5532,6 +5688,89 @@ unsigned long long fsclg_curve_forced(fsclg_ctx* c) {
   if (!c || hipSetDevice(c->device) != hipSuccess) return 0;
   if (hipMemcpy(&h, c->d_stats + 24, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) return 0;
   return h;
+}
+
+// ------------------------------------------------------------ likelihood surface (host side)
+// The runs' position-by-alpha surfaces on the rows a slot holds: fsclg_cellmax_submit's checks, slot and
+// window null sums (one covering cell per run); surface_kernel stores n_la values and one point per
+// position.  A chunk holds as many positions as give its workgroup about two items per wave (the result
+// does not depend on it).
+int fsclg_surface_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* runs, int n_runs, const double* la,
+                         int n_la, int eval_range) {
+  if (!c || (!runs && n_runs) || n_runs < 0 || eval_range < 0) return set_err(FSCLG_E_ARG, "runs");
+  if (batch < 0 || batch >= NBATCH || slot < 0 || slot >= NSLOT) return set_err(FSCLG_E_ARG, "batch/slot");
+  if (n_la < 1 || n_la > SURF_MAX_LA) return set_err(FSCLG_E_ARG, "alphas per position outside [1, 64]");
+  if (!la && n_runs) return set_err(FSCLG_E_ARG, "alpha lists");
+  if (!c->d_pr0 || !c->d_coef) return set_err(FSCLG_E_STATE, "tables/snps not set");
+  Batch& B = c->batch[batch];
+  if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
+  for (long long i = 0; i < (long long)n_runs * n_la; i++) {
+    // interval_of needs log(alpha d) >= LOG_AD_MIN; above LOG_AD_MAX every walk is empty
+    if (!(la[i] >= LOG_AD_MIN && la[i] <= LOG_AD_MAX)) return set_err(FSCLG_E_ARG, "log alpha outside [LOG_AD_MIN, LOG_AD_MAX]");
+    if (i % n_la && !(la[i] > la[i - 1])) return set_err(FSCLG_E_ARG, "alpha list not ascending");
+  }
+  const int nblk = (n_la + SURF_B - 1) / SURF_B;
+  const int CH = std::max(1, std::min(SURF_CH, (2 * SURF_WAVES + nblk - 1) / nblk));
+  long long total, nchunk;
+  int r;
+  if ((r = validate_runs(c, runs, n_runs, eval_range, CH, &total, &nchunk))) return r;
+  if (total * n_la > 0x7FFFFFFFll / (long long)sizeof(double) || total > 0x7FFFFFFFll / (long long)sizeof(fsclg_point_t))
+    return set_err(FSCLG_E_ARG, "too many surface cells");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  B.n_cells = 0; B.nu = (int)nchunk; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
+  B.eval_range = eval_range; B.bp_resl = 0; B.sf_ms = 0.0; B.sf_n = (int)total; B.sf_nla = n_la;
+  if (total > 0) {
+    std::vector<fsclg_cell_t> cover;
+    for (int i = 0; i < n_runs; i++)
+      if (runs[i].count > 0)
+        cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos, runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
+    if ((r = cover_windows(c, B, slot, cover, eval_range))) return r;
+    if ((r = ensure_io(B, (int)total))) return r;
+    if ((r = ensure_pinned(&B.p_sfchunks, &B.sfchunk_cap, (int)nchunk))) return r;
+    if ((r = ensure_pinned(&B.p_sfla, &B.sfla_cap, n_runs * n_la))) return r;
+    if ((r = ensure_pinned(&B.p_sfsm, &B.sfsm_cap, (int)(total * n_la)))) return r;
+    memcpy(B.p_sfla, la, sizeof(double) * (size_t)n_runs * (size_t)n_la);
+    int nc = 0, o = 0;
+    for (int i = 0; i < n_runs; i++)
+      for (int j = 0; j < runs[i].count; j += CH) {
+        const int cnt = std::min(CH, runs[i].count - j);
+        B.p_sfchunks[nc++] = SurfChunk{runs[i].chr, runs[i].start_pos + j * runs[i].step, runs[i].step, cnt, o, i, {0, 0}};
+        o += cnt;
+      }
+    HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
+    Params P = make_params(c, B, slot, nc, 3, eval_range, 0);
+    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
+    hipLaunchKernelGGL(surface_kernel, dim3(nc), dim3(64 * SURF_WAVES), 0, B.stream, P, (const SurfChunk*)B.p_sfchunks,
+                       (const double*)B.p_sfla, n_la, B.p_sfsm);
+    HIPCHK(hipGetLastError(), "launch surface_kernel");
+    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+  }
+  B.holds = BK_SURFACE;
+  c->slot[slot].users++;
+  return FSCLG_OK;
+}
+
+int fsclg_surface_wait(fsclg_ctx* c, int batch, fsclg_point_t* pts, double* sm) {
+  if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
+  Batch& B = c->batch[batch];
+  if (B.holds != BK_SURFACE) return set_err(FSCLG_E_STATE, "no surfaces submitted on the batch");
+  if ((!pts || !sm) && B.sf_n) return set_err(FSCLG_E_ARG, "out");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  B.holds = BK_NONE;
+  c->slot[B.slot].users--;
+  const int n = B.sf_n;
+  if (n == 0) return FSCLG_OK;
+  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  memcpy(pts, B.p_out, sizeof(fsclg_point_t) * (size_t)n);
+  memcpy(sm, B.p_sfsm, sizeof(double) * (size_t)n * (size_t)B.sf_nla);
+  int r, flags = 0;
+  if ((r = batch_time(c, B, 1, &B.sf_ms))) return r;
+  for (int i = 0; i < n; i++) flags |= pts[i].flags;
+  return flags_err(flags);
+}
+
+double fsclg_surface_last_ms(fsclg_ctx* c, int batch) {
+  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].sf_ms : 0.0;
 }
 
 // ------------------------------------------------------------ per-site terms (host side)

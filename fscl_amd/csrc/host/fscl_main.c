@@ -113,6 +113,9 @@ int main(int argc, char **argv) {
   strlist_t simulate_sweep = {NULL, 0}, bootstrap_sweep = {NULL, 0};
   int simulate_rep = 0, bootstrap_reps = 100, bootstrap_window = -1, bootstrap_top = 3, need_tables;
   char *tail_fname = NULL, *tail_df_str = NULL;
+  char *surface_fname = NULL, *surface_alphas = NULL;
+  int surface_top = 3, surface_halfwidth = -1, surface_step = -1, surface_n = 33;
+  double surface_drop = 2.0, surface_lo = LOG_AD_MIN, surface_hi = LOG_AD_MAX;
   int tail_df = 2, tail_min_n = 20;
   scan_t *s;
   double **fsp;
@@ -174,6 +177,16 @@ int main(int argc, char **argv) {
       {0, "tail-file", &tail_fname, T_STR, "after the permutation test, write every scan point's p-value projected from a noncentral "
                                            "chi-square fit of its null CLRs (below 1/n-permute) to this file"},
       {0, "tail-df", &tail_df_str, T_STR, "degrees of freedom of the --tail-file fit: an even integer >= 2 (default 2)"},
+      {0, "surface-file", &surface_fname, T_STR, "write the position-by-alpha likelihood surface around the scan points of greatest "
+                                                 "CLR, and a region summary per point, to this file"},
+      {0, "surface-top", &surface_top, T_INT, "--surface-file takes this many points of greatest CLR (default 3)"},
+      {0, "surface-halfwidth", &surface_halfwidth, T_INT, "half-width in bp of a surface's positions around its point (default: the -G spacing)"},
+      {0, "surface-step", &surface_step, T_INT, "spacing in bp of a surface's positions (default: the -g spacing; at least 1)"},
+      {0, "surface-alphas", &surface_alphas, T_STR, "LO:HI:N, the surface's alpha grid: natural-log alpha endpoints within [-20, 4] and a "
+                                                    "count N <= 63 (default -20:4:33, steps of 0.75); the point's fitted alpha is added"},
+      {0, "surface-drop", &surface_drop, T_DBL, "log-likelihood drop of the region in --surface-file (default 2.0, as --alpha-drop; a joint "
+                                                "two-parameter 95 % region under the chi-square reading would be about 3.0; descriptive: "
+                                                "the likelihood is composite)"},
       {0, "tail-min-n", &tail_min_n, T_INT, "--tail-file fits a point with at least this many positive null CLRs (default 20)"},
       {0, NULL, NULL, 0, NULL}};
 
@@ -315,6 +328,23 @@ int main(int argc, char **argv) {
     stop = 1;
   }
   if (tail_fname && tail_min_n < 1) { logmsg(MSG_ERROR, "Error: --tail-min-n must be >= 1.\n"); stop = 1; }
+  if (surface_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --surface-file needs the scan (not with --no-scan).\n"); stop = 1; }
+  if (surface_top < 0) { logmsg(MSG_ERROR, "Error: --surface-top must be >= 0.\n"); stop = 1; }
+  if (surface_halfwidth < 0) surface_halfwidth = surface_halfwidth == -1 ? large_grid_sp : -2;
+  if (surface_halfwidth == -2) { logmsg(MSG_ERROR, "Error: --surface-halfwidth must be >= 0.\n"); stop = 1; }
+  if (surface_step == -1) surface_step = surface_fname ? small_grid_sp : 1;
+  if (surface_step < 1) { logmsg(MSG_ERROR, "Error: --surface-step must be at least 1.\n"); stop = 1; }
+  if (!(surface_drop >= 0.0)) { logmsg(MSG_ERROR, "Error: --surface-drop must be >= 0.\n"); stop = 1; }
+  if (surface_alphas) {
+    char tail_c = 0;
+    double probe[FSCL_AMD_SURFACE_MAX_LA];
+    if (sscanf(surface_alphas, "%lf:%lf:%d%c", &surface_lo, &surface_hi, &surface_n, &tail_c) != 3 ||
+        fscl_amd_surface_alphas(surface_lo, surface_hi, surface_n, NAN, probe) < 1) {
+      logmsg(MSG_ERROR, "Error: --surface-alphas must be LO:HI:N with -20 <= LO <= HI <= 4 (natural-log alpha), 1 <= N <= 63, "
+                        "and LO < HI unless N is 1 (not \"%s\").\n", surface_alphas);
+      stop = 1;
+    }
+  }
   if (permute_seed && !(permute_mode && !strcmp(permute_mode, "throughput")))
     logmsg(MSG_WARN, "Warning: --permute-seed is used only with --permute-mode=throughput.\n");
   if (stop) {
@@ -419,6 +449,18 @@ int main(int argc, char **argv) {
       logmsg(MSG_STATUS, "Site terms: %d walks, %llu terms, kernel %.3f ms\n", st.n, (unsigned long long)st.n_terms,
              fscl_amd_sites_last_ms());
       fscl_amd_sites_free(&st);
+    }
+    if (surface_fname && !(ws && rk && atoi(ws) > 1 && atoi(rk) != 0)) {
+      /* the likelihood surfaces around the points of greatest CLR, of the data as loaded (rank 0 alone); no rand() draw */
+      fscl_amd_surfaces_t sf;
+      const int r = fscl_amd_scan_point_surfaces(s, sm, eval_range, surface_top, surface_halfwidth, surface_step, surface_lo,
+                                                 surface_hi, surface_n, &sf);
+      if (r != 0) logmsg(MSG_FATAL, "fscl: likelihood surfaces failed (code %d)", r);
+      if (fscl_amd_surface_output(surface_fname, s, &sf, surface_drop, prepend_label) != 0)
+        logmsg(MSG_FATAL, "fscl: cannot write %s", surface_fname);
+      logmsg(MSG_STATUS, "Surfaces: %d points, %llu cells, %llu terms, kernel %.3f ms\n", sf.n, (unsigned long long)sf.n_cells,
+             sf.n_terms, fscl_amd_surface_last_ms());
+      fscl_amd_surfaces_free(&sf);
     }
     if (dont_scan) {
       /* nothing to test or to write */

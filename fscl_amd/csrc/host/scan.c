@@ -2743,6 +2743,169 @@ void fscl_amd_curve_output(const char *fname, const scan_t *s, const fscl_amd_cu
   if (fname) fclose(f);
 }
 
+/* ------------------------------------------------------ likelihood surfaces
+   The position-by-alpha surfaces of requests (fsclg_surface_submit), on the data as loaded.  A
+   device call takes lists of one length, so the requests are evaluated one list length after
+   another (the top-K helper's lists differ by one value at most); within a length the local
+   devices take contiguous shares balanced by window size x cells, every device is submitted to
+   before the first is waited for. */
+static double g_surface_ms;
+double fscl_amd_surface_last_ms(void) { return g_surface_ms; }
+
+static unsigned long long dev_terms(int l) {
+  fsclg_stats_t st;
+  return fsclg_get_stats(D.ctx[l], &st) == FSCLG_OK ? st.n_terms : 0ull;
+}
+
+/* a list fsclg_surface_submit takes: 1 .. 64 values in [LOG_AD_MIN, LOG_AD_MAX], strictly ascending */
+static int surface_list_ok(const double *la, int n) {
+  int k;
+  if (n < 1 || n > FSCL_AMD_SURFACE_MAX_LA) return 0;
+  for (k = 0; k < n; k++)
+    if (!(la[k] >= LOG_AD_MIN && la[k] <= LOG_AD_MAX) || (k && !(la[k] > la[k - 1]))) return 0;
+  return 1;
+}
+
+int fscl_amd_scan_surface(scan_t *s, sm_ptable_t *sm, int eval_range, const fscl_amd_surface_req_t *req, int n,
+                          fscl_amd_surfaces_t *out) {
+  fsclg_run_t *runs;
+  double *cost, *la, dev_ms[FH_MAX_DEV];
+  int *idx, lo[FH_MAX_DEV], hi[FH_MAX_DEV], i, j, l, k, m, nla, r = FSCLG_OK;
+  uint64_t po = 0, co = 0;
+  if (!s || !sm || !out || n < 0 || (n && !req)) return FSCLG_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (D.world > 1 && D.rank != 0) return FSCLG_OK; /* rank 0 alone evaluates, as the curves */
+  runs = fh_malloc(sizeof(fsclg_run_t) * (n ? n : 1), "surface runs");
+  out->hdr = fh_calloc(n ? n : 1, sizeof *out->hdr, "surface headers");
+  for (i = 0; i < n; i++) {
+    fscl_amd_surface_hdr_t *h = out->hdr + i;
+    if (!surface_list_ok(req[i].la, req[i].n_la) || fscl_amd_surface_run(s, req + i, runs + i) != 0) {
+      free(runs); fscl_amd_surfaces_free(out);
+      return FSCLG_E_ARG;
+    }
+    h->chr = req[i].chr; h->centre_pos = req[i].centre_pos; h->halfwidth = req[i].halfwidth; h->step = req[i].step;
+    h->n_la = req[i].n_la; h->point = req[i].point; h->start_pos = runs[i].start_pos; h->n_pos = runs[i].count;
+    memcpy(h->la, req[i].la, sizeof(double) * (size_t)h->n_la);
+    h->pos_off = po; h->cell_off = co;
+    po += (uint64_t)h->n_pos; co += (uint64_t)h->n_pos * (uint64_t)h->n_la;
+  }
+  prepare(s, sm); /* (the requests are checked before the first device call) */
+  out->n = n; out->n_pos = (size_t)po; out->n_cells = (size_t)co;
+  out->pts = fh_calloc(po ? po : 1, sizeof *out->pts, "surface points");
+  out->sm = fh_calloc(co ? co : 1, sizeof *out->sm, "surface values");
+  set_original_rows();
+  g_surface_ms = 0.;
+  for (l = 0; l < FH_MAX_DEV; l++) dev_ms[l] = 0.;
+  idx = fh_malloc(sizeof(int) * (n ? n : 1), "surface requests");
+  cost = fh_malloc(sizeof(double) * (n ? n : 1), "cost");
+  for (nla = 1; nla <= FSCL_AMD_SURFACE_MAX_LA && r == FSCLG_OK; nla++) {
+    fsclg_run_t *gr;
+    fsclg_point_t *gp;
+    double *gs;
+    size_t np = 0, off;
+    for (i = 0, m = 0; i < n; i++)
+      if (req[i].n_la == nla) { idx[m] = i; cost[m] = window_cost(req[i].chr, eval_range) * runs[i].count * nla; np += (size_t)runs[i].count; m++; }
+    if (m == 0) continue;
+    gr = fh_malloc(sizeof *gr * (size_t)m, "surface runs");
+    la = fh_malloc(sizeof(double) * (size_t)m * nla, "surface alphas");
+    gp = fh_malloc(sizeof *gp * (np ? np : 1), "surface points");
+    gs = fh_malloc(sizeof(double) * (np ? np : 1) * nla, "surface values");
+    for (j = 0; j < m; j++) { gr[j] = runs[idx[j]]; memcpy(la + (size_t)j * nla, req[idx[j]].la, sizeof(double) * (size_t)nla); }
+    for (l = 0; l < D.n_dev; l++) {
+      if (D.n_dev <= 1) { lo[l] = 0; hi[l] = m; }
+      else fscl_amd_partition(cost, m, l, D.n_dev, &lo[l], &hi[l]);
+    }
+    for (l = 0; l < D.n_dev; l++) out->n_terms -= dev_terms(l);
+    for (l = 0; l < D.n_dev && r == FSCLG_OK; l++) {
+      DBG("surfaces: device %d, %d alphas, requests [%d, %d)\n", D.dev[l], nla, lo[l], hi[l]);
+      r = fsclg_surface_submit(D.ctx[l], 0, 0, gr + lo[l], hi[l] - lo[l], la + (size_t)lo[l] * nla, nla, eval_range);
+    }
+    for (k = 0; k < l; k++) {
+      int rw;
+      if (k == l - 1 && r != FSCLG_OK) break; /* the submit that failed left nothing to wait for */
+      for (j = 0, off = 0; j < lo[k]; j++) off += (size_t)gr[j].count;
+      rw = fsclg_surface_wait(D.ctx[k], 0, gp + off, gs + off * nla);
+      dev_ms[k] += fsclg_surface_last_ms(D.ctx[k], 0);
+      if (r == FSCLG_OK) r = rw;
+    }
+    for (l = 0; l < D.n_dev; l++) out->n_terms += dev_terms(l);
+    for (j = 0, off = 0; j < m && r == FSCLG_OK; j++) { /* back into request order */
+      const fscl_amd_surface_hdr_t *h = out->hdr + idx[j];
+      memcpy(out->pts + h->pos_off, gp + off, sizeof *gp * (size_t)h->n_pos);
+      memcpy(out->sm + h->cell_off, gs + off * nla, sizeof(double) * (size_t)h->n_pos * nla);
+      off += (size_t)h->n_pos;
+    }
+    free(gr); free(la); free(gp); free(gs);
+  }
+  for (l = 0; l < D.n_dev; l++)
+    if (dev_ms[l] > g_surface_ms) g_surface_ms = dev_ms[l]; /* the devices run side by side */
+  free(runs); free(idx); free(cost);
+  if (r != FSCLG_OK) fscl_amd_surfaces_free(out);
+  return r;
+}
+
+int fscl_amd_scan_point_surfaces(scan_t *s, sm_ptable_t *sm, int eval_range, int top, int halfwidth, int step,
+                                 double la_lo, double la_hi, int n_grid, fscl_amd_surfaces_t *out) {
+  fscl_amd_surface_req_t *req;
+  char *used;
+  int n = 0, i, k, r;
+  if (!s || !sm || !out || (!s->scan_pts && s->n_scan_pts) || s->n_scan_pts < 0 || top < 0 || halfwidth < 0 || step < 1)
+    return FSCLG_E_ARG;
+  memset(out, 0, sizeof *out);
+  req = fh_calloc(top ? top : 1, sizeof *req, "surface requests");
+  used = fh_calloc(s->n_scan_pts ? s->n_scan_pts : 1, 1, "surface requests");
+  while (n < top) { /* descending CLR, as the --bootstrap-top points */
+    int best = -1;
+    for (i = 0; i < s->n_scan_pts; i++)
+      if (!used[i] && s->scan_pts[i].clr == s->scan_pts[i].clr && (best < 0 || s->scan_pts[i].clr > s->scan_pts[best].clr))
+        best = i;
+    if (best < 0) break;
+    used[best] = 1;
+    for (k = 0; k < n; k++) {
+      long long d = (long long)s->scan_pts[best].sweep_pos - req[k].centre_pos;
+      if (req[k].chr == s->scan_pts[best].chr && (d < 0 ? -d : d) <= halfwidth) break;
+    }
+    if (k < n) continue;
+    req[n].chr = s->scan_pts[best].chr; req[n].centre_pos = s->scan_pts[best].sweep_pos;
+    req[n].halfwidth = halfwidth; req[n].step = step; req[n].point = best;
+    req[n].n_la = fscl_amd_surface_alphas(la_lo, la_hi, n_grid, s->scan_pts[best].lalpha, req[n].la);
+    if (req[n].n_la < 1) { free(req); free(used); return FSCLG_E_ARG; }
+    n++;
+  }
+  free(used);
+  r = fscl_amd_scan_surface(s, sm, eval_range, req, n, out);
+  free(req);
+  return r;
+}
+
+/* the test handle of fsclg_surface_submit / fsclg_surface_wait on the first device, for any runs
+   and batch: on the uploaded rows (rows NULL: slot 0) or on `rows` (slot 1), as fscl_amd_cellmax_runs */
+int fscl_amd_surface_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int n_runs, const double *la, int n_la,
+                          int eval_range, const uint32_t *rows, int batch, fsclg_point_t *pts, double *smv) {
+  int r, slot = 0;
+  if (!s || !sm || (!runs && n_runs) || n_runs < 0) return FSCLG_E_ARG;
+  prepare(s, sm);
+  g_surface_ms = 0.;
+  if (rows) {
+    double *nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
+    int i;
+    for (i = 0; i < s->n_snps; i++)
+      if (rows[i] >= (uint32_t)D.rm.n_dev_rows) { free(nul); return FSCLG_E_ARG; }
+    chr_null_sums_32(rows, nul);
+    slot = 1;
+    r = fsclg_slot_set_rows(D.ctx[0], slot, rows, nul);
+    free(nul);
+    if (r != FSCLG_OK) return r;
+  } else {
+    set_original_rows();
+  }
+  r = fsclg_surface_submit(D.ctx[0], batch, slot, runs, n_runs, la, n_la, eval_range);
+  if (r != FSCLG_OK) return r;
+  r = fsclg_surface_wait(D.ctx[0], batch, pts, smv);
+  g_surface_ms = fsclg_surface_last_ms(D.ctx[0], batch);
+  return r;
+}
+
 /* ------------------------------------------------------ per-site likelihood terms
    The terms of single sm_likelihood walks (fsclg_sites_submit), on the data as loaded.  The local
    devices take contiguous shares of the requests balanced by window size; every device is

@@ -377,6 +377,105 @@ int fscl_amd_curve_runs(scan_t *scan_obj, sm_ptable_t *sm_p, const fsclg_run_t *
 double fscl_amd_curve_last_ms(void);
 unsigned long long fscl_amd_curve_forced(void);
 
+/* ---- position-by-alpha likelihood surfaces (--surface-file) --------------------------
+   The surface whose position axis the profile gives (alpha maximised away) and whose alpha axis
+   the curve gives (at one position): the composite likelihood at every position of a small grid
+   around a centre, for every log alpha of one list, with no alpha search (fsclg_surface_submit).
+
+   A request is (chromosome index, centre position, half-width bp, step bp, alpha list): its
+   positions are centre + k * step for |k| <= halfwidth / step, those outside the chromosome's span
+   [chr_limits.start_pos, chr_limits.bp_length] -- the span the profile's grid covers -- left out
+   (fscl_amd_surface_run gives them as one run; -1 for a bad chromosome, step < 1 or halfwidth < 0).
+   la[0 .. n_la) is strictly ascending, 1 <= n_la <= 64, each value in [LOG_AD_MIN, LOG_AD_MAX] =
+   [-20, 4].  fscl_amd_surface_alphas builds such a list: the grid lo + i (hi - lo) / (n - 1), i < n
+   (n = 1: lo = hi alone), its last value hi itself, with `fitted` inserted in order -- at either
+   end when it lies outside [lo, hi]; not added when it equals a grid value, is NaN or lies outside
+   [-20, 4]; returns the length (n or n + 1), or -1 for n outside [1, 63], endpoints outside
+   [-20, 4], lo > hi, lo == hi with n > 1, or a grid whose neighbours are equal in double.
+
+   A result owns its arrays (fscl_amd_surfaces_free; a zeroed one is empty).  Surface i has
+   hdr[i]: its request, the run evaluated (start_pos, step, n_pos), the scan point it was centred
+   on (point, -1: none), and where its n_pos points and n_pos * n_la values (position-major) start
+   in pts[] and sm[].  pts and sm are fsclg_surface_wait's: sm[cell_off + p * n_la + k] is what
+   sm_likelihood returns for la[k] at the p-th position, bit for bit; pts[pos_off + p] is the
+   position's point with the row's first strict maximum.  n_terms: the walks' terms.
+
+   fscl_amd_scan_surface: the surfaces of n requests, on the data as loaded (also after
+   scan_permute), on the device context scan_chromosome uses; several local devices take
+   contiguous shares of the requests balanced by window size x cells (identical results); with
+   several ranks, rank 0 alone evaluates (the others return FSCLG_OK and an empty result).  Returns
+   a fsclg status code (FSCLG_E_ARG: a NULL argument, n < 0, a request fscl_amd_surface_run or the
+   device refuses).  fscl_amd_scan_point_surfaces: the `top` scan points of greatest CLR (ties in
+   scan order, a NaN never; a point within halfwidth bp of one already chosen on its chromosome is
+   skipped, as --bootstrap-top does), in that order, each centred on its sweep_pos with
+   fscl_amd_surface_alphas(la_lo, la_hi, n_grid, its fitted lalpha).
+
+   fscl_amd_surface_region (host only), on sm[n_pos][n_la] and the positions' null sums: V = sm -
+   null_logl per cell; M its maximum, the first in position order, then alpha order (max_ipos,
+   max_ila, max_v = M); the joint region is the 4-connected component of the cells with V >= M -
+   drop that holds the argmax (n_region cells; mark, if not NULL, gets 2 at the argmax, 1 inside the
+   region, 0 elsewhere); the position interval [ipos_lo, ipos_hi] is the connected run, around the
+   argmax position, of positions whose row maximum is >= M - drop, the alpha interval the same over
+   columns; an open_* flag is 1 where its interval reaches the edge of the evaluated grid.  A NaN
+   cell is never in a region.  Returns 1; 0 when every cell is NaN (indices -1, max_v NaN, flags
+   0); -1 for a NULL array, an empty grid or a drop that is negative or NaN.  With drop = 2 the
+   intervals match --alpha-file's; a joint two-parameter 95 % region under the chi-square reading
+   would be about 3.0.  The likelihood is a COMPOSITE one (sites are not independent), so the
+   region describes the surface's shape and is not a calibrated confidence region.
+
+   fscl_amd_surface_output (fname NULL: stdout; 0, or -1 if the file cannot be opened or a header
+   does not fit the arrays), per surface one row per cell, position-major:
+     [label TAB] chromosome TAB centre_pos TAB pos TAB alpha (%1.3e) TAB 2 * (sm - null_logl) (%1.2f) TAB mark
+   (pos: the point's sweep_pos; mark * at the argmax, + inside the joint region, - elsewhere), then
+     [label TAB] chromosome TAB centre_pos TAB summary TAB n_pos TAB n_alpha TAB max_pos TAB max_alpha
+       TAB max_clr TAB pos_lo TAB pos_hi TAB open_pos_lo TAB open_pos_hi TAB alpha_lo TAB alpha_hi
+       TAB open_alpha_lo TAB open_alpha_hi TAB n_region
+   with NA for the seven values and 0 for the flags and n_region when every cell is NaN. */
+#define FSCL_AMD_SURFACE_MAX_LA 64
+typedef struct {
+  int32_t chr, centre_pos, halfwidth, step;
+  int32_t n_la, point;  /* point: the scan point the request is centred on, -1: none */
+  double la[FSCL_AMD_SURFACE_MAX_LA];
+} fscl_amd_surface_req_t;
+typedef struct {
+  int32_t chr, centre_pos, halfwidth, step, n_la, point;
+  int32_t start_pos, n_pos;  /* the run evaluated: start_pos + p * step, p < n_pos */
+  uint64_t pos_off, cell_off;
+  double la[FSCL_AMD_SURFACE_MAX_LA];
+} fscl_amd_surface_hdr_t;
+typedef struct {
+  int n;  /* surfaces */
+  fscl_amd_surface_hdr_t *hdr;
+  fsclg_point_t *pts;
+  double *sm;
+  size_t n_pos, n_cells;
+  unsigned long long n_terms;
+} fscl_amd_surfaces_t;
+typedef struct {
+  int32_t n_pos, n_la, max_ipos, max_ila, ipos_lo, ipos_hi, ila_lo, ila_hi;
+  int32_t open_pos_lo, open_pos_hi, open_la_lo, open_la_hi, n_region, pad;
+  double max_v;
+} fscl_amd_surface_region_t;
+int fscl_amd_surface_alphas(double lo, double hi, int n, double fitted, double *out /* [64] */);
+int fscl_amd_surface_run(const scan_t *scan_obj, const fscl_amd_surface_req_t *req, fsclg_run_t *run);
+int fscl_amd_scan_surface(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, const fscl_amd_surface_req_t *req, int n,
+                          fscl_amd_surfaces_t *out);
+int fscl_amd_scan_point_surfaces(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, int top, int halfwidth, int step,
+                                 double la_lo, double la_hi, int n_grid, fscl_amd_surfaces_t *out);
+void fscl_amd_surfaces_free(fscl_amd_surfaces_t *r);
+int fscl_amd_surface_region(const double *sm, const double *null_logl, int n_pos, int n_la, double drop,
+                            fscl_amd_surface_region_t *out, unsigned char *mark);
+int fscl_amd_surface_output(const char *fname, const scan_t *scan_obj, const fscl_amd_surfaces_t *r, double drop,
+                            const char *prepend_label);
+/* fsclg_surface_submit / fsclg_surface_wait on the first device, for any runs (the device entry's
+   test handle): la holds n_runs lists of n_la values, pts sum(count) points, sm sum(count) * n_la
+   values; rows as for fscl_amd_cellmax_runs, batch any batch of the device (rows NULL: slot 0, else
+   slot 1).  fscl_amd_surface_last_ms: the surface kernel's milliseconds of the last evaluation
+   (the slowest device's, summed over its launches). */
+int fscl_amd_surface_runs(scan_t *scan_obj, sm_ptable_t *sm_p, const fsclg_run_t *runs, int n_runs, const double *la,
+                          int n_la, int eval_range, const uint32_t *rows, int batch, fsclg_point_t *pts, double *sm);
+double fscl_amd_surface_last_ms(void);
+
 /* ---- per-site likelihood terms (--sites-file) --------------------------------------
    The data axis of a sweep position: which sites made this CLR.  A walk is one sm_likelihood
    (sm-search.c:105-150) at (chromosome index, position, log alpha); its header and terms are

@@ -278,6 +278,34 @@ int fsclg_curve_wait(fsclg_ctx *c, int batch, fsclg_curve_t *out);
 double fsclg_curve_last_ms(fsclg_ctx *c, int batch);
 unsigned long long fsclg_curve_forced(fsclg_ctx *c);
 
+/* Likelihood surfaces: the composite likelihood at every position of dense runs for every log alpha
+   of a list, no alpha search.  Run i has its own list la[i * n_la .. (i + 1) * n_la), 1 <= n_la <= 64
+   values, strictly ascending, each finite and in [LOG_AD_MIN, LOG_AD_MAX] = [-20, 4].
+   sm[p * n_la + k] (position-major; p counts the positions in run order, then position order) is what
+   sm_likelihood (sm-search.c:105-150) returns for la[k] at position p: the null sum plus the walk's
+   terms added one by one in walk order -- the nearest SNP, then leftwards, then rightwards, cut where
+   log(alpha d) > LOG_AD_MAX -- bit for bit; an empty walk gives null_logl.  pts[p] is what
+   init_scan_result gives at the position on the slot's rows (the de-collided sweep_pos, nearest_snp,
+   the window, n_snps, null_logl) with (lalpha, sm_logl) the first strict maximum of the position's
+   row in list order from the reference's (LOG_AD_MAX, -DBL_MAX) state -- a row of NaN alone leaves
+   that state -- clr = 2 * (sm_logl - null_logl), and cost the terms / 1024 of the row's walks.  Every
+   byte of pts[0 .. sum(count)) and sm[0 .. sum(count) * n_la) is written.
+   fsclg_surface_submit / fsclg_surface_wait take runs, batches, slots and window null sums exactly as
+   fsclg_curve_submit / fsclg_curve_wait do (any batch and slot; the runs and lists are copied; several
+   devices: submit to all, then wait).  The same input gives the same bytes on every batch and slot
+   and however the kernel chunks the runs (every sum has a fixed order, nothing is accumulated across
+   workgroups).  FSCLG_E_ARG: n_la outside [1, 64], an alpha outside the range, NaN, or not above its
+   predecessor, step < 1, count < 0, a bad chr, batch or slot, a position past the int range;
+   FSCLG_E_STATE: tables or SNPs not uploaded, the batch pending (submit), no surfaces submitted on
+   it (wait).  fsclg_surface_last_ms: the kernel's own time (HIP events) of the batch's last surface
+   launch.  The device counters count the walks (n_terms, n_null, n_walks); the alpha grid of
+   fsclg_set_alpha_grid is not used. */
+int fsclg_surface_submit(fsclg_ctx *c, int batch, int slot, const fsclg_run_t *runs, int n_runs,
+                         const double *la /* [n_runs][n_la] */, int n_la, int eval_range);
+int fsclg_surface_wait(fsclg_ctx *c, int batch, fsclg_point_t *pts /* sum(count) */,
+                       double *sm /* sum(count) * n_la, position-major */);
+double fsclg_surface_last_ms(fsclg_ctx *c, int batch);
+
 /* Per-site likelihood terms: the data axis of a sweep position.  A request is one walk of
    sm_likelihood (sm-search.c:105-150) -- a chromosome, a position and a log alpha, any double
    >= LOG_AD_MIN (-20), not only a value of the alpha grid -- on the rows a slot holds.  Its header's

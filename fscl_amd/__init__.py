@@ -126,6 +126,11 @@ class SurfacesT(C.Structure):  # fscl_amd_surfaces_t
                 ("n_cells", C.c_size_t), ("n_terms", C.c_ulonglong)]
 
 
+class BlocksT(C.Structure):  # fscl_amd_blocks_t
+    _fields_ = [("n", C.c_int), ("hdr", C.c_void_p), ("pts", C.c_void_p), ("bs", C.c_void_p), ("cnt", C.c_void_p),
+                ("n_pos", C.c_size_t), ("n_cells", C.c_size_t), ("n_terms", C.c_ulonglong)]
+
+
 class PointT(C.Structure):  # fsclg_point_t
     _fields_ = [("chr", C.c_int32), ("nearest_snp", C.c_int32), ("sweep_pos", C.c_int32), ("n_snps", C.c_int32),
                 ("window_start", C.c_int32), ("window_end", C.c_int32), ("flags", C.c_int32), ("cost", C.c_uint32),
@@ -173,6 +178,10 @@ EXPORTS = [
     "fscl_amd_surface_alphas", "fscl_amd_surface_run", "fscl_amd_scan_surface", "fscl_amd_scan_point_surfaces",
     "fscl_amd_surfaces_free", "fscl_amd_surface_region", "fscl_amd_surface_output", "fscl_amd_surface_runs",
     "fscl_amd_surface_last_ms",
+    "fsclg_blocks_submit", "fsclg_blocks_wait", "fsclg_blocks_last_ms",
+    "fscl_amd_scan_blocks", "fscl_amd_scan_point_jackknife", "fscl_amd_blocks_free", "fscl_amd_blocks_cap",
+    "fscl_amd_blocks_bound", "fscl_amd_jackknife_combine", "fscl_amd_jackknife_output", "fscl_amd_blocks_runs",
+    "fscl_amd_blocks_last_ms",
 ]
 
 
@@ -279,6 +288,18 @@ def _load() -> C.CDLL:
         "fscl_amd_surface_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(RunT), C.c_int, C.c_void_p, C.c_int, C.c_int,
                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
         "fscl_amd_surface_last_ms": (C.c_double, []),
+        "fscl_amd_scan_blocks": (C.c_int, [P(ScanT), P(SmPtableT), C.c_int, C.c_void_p, C.c_int, C.c_int, P(BlocksT)]),
+        "fscl_amd_scan_point_jackknife": (C.c_int, [P(ScanT), P(SmPtableT), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                    C.c_double, C.c_int, C.c_int, P(BlocksT)]),
+        "fscl_amd_blocks_free": (None, [P(BlocksT)]),
+        "fscl_amd_blocks_cap": (C.c_size_t, []),
+        "fscl_amd_blocks_bound": (C.c_int, [P(ScanT), P(RunT), C.c_int, C.c_int, P(C.c_int), P(C.c_int)]),
+        "fscl_amd_jackknife_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
+        "fscl_amd_jackknife_output": (C.c_int, [C.c_char_p, P(ScanT), P(BlocksT), C.c_char_p]),
+        "fscl_amd_blocks_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(RunT), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "fscl_amd_blocks_last_ms": (C.c_double, []),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -923,6 +944,176 @@ def surface_last_ms() -> float:
     return float(get_lib().fscl_amd_surface_last_ms())
 
 
+BLOCKS_MAX_NB = 1024  # FSCL_AMD_BLOCKS_MAX_NB: blocks per peak at most
+# fscl_amd_blocks_hdr_t: the request, the run evaluated, the blocks (block j holds the sites with
+# b0 + j == pos // block_bp; the edge blocks also what lies beyond) and where the peak's points and cells start
+BLOCKS_DTYPE = np.dtype([("chr", "i4"), ("centre_pos", "i4"), ("halfwidth", "i4"), ("step", "i4"), ("n_la", "i4"),
+                         ("point", "i4"), ("start_pos", "i4"), ("n_pos", "i4"), ("block_bp", "i4"), ("b0", "i4"), ("nb", "i4"),
+                         ("pad", "i4"), ("pos_off", "u8"), ("cell_off", "u8"), ("la", "f8", (SURFACE_MAX_LA,))])
+# fsclg_blocks_t: one run's blocks
+BLOCKSPEC_DTYPE = np.dtype([("block_bp", "i4"), ("b0", "i4"), ("nb", "i4"), ("pad", "i4")])
+# fscl_amd_jack_block_t / fscl_amd_jack_summary_t (fscl_amd_jackknife_combine)
+JACK_BLOCK_DTYPE = np.dtype([("block", "i4"), ("has_terms", "i4"), ("ipos", "i4"), ("ila", "i4"), ("n_terms", "u4"),
+                             ("pad", "i4"), ("v", "f8")])
+JACK_SUMMARY_DTYPE = np.dtype([(k, "i4") for k in ("n_pos", "n_la", "nb", "g", "ipos", "ila", "top_shift", "top_loss",
+                                                    "n_edge_pos", "n_edge_la")] +
+                              [(k, "f8") for k in ("v", "se_pos", "se_la", "se_clr", "bias_pos", "bias_la", "bias_clr")])
+assert BLOCKS_DTYPE.itemsize == 64 + 8 * SURFACE_MAX_LA and JACK_BLOCK_DTYPE.itemsize == 32 and JACK_SUMMARY_DTYPE.itemsize == 96
+
+
+class Blocks:
+    """The block sums of one peak: ``hdr`` (a BLOCKS_DTYPE record), ``la`` (the n_la log alphas), ``pts``
+    (the n_pos points), ``bs`` (float64 [n_pos][nb][n_la]: the surface's terms summed per block) and
+    ``cnt`` (uint32, the same shape: their counts)."""
+
+    def __init__(self, hdr, pts, bs, cnt):
+        self.hdr, self.pts, self.bs, self.cnt = hdr, pts, bs, cnt
+        self.la = np.array(hdr["la"][:int(hdr["n_la"])], dtype=np.float64)
+
+    @property
+    def sweep_pos(self):
+        return np.ascontiguousarray(self.pts["sweep_pos"], dtype=np.int32)
+
+
+def _blocks_take(res: BlocksT) -> list:
+    """The peaks copied out of a native result, which is released."""
+    n, npos, nc = int(res.n), int(res.n_pos), int(res.n_cells)
+    hdr = np.zeros(n, dtype=BLOCKS_DTYPE)
+    pts = np.zeros(npos, dtype=_POINT_RAW)
+    bs = np.zeros(nc, dtype=np.float64)
+    cnt = np.zeros(nc, dtype=np.uint32)
+    if n:
+        C.memmove(hdr.ctypes.data, res.hdr, n * BLOCKS_DTYPE.itemsize)
+    if npos:
+        C.memmove(pts.ctypes.data, res.pts, npos * _POINT_RAW.itemsize)
+    if nc:
+        C.memmove(bs.ctypes.data, res.bs, nc * 8)
+        C.memmove(cnt.ctypes.data, res.cnt, nc * 4)
+    get_lib().fscl_amd_blocks_free(C.byref(res))
+    out = []
+    for h in hdr:
+        p0, c0, m, b, k = int(h["pos_off"]), int(h["cell_off"]), int(h["n_pos"]), int(h["nb"]), int(h["n_la"])
+        out.append(Blocks(h, pts[p0:p0 + m].copy(), bs[c0:c0 + m * b * k].reshape(m, b, k).copy(),
+                          cnt[c0:c0 + m * b * k].reshape(m, b, k).copy()))
+    return out
+
+
+def blocks_cap() -> int:
+    """$FSCL_AMD_BLOCKS_CAP: the bytes of block sums and counts one scan_blocks call may return (default 2^30)."""
+    return int(get_lib().fscl_amd_blocks_cap())
+
+
+def blocks_bound(scan, run, block_bp: int, eval_range: int = 81920):
+    """(b0, nb): the blocks of the widest windows the positions of ``run`` = (chr, start_pos, step, count) can
+    have.  Host only."""
+    b0, nb = C.c_int(0), C.c_int(0)
+    if get_lib().fscl_amd_blocks_bound(scan, C.byref(RunT(*[int(v) for v in run])), int(eval_range), int(block_bp),
+                                       C.byref(b0), C.byref(nb)) != 0:
+        raise ValueError("blocks_bound: a chromosome of the scan, step >= 1, block_bp >= 1")
+    return b0.value, nb.value
+
+
+def scan_blocks(scan, tables, requests, block_bp: int, eval_range: int = 81920) -> list:
+    """The block sums of each surface request (chromosome index, centre position, half-width bp, step bp,
+    ascending log alphas[, scan point index]) in blocks of ``block_bp``, on the data as loaded
+    (include/fscl_amd.h): a list of Blocks in the given order."""
+    req = _surface_requests(requests)
+    res = BlocksT()
+    _curve_check(get_lib().fscl_amd_scan_blocks(scan, tables, int(eval_range), req.ctypes.data if len(req) else None, len(req),
+                                                int(block_bp), C.byref(res)), "fscl_amd_scan_blocks")
+    return _blocks_take(res)
+
+
+def scan_point_jackknife(scan, tables, top: int = 3, halfwidth: int = 100000, step: int = 1000,
+                         alphas=(LOG_AD_MIN, LOG_AD_MAX, 33), block_bp: int = 50000, eval_range: int = 81920) -> list:
+    """The block sums around the ``top`` scan points of greatest CLR, chosen and centred as scan_point_surfaces
+    does: a list of Blocks in descending CLR order (jackknife_combine gives each one's delete-one estimates)."""
+    res = BlocksT()
+    _curve_check(get_lib().fscl_amd_scan_point_jackknife(scan, tables, int(eval_range), int(top), int(halfwidth), int(step),
+                                                         float(alphas[0]), float(alphas[1]), int(alphas[2]), int(block_bp),
+                                                         C.byref(res)), "fscl_amd_scan_point_jackknife")
+    return _blocks_take(res)
+
+
+def blocks_runs(scan, tables, runs, alphas, blocks, eval_range: int = 81920, rows=None, batch: int = 0, pts=None, bs=None,
+                cnt=None):
+    """fsclg_blocks_submit / fsclg_blocks_wait on the scan's first device (the shim-level handle, next to
+    surface_runs): ``alphas`` holds one ascending list per run, all of one length, ``blocks`` one
+    (block_bp, b0, nb) per run.  Returns (points [sum(count)], sums, counts), the latter two flat,
+    position-major, then block, then alpha; ``pts`` / ``bs`` / ``cnt``: arrays to fill (tests pre-fill them)."""
+    arr = (RunT * max(len(runs), 1))(*[RunT(*[int(v) for v in r]) for r in runs])
+    la = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(runs), -1) if len(runs) else np.zeros((0, 1))
+    blk = np.zeros(max(len(runs), 1), dtype=BLOCKSPEC_DTYPE)
+    for q, b in zip(blk, blocks):
+        q["block_bp"], q["b0"], q["nb"] = (int(v) for v in b)
+    n, k = sum(max(int(r[3]), 0) for r in runs), la.shape[1]
+    nc = sum(max(int(r[3]), 0) * max(int(b[2]), 0) for r, b in zip(runs, blocks)) * k
+    if pts is None:
+        pts = np.zeros(max(n, 1), dtype=_POINT_RAW)
+    if bs is None:
+        bs = np.zeros(max(nc, 1), dtype=np.float64)
+    if cnt is None:
+        cnt = np.zeros(max(nc, 1), dtype=np.uint32)
+    if pts.dtype != _POINT_RAW or len(pts) < n or bs.dtype != np.float64 or bs.size < nc or cnt.dtype != np.uint32 or \
+            cnt.size < nc or not (pts.flags.c_contiguous and bs.flags.c_contiguous and cnt.flags.c_contiguous):
+        raise ValueError("pts / bs / cnt must be contiguous arrays of sum(count) points and sum(count * nb) * n_la cells")
+    rp = None
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        if len(rows) != scan.contents.n_snps:
+            raise ValueError("rows must hold one row per site")
+        rp = rows.ctypes.data
+    _curve_check(get_lib().fscl_amd_blocks_runs(scan, tables, arr, len(runs), la.ctypes.data, k, blk.ctypes.data, int(eval_range),
+                                                rp, int(batch), pts.ctypes.data, bs.ctypes.data, cnt.ctypes.data),
+                 "fscl_amd_blocks_runs")
+    return pts[:n], bs.reshape(-1)[:nc], cnt.reshape(-1)[:nc]
+
+
+def jackknife_combine(bs, cnt, pos, la):
+    """The delete-one-block estimates of one peak from its block sums ``bs`` / counts ``cnt`` [n_pos][nb][n_la],
+    the positions' sweep_pos and the log alphas (or ``jackknife_combine(blocks)`` for a Blocks): (JACK_BLOCK_DTYPE
+    records [nb], a JACK_SUMMARY_DTYPE record); the summary's ipos is -1 when every cell is NaN.  Host only.
+    The estimator is an argmax on a grid: an SE of 0 means that no block moves it by one step."""
+    bs = np.ascontiguousarray(bs, dtype=np.float64)
+    cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+    pos = np.ascontiguousarray(pos, dtype=np.int32)
+    la = np.ascontiguousarray(la, dtype=np.float64)
+    if bs.ndim != 3 or bs.shape != cnt.shape or min(bs.shape) < 1 or pos.shape != (bs.shape[0],) or la.shape != (bs.shape[2],):
+        raise ValueError("bs and cnt are non-empty [n_pos][nb][n_la] arrays, with n_pos positions and n_la alphas")
+    blocks = np.zeros(bs.shape[1], dtype=JACK_BLOCK_DTYPE)
+    out = np.zeros(1, dtype=JACK_SUMMARY_DTYPE)
+    if get_lib().fscl_amd_jackknife_combine(bs.ctypes.data, cnt.ctypes.data, bs.shape[0], bs.shape[1], bs.shape[2],
+                                            pos.ctypes.data, la.ctypes.data, blocks.ctypes.data, out.ctypes.data) < 0:
+        raise ValueError("jackknife_combine: bad arrays")
+    return blocks, out[0]
+
+
+def jackknife_output(path, scan, blocks, label=None) -> None:
+    """The --jackknife-file format (include/fscl_amd.h, README): per peak one row per block with terms, then one
+    summary row.  Host only."""
+    n = len(blocks)
+    hdr = np.zeros(max(n, 1), dtype=BLOCKS_DTYPE)
+    po = co = 0
+    for i, b in enumerate(blocks):
+        hdr[i] = b.hdr
+        if b.bs.shape != (len(b.pts), int(b.hdr["nb"]), int(b.hdr["n_la"])) or b.cnt.shape != b.bs.shape:
+            raise ValueError("a peak's sums and counts must be [n_pos][nb][n_la]")
+        hdr["n_pos"][i], hdr["pos_off"][i], hdr["cell_off"][i] = len(b.pts), po, co
+        po += len(b.pts)
+        co += b.bs.size
+    pts = np.concatenate([np.ascontiguousarray(b.pts, dtype=_POINT_RAW) for b in blocks]) if n else np.zeros(0, _POINT_RAW)
+    bs = np.concatenate([np.ascontiguousarray(b.bs, dtype=np.float64).reshape(-1) for b in blocks]) if n else np.zeros(0)
+    cnt = np.concatenate([np.ascontiguousarray(b.cnt, dtype=np.uint32).reshape(-1) for b in blocks]) if n else np.zeros(0, np.uint32)
+    res = BlocksT(n, hdr.ctypes.data, pts.ctypes.data if len(pts) else None, bs.ctypes.data if len(bs) else None,
+                  cnt.ctypes.data if len(cnt) else None, len(pts), len(bs), 0)
+    if get_lib().fscl_amd_jackknife_output(_b(path), scan, C.byref(res), _b(label)) != 0:
+        raise ValueError(f"jackknife_output: the peaks must fit their arrays and {path} be writable")
+
+
+def blocks_last_ms() -> float:
+    return float(get_lib().fscl_amd_blocks_last_ms())
+
+
 # fscl_amd_sweep_t: chromosome index, position, alpha (> 0)
 SWEEP_DTYPE = np.dtype([("chr", "i4"), ("pos", "i4"), ("alpha", "f8")])
 # fscl_amd_boot_t: one planted sweep in one replicate; est_pos -1 (and NaN est_lalpha / clr) when the
@@ -1200,7 +1391,9 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         sites_file=None, sites_top=10, simulate_file=None, simulate_sweeps=(), simulate_seed=0xFD821A6, simulate_rep=0,
         bootstrap_file=None, bootstrap_reps=100, bootstrap_window=None, bootstrap_sweeps=(), bootstrap_top=3,
         tail_file=None, tail_df=2, tail_min_n=20, surface_file=None, surface_top=3, surface_halfwidth=None,
-        surface_step=None, surface_alphas=(LOG_AD_MIN, LOG_AD_MAX, 33), surface_drop=2.0):
+        surface_step=None, surface_alphas=(LOG_AD_MIN, LOG_AD_MAX, 33), surface_drop=2.0,
+        jackknife_file=None, jackknife_top=3, jackknife_block=None, jackknife_halfwidth=None, jackknife_step=None,
+        jackknife_alphas=None):
     """The fscl main() pipeline (fscl.c:316-337) in-process; returns the scan_t
     pointer (points(scan) reads the results).  permute_mode "throughput": the
     counter-based permutation test (set_permute_mode).  scan_mode "grid": the CLI's
@@ -1223,6 +1416,18 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         if int(large_grid_sp if surface_halfwidth is None else surface_halfwidth) < 0:
             raise ValueError("surface_halfwidth must be >= 0")
         _surface_grid(*surface_alphas)  # (raises ValueError)
+    if jackknife_file is not None:
+        # the jackknife's grid defaults to the surface's, given or default
+        jackknife_halfwidth = int((large_grid_sp if surface_halfwidth is None else surface_halfwidth)
+                                  if jackknife_halfwidth is None else jackknife_halfwidth)
+        jackknife_step = int((small_grid_sp if surface_step is None else surface_step) if jackknife_step is None else jackknife_step)
+        jackknife_block = int(max(int(large_grid_sp) // 2, 1) if jackknife_block is None else jackknife_block)
+        jackknife_alphas = surface_alphas if jackknife_alphas is None else jackknife_alphas
+        if int(jackknife_top) < 0 or jackknife_halfwidth < 0:
+            raise ValueError("jackknife_top and jackknife_halfwidth must be >= 0")
+        if jackknife_step < 1 or jackknife_block < 1:
+            raise ValueError("jackknife_step and jackknife_block must be at least 1")
+        _surface_grid(*jackknife_alphas)  # (raises ValueError)
     if tail_file is not None:
         _tail_df(tail_df)
         if int(n_permute) <= 0:
@@ -1261,6 +1466,10 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
                        scan_point_surfaces(scan, tab, surface_top, int(large_grid_sp if surface_halfwidth is None else surface_halfwidth),
                                            int(small_grid_sp if surface_step is None else surface_step), surface_alphas,
                                            eval_range), surface_drop, label)
+    if jackknife_file is not None:  # the CLI's --jackknife-file: the delete-one-block jackknife of the same points
+        jackknife_output(jackknife_file, scan,
+                         scan_point_jackknife(scan, tab, jackknife_top, jackknife_halfwidth, jackknife_step, jackknife_alphas,
+                                              jackknife_block, eval_range), label)
     if n_permute > 0 and scan_mode == "grid":
         scan_permute_grid(scan, tab, n_permute, permute_nbp, eval_range, small_grid_sp, large_grid_sp, scan_width_mb)
     elif n_permute > 0:

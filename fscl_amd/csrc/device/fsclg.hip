@@ -2738,6 +2738,153 @@ surface_kernel(Params P, const SurfChunk* __restrict__ chunks, const double* __r
   }
 }
 
+// ------------------------------------------------------------ block sums of the surface
+// The surface's terms summed per genomic block (fsclg_blocks_submit): for every position of dense runs,
+// every block j < nb of the run and every log alpha of the run's list, the strictly sequential sum, from
+// +0.0 and in ascending site index, of the walk's terms whose sites lie in the block, and their count.
+// The lanes are the alphas.  A workgroup takes a chunk of consecutive positions of one run.  Prologue:
+// its waves do init_scan_result for the chunk's positions; then, per position, lane k finds the walk of
+// la[k] as a site-index range [lo, hi] by a binary search of sites_kernel's monotone predicate
+// log(alpha d) > LOG_AD_MAX on either side of the nearest SNP (lo > hi: the nearest SNP is outside, an
+// empty walk), kept in LDS.  Then the waves deal themselves the chunk's items, one item = one position
+// and one block: item it is (position it / nb, block it % nb), so the waves running together hold
+// neighbouring blocks of one position, the further waves the next positions.  A wave walks its block's
+// sites, bf[j] .. bf[j + 1) (the host's table of each block's first site, clamped to the chromosome: no
+// division here) cut to the union of the lanes' ranges, in ascending index.  The site (position, row)
+// and logt(|d|) are the same for every lane; lane k forms x = logt + la[k], takes its own interval and
+// coefficients (surf_term) and adds the term to its own running double iff the site lies in its range.
+// So every sum has the required order by construction: no reduction, no LDS in the loop, no tie logic.
+// BLK_U sites go per trip so that their loads overlap; the adds stay in site order.  A wave stores its
+// item's sums and counts with plain vector stores, consecutive lanes to consecutive words (host memory),
+// and the sums once more to a device copy, from which, after one barrier, one wave per position folds
+// V[k] = the sum over j ascending from +0.0 and lane 0 of the wave takes the first strict maximum of
+// V + null_logl in list order and stores the point.  No atomics on the result path, no workgroup waits
+// for another, and nothing depends on how the positions are chunked.
+constexpr int BLK_WAVES = 8;   // waves per workgroup
+constexpr int BLK_CH = 16;     // positions per chunk at most
+constexpr int BLK_U = 4;       // sites per trip
+constexpr int BLK_MAX_NB = 1024;
+struct BlkChunk {
+  int32_t chr, start_pos, step, count;  // positions start_pos + k * step, k < count <= BLK_CH
+  int32_t out0, run, nb, bf0;           // the chunk's first position among all; its run; the run's blocks and
+                                        // where its nb + 1 first-site indices start
+  unsigned long long item0;             // (position, block) pairs before the chunk's first
+  unsigned long long pad;
+};
+struct BlkSmem {
+  Pt pt[BLK_CH];
+  int lo[BLK_CH][SURF_MAX_LA], hi[BLK_CH][SURF_MAX_LA];  // the walk of (position, alpha): sites [lo, hi]
+  int ulo[BLK_CH], uhi[BLK_CH];                          // the union over the alphas
+  double v[BLK_CH][SURF_MAX_LA];                         // V of (position, alpha)
+};
+
+__global__ void __launch_bounds__(64 * BLK_WAVES)
+blocks_kernel(Params P, const BlkChunk* __restrict__ chunks, const double* __restrict__ la_all,
+              const int32_t* __restrict__ bf_all, int n_la, double* __restrict__ bs_out, uint32_t* __restrict__ cnt_out,
+              double* bs_dev) {
+  __shared__ BlkSmem S;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kc = (int)blockIdx.x;
+  if (kc >= P.n_cells) return;
+  const BlkChunk c = chunks[kc];
+  for (int i = wave; i < c.count; i += BLK_WAVES) init_point_wave(S.pt[i], c.chr, c.start_pos + i * c.step, P, lane);
+  __syncthreads();
+  const bool on = lane < n_la;
+  const double la = la_all[(size_t)c.run * (size_t)n_la + (size_t)(on ? lane : 0)];
+  for (int i = wave; i < c.count; i += BLK_WAVES) {  // the walks' bounds, lane k for alpha k
+    const Pt& pt = S.pt[i];
+    const int near = pt.nearest;
+    const uint32_t usweep = (uint32_t)pt.sweep ^ POS_BIAS;
+    auto outside = [&](int m) { return logt_dev(absdist(P.pr[phys(m)].x, usweep), P.logt3) + la > LOG_AD_MAX; };
+    int lo = 1, hi = 0;
+    if (on && !outside(near)) {
+      // left: outside holds on a prefix of (wstart - 1, near); lo = the first site inside (near if none is)
+      int a = pt.wstart - 1, b = near;
+      while (b - a > 1) {
+        const int m = a + ((b - a) >> 1);
+        if (outside(m)) a = m; else b = m;
+      }
+      lo = b;
+      hi = near;
+      if (near + 1 <= pt.wend && !outside(near + 1)) {  // right: inside holds on a prefix of (near + 1, wend + 1)
+        a = near + 1; b = pt.wend + 1;
+        while (b - a > 1) {
+          const int m = a + ((b - a) >> 1);
+          if (!outside(m)) a = m; else b = m;
+        }
+        hi = b - 1;
+      }
+    }
+    S.lo[i][lane] = lo; S.hi[i][lane] = hi;
+    int ul = lo <= hi ? lo : 0x7FFFFFFF, uh = lo <= hi ? hi : -1;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { ul = min(ul, __shfl_xor(ul, o, 64)); uh = max(uh, __shfl_xor(uh, o, 64)); }
+    if (lane == 0) { S.ulo[i] = ul; S.uhi[i] = uh; }
+  }
+  __syncthreads();
+  const int32_t* __restrict__ bf = bf_all + c.bf0;
+  for (int it = wave; it < c.count * c.nb; it += BLK_WAVES) {
+    const int pi = it / c.nb, j = it - pi * c.nb;
+    const uint32_t usweep = (uint32_t)S.pt[pi].sweep ^ POS_BIAS;
+    const int lo = S.lo[pi][lane], hi = S.hi[pi][lane];
+    const int i0 = max(bf[j], S.ulo[pi]), i1 = min(bf[j + 1] - 1, S.uhi[pi]);  // (wave-uniform)
+    double acc = 0.0;
+    uint32_t n = 0;
+    for (int ib = i0; ib <= i1; ib += BLK_U) {
+      uint2 s[BLK_U];
+      double lt[BLK_U], t[BLK_U];
+      bool in[BLK_U];
+#pragma unroll
+      for (int u = 0; u < BLK_U; u++) s[u] = P.pr[phys(min(ib + u, i1))];
+#pragma unroll
+      for (int u = 0; u < BLK_U; u++) lt[u] = logt_dev(absdist(s[u].x, usweep), P.logt3);
+#pragma unroll
+      for (int u = 0; u < BLK_U; u++) {
+        in[u] = ib + u <= i1 && ib + u >= lo && ib + u <= hi;
+        t[u] = 0.0;
+        if (in[u]) t[u] = surf_term(lt[u] + la, s[u].y, S, P);
+      }
+#pragma unroll
+      for (int u = 0; u < BLK_U; u++)
+        if (in[u]) { acc = acc + t[u]; n++; }
+    }
+    if (on) {
+      const size_t o = (size_t)(c.item0 + (unsigned long long)it) * (size_t)n_la + (size_t)lane;
+      bs_out[o] = acc; cnt_out[o] = n; bs_dev[o] = acc;
+    }
+  }
+  __threadfence();
+  __syncthreads();  // the chunk's sums are in bs_dev
+  for (int i = wave; i < c.count; i += BLK_WAVES) {
+    Pt& pt = S.pt[i];
+    double v = 0.0;
+    if (on) {
+      const double* q = bs_dev + (size_t)(c.item0 + (unsigned long long)i * (unsigned long long)c.nb) * (size_t)n_la + lane;
+      for (int j = 0; j < c.nb; j++) v = v + q[(size_t)j * (size_t)n_la];
+    }
+    S.v[i][lane] = v;
+    const int wl = S.lo[i][lane], wh = S.hi[i][lane];
+    const unsigned long long terms = (unsigned long long)wave_sum64(wl <= wh ? (long long)(wh - wl + 1) : 0ll);
+    if (lane == 0) {  // one store per point (P.out is host memory: no read-modify-write)
+      double best = -1.7976931348623157e308, bla = LOG_AD_MAX, bv = 0.0;
+      bool have = false;
+      const double* __restrict__ lap = la_all + (size_t)c.run * (size_t)n_la;
+      for (int k = 0; k < n_la; k++) {
+        const double w = S.v[i][k] + pt.N;
+        if (w > best) { best = w; bla = lap[k]; bv = S.v[i][k]; have = true; }
+      }
+      pt.la = bla; pt.sm = best; pt.clr = have ? 2.0 * bv : 2.0 * (best - pt.N);
+      fsclg_point_t o;
+      write_point(o, pt);
+      o.cost = (uint32_t)min(terms >> 10, 0xFFFFFFFFull);  // the position's terms / 1024
+      P.out[c.out0 + i] = o;
+      atomicAdd(&P.stats[0], terms);                                   // the device counters, as any launch:
+      atomicAdd(&P.stats[1], (unsigned long long)pt.n_snps);           // terms, null-sum elements, walks
+      atomicAdd(&P.stats[2], (unsigned long long)n_la);
+    }
+  }
+}
+
 // ------------------------------------------------------------ sweep-model sampler
 // One replicate of derived counts under the model (fsclg_sample_submit; the idea of the reference's
 // sm-sample.c:164-212).  One wave per site, SAMPLE_WAVES sites per workgroup.  The site's set-up --
@@ -3599,7 +3746,8 @@ struct Slot {
 };
 
 // what a batch holds between a submit and its wait
-enum BatchKind { BK_NONE, BK_SEARCH, BK_PROFILE, BK_CELLMAX, BK_CURVE, BK_SITES, BK_SAMPLE, BK_TAIL, BK_SURFACE };
+enum BatchKind { BK_NONE, BK_SEARCH, BK_PROFILE, BK_CELLMAX, BK_CURVE, BK_SITES, BK_SAMPLE, BK_TAIL, BK_SURFACE,
+                 BK_BLOCKS };
 
 // one call of any kind in flight (a submit / wait pair: search, profile, cell maxima, curves, site
 // terms, sample, tail fit): its stream and events, the device and pinned host buffers of each kind,
@@ -3687,6 +3835,18 @@ struct Batch {
   int sfchunk_cap = 0, sfla_cap = 0, sfsm_cap = 0;
   int sf_n = 0, sf_nla = 0;         // positions and alphas per position of the submitted surfaces
   double sf_ms = 0.0;               // kernel time of the batch's last surface launch
+  // fsclg_blocks_submit: the chunks, the alpha lists and the blocks' first sites (pinned, read by the kernel),
+  // the block sums and counts (pinned, written by the kernel; the points are p_out), the device copy of the sums
+  BlkChunk* p_bkchunks = nullptr;
+  double* p_bkla = nullptr;
+  int32_t* p_bkbf = nullptr;
+  double* p_bkbs = nullptr;
+  uint32_t* p_bkcnt = nullptr;
+  double* d_bkbs = nullptr;
+  int bkchunk_cap = 0, bkla_cap = 0, bkbf_cap = 0, bkbs_cap = 0, bkcnt_cap = 0, dbkbs_cap = 0;
+  int bk_n = 0;                     // positions of the submitted block sums
+  size_t bk_cells = 0;              // their (position, block, alpha) cells
+  double bk_ms = 0.0;               // kernel time of the batch's last block-sum launch
 };
 
 struct fsclg_ctx {
@@ -3904,8 +4064,10 @@ int fsclg_close(fsclg_ctx* c) {
                     (void*)B.p_cmchunks, (void*)B.p_curve, (void*)B.p_sreq, (void*)B.p_shdr, (void*)B.p_stasks,
                     (void*)B.p_sterms, (void*)B.p_sdepth, (void*)B.p_sfreq, (void*)B.p_ssweeps,
                     (void*)B.p_tsamples, (void*)B.p_toff, (void*)B.p_tcnt, (void*)B.p_tx0, (void*)B.p_tout,
-                    (void*)B.p_sfchunks, (void*)B.p_sfla, (void*)B.p_sfsm})
+                    (void*)B.p_sfchunks, (void*)B.p_sfla, (void*)B.p_sfsm, (void*)B.p_bkchunks, (void*)B.p_bkla,
+                    (void*)B.p_bkbf, (void*)B.p_bkbs, (void*)B.p_bkcnt})
       if (p) hipHostFree(p);
+    if (B.d_bkbs) hipFree(B.d_bkbs);
     hipEventDestroy(B.ev0);
     hipEventDestroy(B.ev1);
     hipEventDestroy(B.ev2);
@@ -5264,7 +5426,8 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
       "batch not submitted", nullptr, "the batch holds a profile (fsclg_profile_wait)",
       "the batch holds cell maxima (fsclg_cellmax_wait)", "the batch holds curves (fsclg_curve_wait)",
       "the batch holds site terms (fsclg_sites_wait)", "the batch holds a sample (fsclg_sample_wait)",
-      "the batch holds a tail fit (fsclg_tail_wait)", "the batch holds surfaces (fsclg_surface_wait)"};
+      "the batch holds a tail fit (fsclg_tail_wait)", "the batch holds surfaces (fsclg_surface_wait)",
+      "the batch holds block sums (fsclg_blocks_wait)"};
   if (B.holds != BK_SEARCH) return set_err(FSCLG_E_STATE, other[B.holds]);
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
@@ -5771,6 +5934,119 @@ int fsclg_surface_wait(fsclg_ctx* c, int batch, fsclg_point_t* pts, double* sm) 
 
 double fsclg_surface_last_ms(fsclg_ctx* c, int batch) {
   return c && batch >= 0 && batch < NBATCH ? c->batch[batch].sf_ms : 0.0;
+}
+
+// ------------------------------------------------------------ block sums of the surface (host side)
+// fsclg_surface_submit's checks, slot and window null sums; per run the table of each block's first site:
+// bf[0] = the chromosome's first site, bf[nb] = one past its last (the edge blocks absorb what lies beyond
+// them), bf[j] = the first site at or past position (b0 + j) * block_bp between.  A chunk holds as many
+// positions as give its workgroup about two items per wave (the result does not depend on it).
+int fsclg_blocks_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* runs, int n_runs, const double* la,
+                        int n_la, const fsclg_blocks_t* blk, int eval_range) {
+  if (!c || (!runs && n_runs) || n_runs < 0 || eval_range < 0) return set_err(FSCLG_E_ARG, "runs");
+  if (batch < 0 || batch >= NBATCH || slot < 0 || slot >= NSLOT) return set_err(FSCLG_E_ARG, "batch/slot");
+  if (n_la < 1 || n_la > SURF_MAX_LA) return set_err(FSCLG_E_ARG, "alphas per position outside [1, 64]");
+  if ((!la || !blk) && n_runs) return set_err(FSCLG_E_ARG, "alpha lists / blocks");
+  if (!c->d_pr0 || !c->d_coef) return set_err(FSCLG_E_STATE, "tables/snps not set");
+  Batch& B = c->batch[batch];
+  if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
+  for (long long i = 0; i < (long long)n_runs * n_la; i++) {
+    if (!(la[i] >= LOG_AD_MIN && la[i] <= LOG_AD_MAX)) return set_err(FSCLG_E_ARG, "log alpha outside [LOG_AD_MIN, LOG_AD_MAX]");
+    if (i % n_la && !(la[i] > la[i - 1])) return set_err(FSCLG_E_ARG, "alpha list not ascending");
+  }
+  long long nbf = 0, nbmax = 1;
+  for (int i = 0; i < n_runs; i++) {
+    if (blk[i].block_bp < 1) return set_err(FSCLG_E_ARG, "block_bp < 1");
+    if (blk[i].b0 < 0) return set_err(FSCLG_E_ARG, "first block id < 0");
+    if (blk[i].nb < 1 || blk[i].nb > BLK_MAX_NB) return set_err(FSCLG_E_ARG, "blocks per run outside [1, 1024]");
+    nbf += blk[i].nb + 1;
+    nbmax = std::max(nbmax, (long long)blk[i].nb);
+  }
+  long long total, nchunk;
+  int r;
+  if ((r = validate_runs(c, runs, n_runs, eval_range, 1, &total, &nchunk))) return r;
+  long long items = 0;
+  for (int i = 0; i < n_runs; i++) items += (long long)runs[i].count * blk[i].nb;
+  if (items * n_la > 0x7FFFFFFFll / (long long)sizeof(double) || total > 0x7FFFFFFFll / (long long)sizeof(fsclg_point_t) ||
+      nbf > 0x7FFFFFFFll / 4)
+    return set_err(FSCLG_E_ARG, "too many block cells");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
+  B.eval_range = eval_range; B.bp_resl = 0; B.bk_ms = 0.0; B.bk_n = (int)total; B.bk_cells = (size_t)(items * n_la);
+  if (total > 0) {
+    std::vector<fsclg_cell_t> cover;
+    nchunk = 0;
+    for (int i = 0; i < n_runs; i++) {
+      if (runs[i].count <= 0) continue;
+      cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos, runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
+      const int CH = std::max(1, std::min(BLK_CH, (2 * BLK_WAVES + blk[i].nb - 1) / blk[i].nb));
+      nchunk += (runs[i].count + CH - 1) / CH;
+    }
+    B.nu = (int)nchunk;
+    if ((r = cover_windows(c, B, slot, cover, eval_range))) return r;
+    if ((r = ensure_io(B, (int)total))) return r;
+    if ((r = ensure_pinned(&B.p_bkchunks, &B.bkchunk_cap, (int)nchunk))) return r;
+    if ((r = ensure_pinned(&B.p_bkla, &B.bkla_cap, n_runs * n_la))) return r;
+    if ((r = ensure_pinned(&B.p_bkbf, &B.bkbf_cap, (int)nbf))) return r;
+    if ((r = ensure_pinned(&B.p_bkbs, &B.bkbs_cap, (int)B.bk_cells))) return r;
+    if ((r = ensure_pinned(&B.p_bkcnt, &B.bkcnt_cap, (int)B.bk_cells))) return r;
+    if ((r = ensure_buf(&B.d_bkbs, &B.dbkbs_cap, (int)B.bk_cells))) return r;
+    memcpy(B.p_bkla, la, sizeof(double) * (size_t)n_runs * (size_t)n_la);
+    int nc = 0, o = 0, bfo = 0;
+    unsigned long long item0 = 0;
+    for (int i = 0; i < n_runs; i++) {
+      const int a = c->h_chr_start[runs[i].chr], n = c->h_chr_n[runs[i].chr], nb = blk[i].nb;
+      const int32_t* pos = c->h_pos.data() + a;
+      int32_t* bf = B.p_bkbf + bfo;
+      bf[0] = a; bf[nb] = a + n;
+      for (int j = 1; j < nb; j++) {  // (positions ascend within a chromosome; the bound as long long: no overflow)
+        const long long lim = ((long long)blk[i].b0 + j) * (long long)blk[i].block_bp;
+        bf[j] = a + (int)(std::lower_bound(pos, pos + n, lim, [](int32_t x, long long v) { return (long long)x < v; }) - pos);
+      }
+      const int CH = std::max(1, std::min(BLK_CH, (2 * BLK_WAVES + nb - 1) / nb));
+      for (int j = 0; j < runs[i].count; j += CH) {
+        const int cnt = std::min(CH, runs[i].count - j);
+        B.p_bkchunks[nc++] = BlkChunk{runs[i].chr, runs[i].start_pos + j * runs[i].step, runs[i].step, cnt, o, i, nb, bfo, item0, 0ull};
+        o += cnt;
+        item0 += (unsigned long long)cnt * (unsigned long long)nb;
+      }
+      bfo += nb + 1;
+    }
+    HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
+    Params P = make_params(c, B, slot, nc, 3, eval_range, 0);
+    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
+    hipLaunchKernelGGL(blocks_kernel, dim3(nc), dim3(64 * BLK_WAVES), 0, B.stream, P, (const BlkChunk*)B.p_bkchunks,
+                       (const double*)B.p_bkla, (const int32_t*)B.p_bkbf, n_la, B.p_bkbs, B.p_bkcnt, B.d_bkbs);
+    HIPCHK(hipGetLastError(), "launch blocks_kernel");
+    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+  }
+  B.holds = BK_BLOCKS;
+  c->slot[slot].users++;
+  return FSCLG_OK;
+}
+
+int fsclg_blocks_wait(fsclg_ctx* c, int batch, fsclg_point_t* pts, double* bs, uint32_t* cnt) {
+  if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
+  Batch& B = c->batch[batch];
+  if (B.holds != BK_BLOCKS) return set_err(FSCLG_E_STATE, "no block sums submitted on the batch");
+  if ((!pts || !bs || !cnt) && B.bk_n) return set_err(FSCLG_E_ARG, "out");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  B.holds = BK_NONE;
+  c->slot[B.slot].users--;
+  const int n = B.bk_n;
+  if (n == 0) return FSCLG_OK;
+  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  memcpy(pts, B.p_out, sizeof(fsclg_point_t) * (size_t)n);
+  memcpy(bs, B.p_bkbs, sizeof(double) * B.bk_cells);
+  memcpy(cnt, B.p_bkcnt, sizeof(uint32_t) * B.bk_cells);
+  int r, flags = 0;
+  if ((r = batch_time(c, B, 1, &B.bk_ms))) return r;
+  for (int i = 0; i < n; i++) flags |= pts[i].flags;
+  return flags_err(flags);
+}
+
+double fsclg_blocks_last_ms(fsclg_ctx* c, int batch) {
+  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].bk_ms : 0.0;
 }
 
 // ------------------------------------------------------------ per-site terms (host side)

@@ -116,6 +116,9 @@ int main(int argc, char **argv) {
   char *surface_fname = NULL, *surface_alphas = NULL;
   int surface_top = 3, surface_halfwidth = -1, surface_step = -1, surface_n = 33;
   double surface_drop = 2.0, surface_lo = LOG_AD_MIN, surface_hi = LOG_AD_MAX;
+  char *jackknife_fname = NULL, *jackknife_alphas = NULL;
+  int jackknife_top = 3, jackknife_block = -1, jackknife_halfwidth = -1, jackknife_step = -1, jackknife_n = 33;
+  double jackknife_lo = LOG_AD_MIN, jackknife_hi = LOG_AD_MAX;
   int tail_df = 2, tail_min_n = 20;
   scan_t *s;
   double **fsp;
@@ -187,6 +190,14 @@ int main(int argc, char **argv) {
       {0, "surface-drop", &surface_drop, T_DBL, "log-likelihood drop of the region in --surface-file (default 2.0, as --alpha-drop; a joint "
                                                 "two-parameter 95 % region under the chi-square reading would be about 3.0; descriptive: "
                                                 "the likelihood is composite)"},
+      {0, "jackknife-file", &jackknife_fname, T_STR, "write a delete-one-block jackknife of the scan points of greatest CLR (the "
+                                                     "re-maximised position, alpha and CLR with each genomic block left out, and their "
+                                                     "standard errors) to this file"},
+      {0, "jackknife-top", &jackknife_top, T_INT, "--jackknife-file takes this many points of greatest CLR (default 3)"},
+      {0, "jackknife-block", &jackknife_block, T_INT, "block length in bp of the jackknife (default: half the -G spacing; at least 1)"},
+      {0, "jackknife-halfwidth", &jackknife_halfwidth, T_INT, "half-width in bp of the jackknife's positions (default: --surface-halfwidth)"},
+      {0, "jackknife-step", &jackknife_step, T_INT, "spacing in bp of the jackknife's positions (default: --surface-step)"},
+      {0, "jackknife-alphas", &jackknife_alphas, T_STR, "LO:HI:N, the jackknife's alpha grid (default: --surface-alphas)"},
       {0, "tail-min-n", &tail_min_n, T_INT, "--tail-file fits a point with at least this many positive null CLRs (default 20)"},
       {0, NULL, NULL, 0, NULL}};
 
@@ -332,6 +343,7 @@ int main(int argc, char **argv) {
   if (surface_top < 0) { logmsg(MSG_ERROR, "Error: --surface-top must be >= 0.\n"); stop = 1; }
   if (surface_halfwidth < 0) surface_halfwidth = surface_halfwidth == -1 ? large_grid_sp : -2;
   if (surface_halfwidth == -2) { logmsg(MSG_ERROR, "Error: --surface-halfwidth must be >= 0.\n"); stop = 1; }
+  if (jackknife_step == -1) jackknife_step = surface_step == -1 ? small_grid_sp : surface_step; /* --surface-step, given or default */
   if (surface_step == -1) surface_step = surface_fname ? small_grid_sp : 1;
   if (surface_step < 1) { logmsg(MSG_ERROR, "Error: --surface-step must be at least 1.\n"); stop = 1; }
   if (!(surface_drop >= 0.0)) { logmsg(MSG_ERROR, "Error: --surface-drop must be >= 0.\n"); stop = 1; }
@@ -344,6 +356,25 @@ int main(int argc, char **argv) {
                         "and LO < HI unless N is 1 (not \"%s\").\n", surface_alphas);
       stop = 1;
     }
+  }
+  if (jackknife_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --jackknife-file needs the scan (not with --no-scan).\n"); stop = 1; }
+  if (jackknife_top < 0) { logmsg(MSG_ERROR, "Error: --jackknife-top must be >= 0.\n"); stop = 1; }
+  if (jackknife_block == -1) jackknife_block = large_grid_sp / 2 > 1 ? large_grid_sp / 2 : 1;
+  if (jackknife_block < 1) { logmsg(MSG_ERROR, "Error: --jackknife-block must be at least 1.\n"); stop = 1; }
+  if (jackknife_halfwidth == -1) jackknife_halfwidth = surface_halfwidth;
+  if (jackknife_halfwidth < 0) { logmsg(MSG_ERROR, "Error: --jackknife-halfwidth must be >= 0.\n"); stop = 1; }
+  if (jackknife_step < 1) { logmsg(MSG_ERROR, "Error: --jackknife-step must be at least 1.\n"); stop = 1; }
+  if (jackknife_alphas) {
+    char tail_c = 0;
+    double probe[FSCL_AMD_SURFACE_MAX_LA];
+    if (sscanf(jackknife_alphas, "%lf:%lf:%d%c", &jackknife_lo, &jackknife_hi, &jackknife_n, &tail_c) != 3 ||
+        fscl_amd_surface_alphas(jackknife_lo, jackknife_hi, jackknife_n, NAN, probe) < 1) {
+      logmsg(MSG_ERROR, "Error: --jackknife-alphas must be LO:HI:N with -20 <= LO <= HI <= 4 (natural-log alpha), 1 <= N <= 63, "
+                        "and LO < HI unless N is 1 (not \"%s\").\n", jackknife_alphas);
+      stop = 1;
+    }
+  } else {
+    jackknife_lo = surface_lo; jackknife_hi = surface_hi; jackknife_n = surface_n;
   }
   if (permute_seed && !(permute_mode && !strcmp(permute_mode, "throughput")))
     logmsg(MSG_WARN, "Warning: --permute-seed is used only with --permute-mode=throughput.\n");
@@ -461,6 +492,18 @@ int main(int argc, char **argv) {
       logmsg(MSG_STATUS, "Surfaces: %d points, %llu cells, %llu terms, kernel %.3f ms\n", sf.n, (unsigned long long)sf.n_cells,
              sf.n_terms, fscl_amd_surface_last_ms());
       fscl_amd_surfaces_free(&sf);
+    }
+    if (jackknife_fname && !(ws && rk && atoi(ws) > 1 && atoi(rk) != 0)) {
+      /* the delete-one-block jackknife of the points of greatest CLR, of the data as loaded (rank 0 alone); no rand() draw */
+      fscl_amd_blocks_t bk;
+      const int r = fscl_amd_scan_point_jackknife(s, sm, eval_range, jackknife_top, jackknife_halfwidth, jackknife_step,
+                                                  jackknife_lo, jackknife_hi, jackknife_n, jackknife_block, &bk);
+      if (r != 0) logmsg(MSG_FATAL, "fscl: jackknife failed (code %d)", r);
+      if (fscl_amd_jackknife_output(jackknife_fname, s, &bk, prepend_label) != 0)
+        logmsg(MSG_FATAL, "fscl: cannot write %s", jackknife_fname);
+      logmsg(MSG_STATUS, "Jackknife: %d peaks, %llu block cells, %llu terms, kernel %.3f ms\n", bk.n, (unsigned long long)bk.n_cells,
+             bk.n_terms, fscl_amd_blocks_last_ms());
+      fscl_amd_blocks_free(&bk);
     }
     if (dont_scan) {
       /* nothing to test or to write */

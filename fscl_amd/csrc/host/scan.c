@@ -2906,6 +2906,201 @@ int fscl_amd_surface_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, i
   return r;
 }
 
+/* ------------------------------------------------------ block sums (delete-one-block jackknife)
+   The surface's terms summed per genomic block (fsclg_blocks_submit) for surface requests, on the
+   data as loaded.  The size checks come first, on the host; then a surface evaluation of the same
+   requests gives every position's window, hence each request's blocks; then the block sums, one
+   list length after another and the local devices side by side, as the surfaces. */
+static double g_blocks_ms;
+double fscl_amd_blocks_last_ms(void) { return g_blocks_ms; }
+
+int fscl_amd_scan_blocks(scan_t *s, sm_ptable_t *sm, int eval_range, const fscl_amd_surface_req_t *req, int n,
+                         int block_bp, fscl_amd_blocks_t *out) {
+  fscl_amd_surfaces_t sf;
+  fsclg_run_t *runs;
+  fsclg_blocks_t *blk;
+  double *cost, *la, dev_ms[FH_MAX_DEV];
+  int *idx, lo[FH_MAX_DEV], hi[FH_MAX_DEV], i, j, l, k, m, nla, r = FSCLG_OK;
+  uint64_t po = 0, co = 0;
+  if (!s || !sm || !out || n < 0 || (n && !req) || block_bp < 1 || eval_range < 0) return FSCLG_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (D.world > 1 && D.rank != 0) return FSCLG_OK; /* rank 0 alone evaluates, as the surfaces */
+  runs = fh_malloc(sizeof(fsclg_run_t) * (n ? n : 1), "block runs");
+  for (i = 0; i < n; i++) { /* every refusal before the first device call */
+    int b0, nb;
+    if (!surface_list_ok(req[i].la, req[i].n_la) || fscl_amd_surface_run(s, req + i, runs + i) != 0 ||
+        fscl_amd_blocks_bound(s, runs + i, eval_range, block_bp, &b0, &nb) != 0) {
+      free(runs);
+      return FSCLG_E_ARG;
+    }
+    if (nb > FSCL_AMD_BLOCKS_MAX_NB) {
+      logmsg(MSG_ERROR, "Error: the jackknife of the peak at %d needs %d blocks of %d bp (at most %d): raise --jackknife-block.\n",
+             req[i].centre_pos, nb, block_bp, FSCL_AMD_BLOCKS_MAX_NB);
+      free(runs);
+      return FSCLG_E_ARG;
+    }
+    co += (uint64_t)runs[i].count * (uint64_t)nb * (uint64_t)req[i].n_la;
+  }
+  if (co * (sizeof(double) + sizeof(uint32_t)) > (uint64_t)fscl_amd_blocks_cap()) {
+    logmsg(MSG_ERROR, "Error: the jackknife's block sums take %llu bytes (limit %llu, $FSCL_AMD_BLOCKS_CAP): raise --jackknife-block "
+                      "or --jackknife-step, or lower --jackknife-top, --jackknife-halfwidth or the count of --jackknife-alphas.\n",
+           (unsigned long long)(co * (sizeof(double) + sizeof(uint32_t))), (unsigned long long)fscl_amd_blocks_cap());
+    free(runs);
+    return FSCLG_E_ARG;
+  }
+  r = fscl_amd_scan_surface(s, sm, eval_range, req, n, &sf); /* the windows of the positions */
+  if (r != FSCLG_OK) { free(runs); return r; }
+  out->hdr = fh_calloc(n ? n : 1, sizeof *out->hdr, "block headers");
+  blk = fh_calloc(n ? n : 1, sizeof *blk, "blocks");
+  for (i = 0, co = 0; i < n; i++) {
+    fscl_amd_blocks_hdr_t *h = out->hdr + i;
+    const fsclg_point_t *pt = sf.pts + sf.hdr[i].pos_off;
+    int ws = -1, we = -1;
+    for (j = 0; j < runs[i].count; j++) {
+      if (ws < 0 || pt[j].window_start < ws) ws = pt[j].window_start;
+      if (we < 0 || pt[j].window_end > we) we = pt[j].window_end;
+    }
+    h->chr = req[i].chr; h->centre_pos = req[i].centre_pos; h->halfwidth = req[i].halfwidth; h->step = req[i].step;
+    h->n_la = req[i].n_la; h->point = req[i].point; h->start_pos = runs[i].start_pos; h->n_pos = runs[i].count;
+    memcpy(h->la, req[i].la, sizeof(double) * (size_t)h->n_la);
+    h->block_bp = block_bp; h->b0 = 0; h->nb = 1;
+    if (ws >= 0) {
+      const int a = s->snps[ws].pos / block_bp, b = s->snps[we].pos / block_bp;
+      h->b0 = a < 0 ? 0 : a;
+      h->nb = b - h->b0 + 1 < 1 ? 1 : b - h->b0 + 1;
+      if (h->nb > FSCL_AMD_BLOCKS_MAX_NB) h->nb = FSCL_AMD_BLOCKS_MAX_NB; /* (the bound above covers these windows) */
+    }
+    blk[i].block_bp = block_bp; blk[i].b0 = h->b0; blk[i].nb = h->nb;
+    h->pos_off = po; h->cell_off = co;
+    po += (uint64_t)h->n_pos; co += (uint64_t)h->n_pos * (uint64_t)h->nb * (uint64_t)h->n_la;
+  }
+  fscl_amd_surfaces_free(&sf);
+  out->n = n; out->n_pos = (size_t)po; out->n_cells = (size_t)co;
+  out->pts = fh_calloc(po ? po : 1, sizeof *out->pts, "block points");
+  out->bs = fh_calloc(co ? co : 1, sizeof *out->bs, "block sums");
+  out->cnt = fh_calloc(co ? co : 1, sizeof *out->cnt, "block counts");
+  g_blocks_ms = 0.;
+  for (l = 0; l < FH_MAX_DEV; l++) dev_ms[l] = 0.;
+  idx = fh_malloc(sizeof(int) * (n ? n : 1), "block requests");
+  cost = fh_malloc(sizeof(double) * (n ? n : 1), "cost");
+  for (nla = 1; nla <= FSCL_AMD_SURFACE_MAX_LA && r == FSCLG_OK; nla++) {
+    fsclg_run_t *gr;
+    fsclg_blocks_t *gb;
+    fsclg_point_t *gp;
+    double *gs;
+    uint32_t *gc;
+    size_t np = 0, ncell = 0, off, coff;
+    for (i = 0, m = 0; i < n; i++)
+      if (req[i].n_la == nla) {
+        idx[m] = i; cost[m] = window_cost(req[i].chr, eval_range) * runs[i].count * nla;
+        np += (size_t)runs[i].count; ncell += (size_t)runs[i].count * blk[i].nb * nla; m++;
+      }
+    if (m == 0) continue;
+    gr = fh_malloc(sizeof *gr * (size_t)m, "block runs");
+    gb = fh_malloc(sizeof *gb * (size_t)m, "blocks");
+    la = fh_malloc(sizeof(double) * (size_t)m * nla, "block alphas");
+    gp = fh_malloc(sizeof *gp * (np ? np : 1), "block points");
+    gs = fh_malloc(sizeof(double) * (ncell ? ncell : 1), "block sums");
+    gc = fh_malloc(sizeof(uint32_t) * (ncell ? ncell : 1), "block counts");
+    for (j = 0; j < m; j++) { gr[j] = runs[idx[j]]; gb[j] = blk[idx[j]]; memcpy(la + (size_t)j * nla, req[idx[j]].la, sizeof(double) * (size_t)nla); }
+    for (l = 0; l < D.n_dev; l++) {
+      if (D.n_dev <= 1) { lo[l] = 0; hi[l] = m; }
+      else fscl_amd_partition(cost, m, l, D.n_dev, &lo[l], &hi[l]);
+    }
+    for (l = 0; l < D.n_dev; l++) out->n_terms -= dev_terms(l);
+    for (l = 0; l < D.n_dev && r == FSCLG_OK; l++) {
+      DBG("blocks: device %d, %d alphas, requests [%d, %d)\n", D.dev[l], nla, lo[l], hi[l]);
+      r = fsclg_blocks_submit(D.ctx[l], 0, 0, gr + lo[l], hi[l] - lo[l], la + (size_t)lo[l] * nla, nla, gb + lo[l], eval_range);
+    }
+    for (k = 0; k < l; k++) {
+      int rw;
+      if (k == l - 1 && r != FSCLG_OK) break; /* the submit that failed left nothing to wait for */
+      for (j = 0, off = 0, coff = 0; j < lo[k]; j++) { off += (size_t)gr[j].count; coff += (size_t)gr[j].count * gb[j].nb * nla; }
+      rw = fsclg_blocks_wait(D.ctx[k], 0, gp + off, gs + coff, gc + coff);
+      dev_ms[k] += fsclg_blocks_last_ms(D.ctx[k], 0);
+      if (r == FSCLG_OK) r = rw;
+    }
+    for (l = 0; l < D.n_dev; l++) out->n_terms += dev_terms(l);
+    for (j = 0, off = 0, coff = 0; j < m && r == FSCLG_OK; j++) { /* back into request order */
+      const fscl_amd_blocks_hdr_t *h = out->hdr + idx[j];
+      const size_t nc = (size_t)h->n_pos * h->nb * nla;
+      memcpy(out->pts + h->pos_off, gp + off, sizeof *gp * (size_t)h->n_pos);
+      memcpy(out->bs + h->cell_off, gs + coff, sizeof(double) * nc);
+      memcpy(out->cnt + h->cell_off, gc + coff, sizeof(uint32_t) * nc);
+      off += (size_t)h->n_pos; coff += nc;
+    }
+    free(gr); free(gb); free(la); free(gp); free(gs); free(gc);
+  }
+  for (l = 0; l < D.n_dev; l++)
+    if (dev_ms[l] > g_blocks_ms) g_blocks_ms = dev_ms[l]; /* the devices run side by side */
+  free(runs); free(blk); free(idx); free(cost);
+  if (r != FSCLG_OK) fscl_amd_blocks_free(out);
+  return r;
+}
+
+int fscl_amd_scan_point_jackknife(scan_t *s, sm_ptable_t *sm, int eval_range, int top, int halfwidth, int step,
+                                  double la_lo, double la_hi, int n_grid, int block_bp, fscl_amd_blocks_t *out) {
+  fscl_amd_surface_req_t *req;
+  char *used;
+  int n = 0, i, k, r;
+  if (!s || !sm || !out || (!s->scan_pts && s->n_scan_pts) || s->n_scan_pts < 0 || top < 0 || halfwidth < 0 || step < 1 ||
+      block_bp < 1)
+    return FSCLG_E_ARG;
+  memset(out, 0, sizeof *out);
+  req = fh_calloc(top ? top : 1, sizeof *req, "jackknife requests");
+  used = fh_calloc(s->n_scan_pts ? s->n_scan_pts : 1, 1, "jackknife requests");
+  while (n < top) { /* descending CLR, as the --surface-top and --bootstrap-top points */
+    int best = -1;
+    for (i = 0; i < s->n_scan_pts; i++)
+      if (!used[i] && s->scan_pts[i].clr == s->scan_pts[i].clr && (best < 0 || s->scan_pts[i].clr > s->scan_pts[best].clr))
+        best = i;
+    if (best < 0) break;
+    used[best] = 1;
+    for (k = 0; k < n; k++) {
+      long long d = (long long)s->scan_pts[best].sweep_pos - req[k].centre_pos;
+      if (req[k].chr == s->scan_pts[best].chr && (d < 0 ? -d : d) <= halfwidth) break;
+    }
+    if (k < n) continue;
+    req[n].chr = s->scan_pts[best].chr; req[n].centre_pos = s->scan_pts[best].sweep_pos;
+    req[n].halfwidth = halfwidth; req[n].step = step; req[n].point = best;
+    req[n].n_la = fscl_amd_surface_alphas(la_lo, la_hi, n_grid, s->scan_pts[best].lalpha, req[n].la);
+    if (req[n].n_la < 1) { free(req); free(used); return FSCLG_E_ARG; }
+    n++;
+  }
+  free(used);
+  r = fscl_amd_scan_blocks(s, sm, eval_range, req, n, block_bp, out);
+  free(req);
+  return r;
+}
+
+/* the test handle of fsclg_blocks_submit / fsclg_blocks_wait on the first device, as fscl_amd_surface_runs */
+int fscl_amd_blocks_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int n_runs, const double *la, int n_la,
+                         const fsclg_blocks_t *blk, int eval_range, const uint32_t *rows, int batch, fsclg_point_t *pts,
+                         double *bs, uint32_t *cnt) {
+  int r, slot = 0;
+  if (!s || !sm || (!runs && n_runs) || n_runs < 0) return FSCLG_E_ARG;
+  prepare(s, sm);
+  g_blocks_ms = 0.;
+  if (rows) {
+    double *nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
+    int i;
+    for (i = 0; i < s->n_snps; i++)
+      if (rows[i] >= (uint32_t)D.rm.n_dev_rows) { free(nul); return FSCLG_E_ARG; }
+    chr_null_sums_32(rows, nul);
+    slot = 1;
+    r = fsclg_slot_set_rows(D.ctx[0], slot, rows, nul);
+    free(nul);
+    if (r != FSCLG_OK) return r;
+  } else {
+    set_original_rows();
+  }
+  r = fsclg_blocks_submit(D.ctx[0], batch, slot, runs, n_runs, la, n_la, blk, eval_range);
+  if (r != FSCLG_OK) return r;
+  r = fsclg_blocks_wait(D.ctx[0], batch, pts, bs, cnt);
+  g_blocks_ms = fsclg_blocks_last_ms(D.ctx[0], batch);
+  return r;
+}
+
 /* ------------------------------------------------------ per-site likelihood terms
    The terms of single sm_likelihood walks (fsclg_sites_submit), on the data as loaded.  The local
    devices take contiguous shares of the requests balanced by window size; every device is

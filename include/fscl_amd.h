@@ -476,6 +476,106 @@ int fscl_amd_surface_runs(scan_t *scan_obj, sm_ptable_t *sm_p, const fsclg_run_t
                           int n_la, int eval_range, const uint32_t *rows, int batch, fsclg_point_t *pts, double *sm);
 double fscl_amd_surface_last_ms(void);
 
+/* ---- delete-one-block jackknife of sweep peaks (--jackknife-file) ---------------------
+   An interval on a peak that respects linkage: the peak's footprint is cut into contiguous genomic
+   blocks of block_bp, one block at a time is left out, the composite likelihood is re-maximised over
+   the surface's position and alpha grid, and the spread of the re-estimates is read.  The device
+   gives the surface's terms summed per block (fsclg_blocks_submit); the rest is host arithmetic.
+
+   fscl_amd_scan_blocks: the block sums of n surface requests (fscl_amd_surface_req_t, positions by
+   fscl_amd_surface_run) on the data as loaded, run as fscl_amd_scan_surface runs (slot 0; several
+   local devices take contiguous shares balanced by window size x cells, all submitted to before the
+   first wait; with several ranks, rank 0 alone evaluates).  A request's first block id b0 and block
+   count nb come from the least window_start and the greatest window_end of its positions, taken
+   from a surface evaluation of the same request, so the device's clamp never bites: block j holds
+   the sites with b0 + j == pos / block_bp.  Before any device call it refuses (FSCLG_E_ARG, with a
+   message naming the option to change) a request that needs more than 1024 blocks or a result
+   above $FSCL_AMD_BLOCKS_CAP bytes (default 2^30; fscl_amd_blocks_cap), both judged with
+   fscl_amd_blocks_bound: host only, the blocks of the widest windows the run's positions can have
+   (the exact ones or one site more on either side); -1 for a bad argument.
+   Result (owns its arrays; fscl_amd_blocks_free): hdr[i] the request, its run, block_bp, b0, nb and
+   where its n_pos points and n_pos * nb * n_la cells (position-major, then block, then alpha) start;
+   pts, bs, cnt are fsclg_blocks_wait's.
+
+   fscl_amd_scan_point_jackknife: the `top` scan points of greatest CLR, chosen as
+   fscl_amd_scan_point_surfaces chooses them, each centred on its sweep_pos with
+   fscl_amd_surface_alphas(la_lo, la_hi, n_grid, its fitted lalpha).
+
+   fscl_amd_jackknife_combine (host only) on bs / cnt [n_pos][nb][n_la], the positions' sweep_pos
+   and the alphas: for every block b, V_b[p][k] = the sum of bs[p][j][k] over j != b in ascending j
+   from +0.0; the block's estimate is the first strict maximum of V_b in position order, then alpha
+   order (ipos, ila, v = V_b there; a NaN never wins; ipos = ila = -1 and v NaN when every cell is
+   NaN), computed for the blocks that hold at least one term of some cell (has_terms; g of them).
+   The full estimate (out->ipos, ila, v) is the same over every block.  blocks[b].n_terms is cnt at
+   the full estimate's cell.  Over the g blocks, for theta in {sweep_pos, log alpha, CLR = 2 v}, with
+   mean the plain mean of theta_b in block order: se^2 = (g - 1) / g * sum (theta_b - mean)^2, bias =
+   (g - 1) (mean - theta_full); NaN (printed NA) when g < 2 or some delete-one surface is NaN alone.
+   top_shift: the first block of greatest |pos_b - pos|; top_loss: the first of greatest CLR loss;
+   n_edge_pos / n_edge_la: the delete-one maxima on the edge of the position / alpha grid (the
+   open_* warning: the grid may be too small).  Returns 1; 0 when every cell of the full surface is
+   NaN; -1 for a NULL or an empty array.
+
+   The estimator is an argmax on a grid: an SE of 0 means "no block moves it by one step", and the
+   jackknife of a non-smooth estimator is a guide, not a theorem.  The background spectrum and the
+   tables are not re-estimated; the blocks are equal in bp and unweighted.
+
+   fscl_amd_jackknife_output (fname NULL: stdout; 0, or -1 if the file cannot be opened or a header
+   does not fit the arrays), per peak one row per block with terms:
+     [label TAB] chromosome TAB centre_pos TAB block_start TAB block_end TAB n_terms TAB loo_pos TAB
+       loo_alpha (%1.3e) TAB loo_clr (%1.2f) TAB d_pos TAB d_logalpha (%1.4f) TAB d_clr (%1.2f)
+   (block_start = (b0 + j) * block_bp, block_end = block_start + block_bp - 1; the first and the last
+   block also hold what lies beyond them), then
+     [label TAB] chromosome TAB centre_pos TAB summary TAB n_pos TAB n_alpha TAB n_blocks (g) TAB pos TAB
+       alpha TAB clr TAB se_pos (%1.1f) TAB se_logalpha (%1.4f) TAB se_clr (%1.2f) TAB bias_pos TAB
+       bias_logalpha TAB top_shift_block TAB top_loss_block (their block_start) TAB n_edge_pos TAB n_edge_alpha
+   with NA where a value does not exist. */
+#define FSCL_AMD_BLOCKS_MAX_NB 1024
+typedef struct {
+  int32_t chr, centre_pos, halfwidth, step, n_la, point;
+  int32_t start_pos, n_pos;  /* the run evaluated: start_pos + p * step, p < n_pos */
+  int32_t block_bp, b0, nb, pad;
+  uint64_t pos_off, cell_off;
+  double la[FSCL_AMD_SURFACE_MAX_LA];
+} fscl_amd_blocks_hdr_t;
+typedef struct {
+  int n;  /* peaks */
+  fscl_amd_blocks_hdr_t *hdr;
+  fsclg_point_t *pts;
+  double *bs;
+  uint32_t *cnt;
+  size_t n_pos, n_cells;
+  unsigned long long n_terms;
+} fscl_amd_blocks_t;
+typedef struct {
+  int32_t block, has_terms, ipos, ila;
+  uint32_t n_terms;
+  int32_t pad;
+  double v;
+} fscl_amd_jack_block_t;
+typedef struct {
+  int32_t n_pos, n_la, nb, g, ipos, ila, top_shift, top_loss, n_edge_pos, n_edge_la;
+  double v, se_pos, se_la, se_clr, bias_pos, bias_la, bias_clr;
+} fscl_amd_jack_summary_t;
+int fscl_amd_scan_blocks(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, const fscl_amd_surface_req_t *req, int n,
+                         int block_bp, fscl_amd_blocks_t *out);
+int fscl_amd_scan_point_jackknife(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, int top, int halfwidth, int step,
+                                  double la_lo, double la_hi, int n_grid, int block_bp, fscl_amd_blocks_t *out);
+void fscl_amd_blocks_free(fscl_amd_blocks_t *r);
+size_t fscl_amd_blocks_cap(void);
+int fscl_amd_blocks_bound(const scan_t *scan_obj, const fsclg_run_t *run, int eval_range, int block_bp, int *b0, int *nb);
+int fscl_amd_jackknife_combine(const double *bs, const uint32_t *cnt, int n_pos, int nb, int n_la, const int32_t *pos,
+                               const double *la, fscl_amd_jack_block_t *blocks /* [nb] */, fscl_amd_jack_summary_t *out);
+int fscl_amd_jackknife_output(const char *fname, const scan_t *scan_obj, const fscl_amd_blocks_t *r, const char *prepend_label);
+/* fsclg_blocks_submit / fsclg_blocks_wait on the first device, for any runs (the device entry's test
+   handle): la holds n_runs lists of n_la values, blk one (block_bp, b0, nb) per run; pts sum(count)
+   points, bs and cnt sum(count * nb) * n_la cells; rows and batch as fscl_amd_surface_runs.
+   fscl_amd_blocks_last_ms: the block kernel's milliseconds of the last evaluation (the slowest
+   device's). */
+int fscl_amd_blocks_runs(scan_t *scan_obj, sm_ptable_t *sm_p, const fsclg_run_t *runs, int n_runs, const double *la,
+                         int n_la, const fsclg_blocks_t *blk, int eval_range, const uint32_t *rows, int batch,
+                         fsclg_point_t *pts, double *bs, uint32_t *cnt);
+double fscl_amd_blocks_last_ms(void);
+
 /* ---- per-site likelihood terms (--sites-file) --------------------------------------
    The data axis of a sweep position: which sites made this CLR.  A walk is one sm_likelihood
    (sm-search.c:105-150) at (chromosome index, position, log alpha); its header and terms are

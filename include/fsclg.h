@@ -306,6 +306,39 @@ int fsclg_surface_wait(fsclg_ctx *c, int batch, fsclg_point_t *pts /* sum(count)
                        double *sm /* sum(count) * n_la, position-major */);
 double fsclg_surface_last_ms(fsclg_ctx *c, int batch);
 
+/* Block sums of the surface: the surface's terms summed per contiguous genomic block, the input of a
+   delete-one-block jackknife.  Runs, alpha lists, batch, slot, eval_range and window null sums are
+   fsclg_surface_submit's; run i also has blk[i]: block_bp >= 1, a first block id b0 >= 0 and a block
+   count nb in [1, 1024].  A site at position x belongs to block j = clamp(x / block_bp - b0, 0, nb - 1)
+   (integer division): the first and the last block absorb whatever lies beyond them, no term is ever
+   dropped.  With item(p, j) = (the (position, block) pairs of the positions before p, runs in order) +
+   j, and cell(p, j, k) = item(p, j) * n_la + k -- position-major, then block, then alpha --
+     bs[cell]   the strictly sequential sum, from +0.0 and in ascending site index, of the terms of the
+                walk of sm_likelihood at position p and la[k] whose sites lie in block j (+0.0: none);
+     cnt[cell]  the number of those terms;
+     pts[p]     what init_scan_result gives at the position, with (lalpha, sm_logl) the first strict
+                maximum, in list order from the reference's (LOG_AD_MAX, -DBL_MAX) state, of V[p][k] +
+                null_logl, V[p][k] the sum of bs[p][0 .. nb)[k] in ascending j from +0.0, clr = 2 V at
+                that maximum (2 (sm_logl - null_logl) when nothing beat the state), cost the terms /
+                1024 of the position's walks.
+   The terms are the values fsclg_sites_wait stores for the same walk, and the walk's sites are its
+   [nearest - nl, nearest + nr]; an alpha whose nearest SNP is already outside log(alpha d) <=
+   LOG_AD_MAX has cnt = 0 everywhere.  Every byte of the three outputs is written.  The same input
+   gives the same bytes on every batch and slot and however the kernel chunks the runs (every sum has
+   a fixed order, nothing is accumulated across workgroups, no atomic is on the result path).
+   Error codes as fsclg_surface_submit's, and FSCLG_E_ARG for block_bp < 1, b0 < 0, nb outside
+   [1, 1024] or more cells than an int of bytes addresses; FSCLG_E_STATE from the wait when the batch
+   holds no block sums.  fsclg_blocks_last_ms: the kernel's own time of the batch's last launch. */
+typedef struct {
+  int32_t block_bp, b0, nb, pad;
+} fsclg_blocks_t;
+int fsclg_blocks_submit(fsclg_ctx *c, int batch, int slot, const fsclg_run_t *runs, int n_runs,
+                        const double *la /* [n_runs][n_la] */, int n_la, const fsclg_blocks_t *blk /* [n_runs] */,
+                        int eval_range);
+int fsclg_blocks_wait(fsclg_ctx *c, int batch, fsclg_point_t *pts /* sum(count) */,
+                      double *bs /* sum(count * nb) * n_la */, uint32_t *cnt /* as bs */);
+double fsclg_blocks_last_ms(fsclg_ctx *c, int batch);
+
 /* Per-site likelihood terms: the data axis of a sweep position.  A request is one walk of
    sm_likelihood (sm-search.c:105-150) -- a chromosome, a position and a log alpha, any double
    >= LOG_AD_MIN (-20), not only a value of the alpha grid -- on the rows a slot holds.  Its header's

@@ -15,6 +15,7 @@ fails loudly without it.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from pathlib import Path
 
@@ -126,6 +127,11 @@ class SurfacesT(C.Structure):  # fscl_amd_surfaces_t
                 ("n_cells", C.c_size_t), ("n_terms", C.c_ulonglong)]
 
 
+class ConditionalT(C.Structure):  # fscl_amd_conditional_t
+    _fields_ = [("n_blocks", C.c_int), ("blk", C.c_void_p), ("rows", C.c_void_p), ("given", C.c_void_p),
+                ("n_rows", C.c_size_t), ("n_given", C.c_size_t), ("n_terms", C.c_ulonglong), ("fold_s", C.c_double)]
+
+
 class BlocksT(C.Structure):  # fscl_amd_blocks_t
     _fields_ = [("n", C.c_int), ("hdr", C.c_void_p), ("pts", C.c_void_p), ("bs", C.c_void_p), ("cnt", C.c_void_p),
                 ("n_pos", C.c_size_t), ("n_cells", C.c_size_t), ("n_terms", C.c_ulonglong)]
@@ -182,6 +188,10 @@ EXPORTS = [
     "fscl_amd_scan_blocks", "fscl_amd_scan_point_jackknife", "fscl_amd_blocks_free", "fscl_amd_blocks_cap",
     "fscl_amd_blocks_bound", "fscl_amd_jackknife_combine", "fscl_amd_jackknife_output", "fscl_amd_blocks_runs",
     "fscl_amd_blocks_last_ms",
+    "fsclg_cond_submit", "fsclg_cond_wait", "fsclg_cond_last_ms",
+    "fscl_amd_cond_clip", "fscl_amd_cond_given_terms", "fscl_amd_cond_base", "fscl_amd_conditional_cap",
+    "fscl_amd_conditional_error", "fscl_amd_conditional_check", "fscl_amd_scan_conditional", "fscl_amd_conditional_output", "fscl_amd_conditional_free",
+    "fscl_amd_conditional_last_ms", "fscl_amd_cond_runs",
 ]
 
 
@@ -300,6 +310,17 @@ def _load() -> C.CDLL:
         "fscl_amd_blocks_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(RunT), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
         "fscl_amd_blocks_last_ms": (C.c_double, []),
+        "fscl_amd_cond_clip": (C.c_int, [P(ScanT), C.c_void_p, C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]),
+        "fscl_amd_cond_base": (C.c_double, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int)]),
+        "fscl_amd_conditional_cap": (C.c_size_t, []),
+        "fscl_amd_conditional_error": (C.c_char_p, []),
+        "fscl_amd_scan_conditional": (C.c_int, [P(ScanT), P(SmPtableT), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_int, C.c_int, C.c_double, P(ConditionalT)]),
+        "fscl_amd_conditional_output": (C.c_int, [C.c_char_p, P(ScanT), P(ConditionalT), C.c_char_p]),
+        "fscl_amd_conditional_free": (None, [P(ConditionalT)]),
+        "fscl_amd_conditional_last_ms": (C.c_double, []),
+        "fscl_amd_cond_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(RunT), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -1146,6 +1167,146 @@ def nearest_sweep(sweeps, chrom: int, pos: int) -> int:
     return int(get_lib().fscl_amd_nearest_sweep(a.ctypes.data if len(a) else None, len(a), int(chrom), int(pos)))
 
 
+# fscl_amd_cond_row_t: one candidate position of a conditional scan -- its sweep_pos, the global site interval it
+# owns (lo > hi: none), the sites of it inside the window, the kernel point's log alpha, cond_clr, the base A,
+# V at that alpha and the window null sum N
+COND_ROW_DTYPE = np.dtype([("pos", "i4"), ("lo", "i4"), ("hi", "i4"), ("n_terms", "i4"), ("lalpha", "f8"), ("cond_clr", "f8"),
+                           ("base", "f8"), ("v", "f8"), ("null_logl", "f8")])
+# fscl_amd_cond_block_t: one (round, chromosome) -- its rows and given sweeps in the flat arrays, the row of
+# greatest cond_clr (-1: none) and whether it joined the given sweeps
+COND_BLOCK_DTYPE = np.dtype([("chr", "i4"), ("round", "i4"), ("n_pos", "i4"), ("n_given", "i4"), ("row_off", "u8"),
+                             ("given_off", "u8"), ("max_row", "i4"), ("added", "i4")])
+assert COND_ROW_DTYPE.itemsize == 56 and COND_BLOCK_DTYPE.itemsize == 40
+COND_MAX_GIVEN, COND_MAX_ROUNDS = 64, 8
+
+
+class CondBlock:
+    """One round and chromosome of a conditional scan: ``hdr`` (a COND_BLOCK_DTYPE record), ``rows`` (COND_ROW_DTYPE, one
+    per position) and ``given`` (SWEEP_DTYPE: the sweeps held fixed in this round, on this chromosome)."""
+
+    def __init__(self, hdr, rows, given):
+        self.hdr, self.rows, self.given = hdr, rows, given
+
+
+def cond_clip(scan, given, chrom: int, pos: int):
+    """(sweep_pos, lo, hi): the de-collided position of a candidate at ``pos`` and the global site interval it owns
+    against the ``given`` sweeps (chromosome index, pos, alpha) of its chromosome; lo > hi: none.  Host only."""
+    a = _sweeps(given)
+    sp, lo, hi = C.c_int(), C.c_int(), C.c_int()
+    if get_lib().fscl_amd_cond_clip(scan, a.ctypes.data if len(a) else None, len(a), int(chrom), int(pos), C.byref(sp),
+                                    C.byref(lo), C.byref(hi)) != 0:
+        raise ValueError("cond_clip: a chromosome of the scan")
+    return sp.value, lo.value, hi.value
+
+
+def cond_base(g, chr_start_index: int, lo: int, hi: int, window_start: int, window_end: int):
+    """(A, n): the sequential sum from +0.0 of g[i - chr_start_index] over the sites i of [lo, hi] inside the window, in
+    ascending order, and their count.  Host only."""
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    a, b = max(int(lo), int(window_start)), min(int(hi), int(window_end))
+    if a <= b and not (0 <= a - int(chr_start_index) and b - int(chr_start_index) < len(g)):
+        raise ValueError("cond_base: the interval leaves g")
+    n = C.c_int()
+    v = get_lib().fscl_amd_cond_base(g.ctypes.data, int(chr_start_index), int(lo), int(hi), int(window_start), int(window_end),
+                                     C.byref(n))
+    return float(v), n.value
+
+
+def conditional_cap() -> int:
+    return int(get_lib().fscl_amd_conditional_cap())
+
+
+_cond_last = {"n_terms": 0, "fold_s": 0.0}
+
+
+def conditional_last_terms() -> int:
+    """The device's walk terms of the last scan_conditional call."""
+    return _cond_last["n_terms"]
+
+
+def conditional_last_fold_s() -> float:
+    """Host seconds of the base folds of the last scan_conditional call."""
+    return _cond_last["fold_s"]
+
+
+def scan_conditional(scan, tables, given, halfwidth: int = 0, step: int = 1000, alphas=None, rounds: int = 1,
+                     min_clr: float = 0.0, eval_range: int = 81920) -> list:
+    """The conditional sweep scan (include/fscl_amd.h): the likelihood ratio of one more sweep at every position
+    chromosome start + k * step (within ``halfwidth`` of a given sweep when it is > 0), given the sweeps ``given``
+    (chromosome index, pos, alpha) held fixed; ``alphas``: ascending log alphas (default surface_alphas()).  Returns
+    a list of CondBlock, per round the chromosomes that hold a given sweep.  The given sweeps stay fixed, ownership
+    goes by distance alone and the likelihood is composite: the ratio describes, it is not a calibrated test."""
+    g = _sweeps(given)
+    la = np.ascontiguousarray(surface_alphas() if alphas is None else alphas, dtype=np.float64).reshape(-1)
+    res = ConditionalT()
+    r = get_lib().fscl_amd_scan_conditional(scan, tables, int(eval_range), g.ctypes.data if len(g) else None, len(g), int(halfwidth),
+                                            int(step), la.ctypes.data if len(la) else None, len(la), int(rounds), float(min_clr),
+                                            C.byref(res))
+    if r == -1:
+        raise ValueError("scan_conditional: " + (get_lib().fscl_amd_conditional_error() or b"bad argument").decode())
+    _curve_check(r, "fscl_amd_scan_conditional")
+    nb, nr, ng = int(res.n_blocks), int(res.n_rows), int(res.n_given)
+    blk, rows, gv = np.zeros(nb, dtype=COND_BLOCK_DTYPE), np.zeros(nr, dtype=COND_ROW_DTYPE), np.zeros(ng, dtype=SWEEP_DTYPE)
+    for a, ptr, n in ((blk, res.blk, nb), (rows, res.rows, nr), (gv, res.given, ng)):
+        if n:
+            C.memmove(a.ctypes.data, ptr, n * a.dtype.itemsize)
+    _cond_last["n_terms"], _cond_last["fold_s"] = int(res.n_terms), float(res.fold_s)
+    get_lib().fscl_amd_conditional_free(C.byref(res))
+    return [CondBlock(h, rows[int(h["row_off"]):int(h["row_off"]) + int(h["n_pos"])].copy(),
+                      gv[int(h["given_off"]):int(h["given_off"]) + int(h["n_given"])].copy()) for h in blk]
+
+
+def conditional_output(path, scan, blocks, label=None) -> None:
+    """The --conditional-file format (include/fscl_amd.h, README): per block one row per position, then one summary
+    row.  Host only."""
+    n = len(blocks)
+    blk = np.zeros(max(n, 1), dtype=COND_BLOCK_DTYPE)
+    ro = go = 0
+    for i, b in enumerate(blocks):
+        blk[i] = b.hdr
+        blk["n_pos"][i], blk["n_given"][i], blk["row_off"][i], blk["given_off"][i] = len(b.rows), len(b.given), ro, go
+        ro += len(b.rows)
+        go += len(b.given)
+    rows = np.concatenate([np.ascontiguousarray(b.rows, dtype=COND_ROW_DTYPE) for b in blocks]) if n else np.zeros(0, COND_ROW_DTYPE)
+    gv = np.concatenate([np.ascontiguousarray(b.given, dtype=SWEEP_DTYPE) for b in blocks]) if n else np.zeros(0, SWEEP_DTYPE)
+    res = ConditionalT(n, blk.ctypes.data, rows.ctypes.data if len(rows) else None, gv.ctypes.data if len(gv) else None,
+                       len(rows), len(gv), 0, 0.0)
+    if get_lib().fscl_amd_conditional_output(_b(path), scan, C.byref(res), _b(label)) != 0:
+        raise ValueError(f"conditional_output: blocks inside their arrays and {path} writable")
+
+
+def cond_runs(scan, tables, runs, alphas, clip, eval_range: int = 81920, rows=None, batch: int = 0, pts=None, sm=None):
+    """fsclg_cond_submit / fsclg_cond_wait on the scan's first device (the shim-level handle, as surface_runs):
+    ``clip`` holds one global site-index pair (lo, hi) per position.  Returns (points [sum(count)], values
+    [sum(count)][n_la])."""
+    arr = (RunT * max(len(runs), 1))(*[RunT(*[int(v) for v in r]) for r in runs])
+    la = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(runs), -1) if len(runs) else np.zeros((0, 1))
+    n, k = sum(max(int(r[3]), 0) for r in runs), la.shape[1]
+    cl = np.ascontiguousarray(clip, dtype=np.int32).reshape(-1)
+    if cl.size != 2 * n:
+        raise ValueError("clip must hold one (lo, hi) pair per position")
+    if pts is None:
+        pts = np.zeros(max(n, 1), dtype=_POINT_RAW)
+    if sm is None:
+        sm = np.zeros(max(n, 1) * k, dtype=np.float64)
+    if pts.dtype != _POINT_RAW or len(pts) < n or sm.dtype != np.float64 or sm.size < n * k or \
+            not (pts.flags.c_contiguous and sm.flags.c_contiguous):
+        raise ValueError("pts / sm must be contiguous arrays of sum(count) points and sum(count) * n_la values")
+    rp = None
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        if len(rows) != scan.contents.n_snps:
+            raise ValueError("rows must hold one row per site")
+        rp = rows.ctypes.data
+    _curve_check(get_lib().fscl_amd_cond_runs(scan, tables, arr, len(runs), la.ctypes.data, k, cl.ctypes.data if n else None,
+                                              int(eval_range), rp, int(batch), pts.ctypes.data, sm.ctypes.data), "fscl_amd_cond_runs")
+    return pts[:n], sm.reshape(-1)[:n * k].reshape(n, k)
+
+
+def conditional_last_ms() -> float:
+    return float(get_lib().fscl_amd_conditional_last_ms())
+
+
 def simulate(scan, tables, sweeps=(), seed: int = 0xFD821A6, rep: int = 0):
     """One replicate under the sweep model at the scan's own sites (include/fscl_amd.h): the int32 array
     of drawn derived counts and the number of degenerate sites (which keep their observed count).
@@ -1393,7 +1554,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         tail_file=None, tail_df=2, tail_min_n=20, surface_file=None, surface_top=3, surface_halfwidth=None,
         surface_step=None, surface_alphas=(LOG_AD_MIN, LOG_AD_MAX, 33), surface_drop=2.0,
         jackknife_file=None, jackknife_top=3, jackknife_block=None, jackknife_halfwidth=None, jackknife_step=None,
-        jackknife_alphas=None):
+        jackknife_alphas=None, conditional_file=None, given_sweeps=(), conditional_halfwidth=0, conditional_step=None,
+        conditional_alphas=None, conditional_rounds=1, conditional_min_clr=0.0):
     """The fscl main() pipeline (fscl.c:316-337) in-process; returns the scan_t
     pointer (points(scan) reads the results).  permute_mode "throughput": the
     counter-based permutation test (set_permute_mode).  scan_mode "grid": the CLI's
@@ -1428,6 +1590,14 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         if jackknife_step < 1 or jackknife_block < 1:
             raise ValueError("jackknife_step and jackknife_block must be at least 1")
         _surface_grid(*jackknife_alphas)  # (raises ValueError)
+    if conditional_file is not None:
+        conditional_step = int(small_grid_sp if conditional_step is None else conditional_step)
+        conditional_alphas = surface_alphas if conditional_alphas is None else conditional_alphas
+        if conditional_step < 1:
+            raise ValueError("conditional_step must be at least 1")
+        if int(conditional_halfwidth) < 0 or not 1 <= int(conditional_rounds) <= COND_MAX_ROUNDS:
+            raise ValueError("conditional_halfwidth must be >= 0 and conditional_rounds 1 .. 8")
+        _surface_grid(*conditional_alphas)  # (raises ValueError)
     if tail_file is not None:
         _tail_df(tail_df)
         if int(n_permute) <= 0:
@@ -1470,6 +1640,18 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         jackknife_output(jackknife_file, scan,
                          scan_point_jackknife(scan, tab, jackknife_top, jackknife_halfwidth, jackknife_step, jackknife_alphas,
                                               jackknife_block, eval_range), label)
+    if conditional_file is not None:  # the CLI's --conditional-file: one more sweep given the fixed ones
+        given = [as_sweep(w) for w in given_sweeps]
+        if not given:  # the scan point of greatest CLR (the first on a tie, never a NaN) at its fitted alpha
+            p = points(scan)
+            ok = [i for i in range(len(p)) if p["clr"][i] == p["clr"][i]]
+            if ok:
+                i = max(ok, key=lambda i: (p["clr"][i], -i))
+                given = [(int(p["chr"][i]), int(p["sweep_pos"][i]), math.exp(float(p["lalpha"][i])))]
+        conditional_output(conditional_file, scan,
+                           scan_conditional(scan, tab, given, conditional_halfwidth, conditional_step,
+                                            _surface_grid(*conditional_alphas), conditional_rounds, conditional_min_clr,
+                                            eval_range), label)
     if n_permute > 0 and scan_mode == "grid":
         scan_permute_grid(scan, tab, n_permute, permute_nbp, eval_range, small_grid_sp, large_grid_sp, scan_width_mb)
     elif n_permute > 0:

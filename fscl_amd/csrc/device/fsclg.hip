@@ -2738,6 +2738,130 @@ surface_kernel(Params P, const SurfChunk* __restrict__ chunks, const double* __r
   }
 }
 
+// ------------------------------------------------------------ conditional sweep scan
+// The surface with every walk cut to the sites the candidate sweep owns (fsclg_cond_submit): per position
+// a global site-index interval [lo, hi] comes with the runs (lo > hi: empty), and a walk's value is the
+// null sum plus, in walk order, the terms of its sites inside the interval.  surface_kernel's
+// decomposition and trip, as a symbol of its own: the clip is intersected with the window when the chunk
+// is set up, and with the walk per item.  The walk bounds nl, nr are those of the block's smallest alpha
+// on the unclipped walk; the left part then runs from min(near, hi) down to max(near - nl, lo) -- the
+// nearest SNP is its first site iff lo <= near <= hi -- and the right part from max(near + 1, lo) up to
+// min(near + nr, hi).  A clipped part is a contiguous piece of the unclipped one, so |d| stays
+// nondecreasing along it once the nearest SNP is inside the alpha's cut (surface_kernel's argument: the
+// sites the de-collision stepped over lie nearer than the nearest SNP), the lanes inside are still a
+// prefix of the trip, and exact_chunk_add folds them in walk order.  An alpha whose nearest SNP is past
+// its own cut has an empty walk, whether or not the clip holds the nearest SNP.  With the clip covering
+// the window every trip is surface_kernel's, site for site.  Results, point and counters as there.
+struct CondSmem {
+  SurfSmem s;
+  int lo[SURF_CH], hi[SURF_CH];  // the clip of each position, cut to its window
+};
+
+__device__ __forceinline__ void cond_block(CondSmem& C, const Params& P, int pi, const double* __restrict__ lap,
+                                           int k0, int nb, int lane) {
+  SurfSmem& S = C.s;
+  const Pt& pt = S.pt[pi];
+  const int near = pt.nearest, clo = C.lo[pi], chi = C.hi[pi];
+  const uint32_t usweep = (uint32_t)pt.sweep ^ POS_BIAS;
+  double la[SURF_B], acc[SURF_B];
+  uint32_t len[SURF_B];
+  bool alive[SURF_B];
+  const double lt0 = logt_dev(absdist(P.pr[phys(near)].x, usweep), P.logt3);
+#pragma unroll
+  for (int b = 0; b < SURF_B; b++) {
+    la[b] = lap[k0 + min(b, nb - 1)];
+    acc[b] = pt.N;
+    len[b] = 0;
+    alive[b] = b < nb && !(lt0 + la[b] > LOG_AD_MAX);  // the nearest SNP outside: an empty walk
+  }
+  if (alive[0] && clo <= chi) {
+    const double la0 = la[0];
+    auto outside = [&](int i) { return logt_dev(absdist(P.pr[phys(i)].x, usweep), P.logt3) + la0 > LOG_AD_MAX; };
+    const int e = group_search<64>(pt.wstart - 1, near, lane, [&](int m) { return outside(m); });
+    const int nl = near - e;
+    const bool ok1 = near + 1 <= pt.wend && !outside(near + 1);
+    const int f = group_search<64>(ok1 ? near + 1 : 0, ok1 ? pt.wend + 1 : 1, lane, [&](int m) { return !outside(m); });
+    const int nr = ok1 ? f - 1 - near : 0;
+    // (wstart <= clo <= chi <= wend: every bound below is a site of the window)
+    const int l0 = min(near, chi), l1 = max(near - nl, clo);      // left part, downwards: l0 .. l1
+    const int r0 = max(near + 1, clo), r1 = min(near + nr, chi);  // right part, upwards: r0 .. r1
+    auto trip = [&](int i, bool valid) {
+      uint2 s = make_uint2(usweep, 0u);
+      double lt = 0.0;
+      if (valid) {
+        s = P.pr[phys(i)];
+        lt = logt_dev(absdist(s.x, usweep), P.logt3);
+      }
+#pragma unroll
+      for (int b = 0; b < SURF_B; b++) {
+        if (!alive[b]) continue;  // (wave-uniform)
+        const double x = lt + la[b];
+        const bool in = valid && !(x > LOG_AD_MAX);
+        const unsigned long long m = __ballot(in);
+        if (m == 0ull) continue;
+        double t = 0.0;
+        if (in) t = surf_term(x, s.y, S, P);
+        const int lim = __popcll(m);  // the lanes inside are the first lim
+        acc[b] = exact_chunk_add(acc[b], t, lim);
+        len[b] += (uint32_t)lim;
+      }
+    };
+    for (int j0 = 0; j0 <= l0 - l1; j0 += 64) trip(l0 - (j0 + lane), j0 + lane <= l0 - l1);
+    for (int j0 = 0; j0 <= r1 - r0; j0 += 64) trip(r0 + j0 + lane, j0 + lane <= r1 - r0);
+  }
+#pragma unroll
+  for (int b = 0; b < SURF_B; b++)
+    if (lane == b && b < nb) { S.sm[pi][k0 + b] = acc[b]; S.len[pi][k0 + b] = len[b]; }
+}
+
+__global__ void __launch_bounds__(64 * SURF_WAVES)
+cond_kernel(Params P, const SurfChunk* __restrict__ chunks, const double* __restrict__ la_all, int n_la,
+            const int32_t* __restrict__ clip, double* __restrict__ sm_out) {
+  __shared__ CondSmem C;
+  SurfSmem& S = C.s;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int k = (int)blockIdx.x;
+  if (k >= P.n_cells) return;
+  const SurfChunk c = chunks[k];
+  for (int i = wave; i < c.count; i += SURF_WAVES) {
+    init_point_wave(S.pt[i], c.chr, c.start_pos + i * c.step, P, lane);
+    if (lane == 0) {  // (the lane that wrote the point)
+      C.lo[i] = max(clip[2 * (size_t)(c.out0 + i)], S.pt[i].wstart);
+      C.hi[i] = min(clip[2 * (size_t)(c.out0 + i) + 1], S.pt[i].wend);
+    }
+  }
+  __syncthreads();
+  const double* __restrict__ lap = la_all + (size_t)c.run * (size_t)n_la;
+  const int nblk = (n_la + SURF_B - 1) / SURF_B;
+  for (int it = wave; it < c.count * nblk; it += SURF_WAVES) {
+    const int pi = it / nblk, k0 = (it - pi * nblk) * SURF_B;
+    cond_block(C, P, pi, lap, k0, min(SURF_B, n_la - k0), lane);
+  }
+  __syncthreads();
+  for (int t = tid; t < c.count * n_la; t += 64 * SURF_WAVES) {  // consecutive lanes, consecutive doubles
+    const int pi = t / n_la;
+    sm_out[(size_t)c.out0 * (size_t)n_la + (size_t)t] = S.sm[pi][t - pi * n_la];
+  }
+  if (tid < c.count) {  // one store per point (P.out is host memory: no read-modify-write)
+    Pt& pt = S.pt[tid];
+    double best = -1.7976931348623157e308, bla = LOG_AD_MAX;
+    unsigned long long terms = 0;
+    for (int j = 0; j < n_la; j++) {
+      const double v = S.sm[tid][j];
+      if (v > best) { best = v; bla = lap[j]; }
+      terms += S.len[tid][j];
+    }
+    pt.la = bla; pt.sm = best; pt.clr = 2.0 * (best - pt.N);
+    fsclg_point_t o;
+    write_point(o, pt);
+    o.cost = (uint32_t)min(terms >> 10, 0xFFFFFFFFull);  // the position's terms / 1024
+    P.out[c.out0 + tid] = o;
+    atomicAdd(&P.stats[0], terms);                                   // the device counters, as any launch:
+    atomicAdd(&P.stats[1], (unsigned long long)pt.n_snps);           // terms, null-sum elements, walks
+    atomicAdd(&P.stats[2], (unsigned long long)n_la);
+  }
+}
+
 // ------------------------------------------------------------ block sums of the surface
 // The surface's terms summed per genomic block (fsclg_blocks_submit): for every position of dense runs,
 // every block j < nb of the run and every log alpha of the run's list, the strictly sequential sum, from
@@ -3747,7 +3871,7 @@ struct Slot {
 
 // what a batch holds between a submit and its wait
 enum BatchKind { BK_NONE, BK_SEARCH, BK_PROFILE, BK_CELLMAX, BK_CURVE, BK_SITES, BK_SAMPLE, BK_TAIL, BK_SURFACE,
-                 BK_BLOCKS };
+                 BK_BLOCKS, BK_COND };
 
 // one call of any kind in flight (a submit / wait pair: search, profile, cell maxima, curves, site
 // terms, sample, tail fit): its stream and events, the device and pinned host buffers of each kind,
@@ -3835,6 +3959,10 @@ struct Batch {
   int sfchunk_cap = 0, sfla_cap = 0, sfsm_cap = 0;
   int sf_n = 0, sf_nla = 0;         // positions and alphas per position of the submitted surfaces
   double sf_ms = 0.0;               // kernel time of the batch's last surface launch
+  // fsclg_cond_submit: the surface call's buffers, and the positions' clips (pinned, read by the kernel)
+  int32_t* p_cdclip = nullptr;
+  int cdclip_cap = 0;
+  double cd_ms = 0.0;               // kernel time of the batch's last conditional launch
   // fsclg_blocks_submit: the chunks, the alpha lists and the blocks' first sites (pinned, read by the kernel),
   // the block sums and counts (pinned, written by the kernel; the points are p_out), the device copy of the sums
   BlkChunk* p_bkchunks = nullptr;
@@ -4065,7 +4193,7 @@ int fsclg_close(fsclg_ctx* c) {
                     (void*)B.p_sterms, (void*)B.p_sdepth, (void*)B.p_sfreq, (void*)B.p_ssweeps,
                     (void*)B.p_tsamples, (void*)B.p_toff, (void*)B.p_tcnt, (void*)B.p_tx0, (void*)B.p_tout,
                     (void*)B.p_sfchunks, (void*)B.p_sfla, (void*)B.p_sfsm, (void*)B.p_bkchunks, (void*)B.p_bkla,
-                    (void*)B.p_bkbf, (void*)B.p_bkbs, (void*)B.p_bkcnt})
+                    (void*)B.p_bkbf, (void*)B.p_bkbs, (void*)B.p_bkcnt, (void*)B.p_cdclip})
       if (p) hipHostFree(p);
     if (B.d_bkbs) hipFree(B.d_bkbs);
     hipEventDestroy(B.ev0);
@@ -5427,7 +5555,7 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
       "the batch holds cell maxima (fsclg_cellmax_wait)", "the batch holds curves (fsclg_curve_wait)",
       "the batch holds site terms (fsclg_sites_wait)", "the batch holds a sample (fsclg_sample_wait)",
       "the batch holds a tail fit (fsclg_tail_wait)", "the batch holds surfaces (fsclg_surface_wait)",
-      "the batch holds block sums (fsclg_blocks_wait)"};
+      "the batch holds block sums (fsclg_blocks_wait)", "the batch holds a conditional scan (fsclg_cond_wait)"};
   if (B.holds != BK_SEARCH) return set_err(FSCLG_E_STATE, other[B.holds]);
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
@@ -5858,12 +5986,16 @@ unsigned long long fsclg_curve_forced(fsclg_ctx* c) {
 // window null sums (one covering cell per run); surface_kernel stores n_la values and one point per
 // position.  A chunk holds as many positions as give its workgroup about two items per wave (the result
 // does not depend on it).
-int fsclg_surface_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* runs, int n_runs, const double* la,
-                         int n_la, int eval_range) {
+// (clip: fsclg_cond_submit's site-index pair per position, cond_kernel; NULL: surface_kernel)
+static int surface_like_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* runs, int n_runs, const double* la,
+                               int n_la, int eval_range, const int32_t* clip, BatchKind kind) {
   if (!c || (!runs && n_runs) || n_runs < 0 || eval_range < 0) return set_err(FSCLG_E_ARG, "runs");
   if (batch < 0 || batch >= NBATCH || slot < 0 || slot >= NSLOT) return set_err(FSCLG_E_ARG, "batch/slot");
   if (n_la < 1 || n_la > SURF_MAX_LA) return set_err(FSCLG_E_ARG, "alphas per position outside [1, 64]");
   if (!la && n_runs) return set_err(FSCLG_E_ARG, "alpha lists");
+  if (kind == BK_COND && !clip)  // (before any state of the batch is touched)
+    for (int i = 0; i < n_runs; i++)
+      if (runs[i].count > 0) return set_err(FSCLG_E_ARG, "clip");
   if (!c->d_pr0 || !c->d_coef) return set_err(FSCLG_E_STATE, "tables/snps not set");
   Batch& B = c->batch[batch];
   if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
@@ -5881,7 +6013,9 @@ int fsclg_surface_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* r
     return set_err(FSCLG_E_ARG, "too many surface cells");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   B.n_cells = 0; B.nu = (int)nchunk; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
-  B.eval_range = eval_range; B.bp_resl = 0; B.sf_ms = 0.0; B.sf_n = (int)total; B.sf_nla = n_la;
+  B.eval_range = eval_range; B.bp_resl = 0; B.sf_n = (int)total; B.sf_nla = n_la;
+  if (kind == BK_COND) B.cd_ms = 0.0;
+  else B.sf_ms = 0.0;
   if (total > 0) {
     std::vector<fsclg_cell_t> cover;
     for (int i = 0; i < n_runs; i++)
@@ -5893,6 +6027,10 @@ int fsclg_surface_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* r
     if ((r = ensure_pinned(&B.p_sfla, &B.sfla_cap, n_runs * n_la))) return r;
     if ((r = ensure_pinned(&B.p_sfsm, &B.sfsm_cap, (int)(total * n_la)))) return r;
     memcpy(B.p_sfla, la, sizeof(double) * (size_t)n_runs * (size_t)n_la);
+    if (kind == BK_COND) {
+      if ((r = ensure_pinned(&B.p_cdclip, &B.cdclip_cap, (int)(2 * total)))) return r;
+      memcpy(B.p_cdclip, clip, sizeof(int32_t) * 2 * (size_t)total);
+    }
     int nc = 0, o = 0;
     for (int i = 0; i < n_runs; i++)
       for (int j = 0; j < runs[i].count; j += CH) {
@@ -5903,20 +6041,30 @@ int fsclg_surface_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* r
     HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
     Params P = make_params(c, B, slot, nc, 3, eval_range, 0);
     HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
-    hipLaunchKernelGGL(surface_kernel, dim3(nc), dim3(64 * SURF_WAVES), 0, B.stream, P, (const SurfChunk*)B.p_sfchunks,
-                       (const double*)B.p_sfla, n_la, B.p_sfsm);
-    HIPCHK(hipGetLastError(), "launch surface_kernel");
+    if (kind == BK_COND)
+      hipLaunchKernelGGL(cond_kernel, dim3(nc), dim3(64 * SURF_WAVES), 0, B.stream, P, (const SurfChunk*)B.p_sfchunks,
+                         (const double*)B.p_sfla, n_la, (const int32_t*)B.p_cdclip, B.p_sfsm);
+    else
+      hipLaunchKernelGGL(surface_kernel, dim3(nc), dim3(64 * SURF_WAVES), 0, B.stream, P, (const SurfChunk*)B.p_sfchunks,
+                         (const double*)B.p_sfla, n_la, B.p_sfsm);
+    HIPCHK(hipGetLastError(), kind == BK_COND ? "launch cond_kernel" : "launch surface_kernel");
     HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
   }
-  B.holds = BK_SURFACE;
+  B.holds = kind;
   c->slot[slot].users++;
   return FSCLG_OK;
 }
 
-int fsclg_surface_wait(fsclg_ctx* c, int batch, fsclg_point_t* pts, double* sm) {
+int fsclg_surface_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* runs, int n_runs, const double* la,
+                         int n_la, int eval_range) {
+  return surface_like_submit(c, batch, slot, runs, n_runs, la, n_la, eval_range, nullptr, BK_SURFACE);
+}
+
+static int surface_like_wait(fsclg_ctx* c, int batch, fsclg_point_t* pts, double* sm, BatchKind kind) {
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
-  if (B.holds != BK_SURFACE) return set_err(FSCLG_E_STATE, "no surfaces submitted on the batch");
+  if (B.holds != kind)
+    return set_err(FSCLG_E_STATE, kind == BK_COND ? "no conditional scan submitted on the batch" : "no surfaces submitted on the batch");
   if ((!pts || !sm) && B.sf_n) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   B.holds = BK_NONE;
@@ -5927,13 +6075,34 @@ int fsclg_surface_wait(fsclg_ctx* c, int batch, fsclg_point_t* pts, double* sm) 
   memcpy(pts, B.p_out, sizeof(fsclg_point_t) * (size_t)n);
   memcpy(sm, B.p_sfsm, sizeof(double) * (size_t)n * (size_t)B.sf_nla);
   int r, flags = 0;
-  if ((r = batch_time(c, B, 1, &B.sf_ms))) return r;
+  if ((r = batch_time(c, B, 1, kind == BK_COND ? &B.cd_ms : &B.sf_ms))) return r;
   for (int i = 0; i < n; i++) flags |= pts[i].flags;
   return flags_err(flags);
 }
 
+int fsclg_surface_wait(fsclg_ctx* c, int batch, fsclg_point_t* pts, double* sm) {
+  return surface_like_wait(c, batch, pts, sm, BK_SURFACE);
+}
+
 double fsclg_surface_last_ms(fsclg_ctx* c, int batch) {
   return c && batch >= 0 && batch < NBATCH ? c->batch[batch].sf_ms : 0.0;
+}
+
+// ------------------------------------------------------------ conditional sweep scan (host side)
+// fsclg_surface_submit with one site-index pair (lo, hi) per position, copied like the runs: cond_kernel
+// adds only the terms of the sites inside it.  The checks, slot, window null sums, chunking and results
+// are the surface's.
+int fsclg_cond_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* runs, int n_runs, const double* la, int n_la,
+                      const int32_t* clip, int eval_range) {
+  return surface_like_submit(c, batch, slot, runs, n_runs, la, n_la, eval_range, clip, BK_COND);
+}
+
+int fsclg_cond_wait(fsclg_ctx* c, int batch, fsclg_point_t* pts, double* sm) {
+  return surface_like_wait(c, batch, pts, sm, BK_COND);
+}
+
+double fsclg_cond_last_ms(fsclg_ctx* c, int batch) {
+  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].cd_ms : 0.0;
 }
 
 // ------------------------------------------------------------ block sums of the surface (host side)

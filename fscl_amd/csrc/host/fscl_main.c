@@ -8,6 +8,7 @@
  * semantics (all blocks form one genome, one chromosome per block, --max-only
  * prints the maximum of each block); -b reads the format --output-bs writes.
  */
+#include <errno.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -36,6 +37,17 @@ static void list_add(strlist_t *l, const char *arg) {
   l->v = realloc(l->v, sizeof(char *) * (size_t)(l->n + 1));
   if (!l->v) { fprintf(stderr, "out of memory (options)\n"); exit(1); }
   l->v[l->n++] = strdup(arg);
+}
+
+/* a whole decimal integer within the int range: 1 and *out, else 0 */
+static int int_option(const char *t, int *out) {
+  char *end = NULL;
+  long v;
+  errno = 0;
+  v = strtol(t, &end, 10);
+  if (end == t || *end || errno || v < -2147483647L || v > 2147483647L) return 0;
+  *out = (int)v;
+  return 1;
 }
 
 /* "chr:pos:alpha" options into sweeps; a bad one is fatal before anything runs on the device */
@@ -117,6 +129,11 @@ int main(int argc, char **argv) {
   int surface_top = 3, surface_halfwidth = -1, surface_step = -1, surface_n = 33;
   double surface_drop = 2.0, surface_lo = LOG_AD_MIN, surface_hi = LOG_AD_MAX;
   char *jackknife_fname = NULL, *jackknife_alphas = NULL;
+  char *cond_fname = NULL, *cond_alphas = NULL;
+  strlist_t given_sweep = {NULL, 0};
+  char *cond_halfwidth_s = NULL, *cond_step_s = NULL, *cond_rounds_s = NULL, *cond_min_clr_s = NULL; /* (NULL: not given) */
+  int cond_halfwidth = 0, cond_step = 1, cond_rounds = 1, cond_n = -1;
+  double cond_min_clr = 0.0, cond_lo = LOG_AD_MIN, cond_hi = LOG_AD_MAX;
   int jackknife_top = 3, jackknife_block = -1, jackknife_halfwidth = -1, jackknife_step = -1, jackknife_n = 33;
   double jackknife_lo = LOG_AD_MIN, jackknife_hi = LOG_AD_MAX;
   int tail_df = 2, tail_min_n = 20;
@@ -190,6 +207,17 @@ int main(int argc, char **argv) {
       {0, "surface-drop", &surface_drop, T_DBL, "log-likelihood drop of the region in --surface-file (default 2.0, as --alpha-drop; a joint "
                                                 "two-parameter 95 % region under the chi-square reading would be about 3.0; descriptive: "
                                                 "the likelihood is composite)"},
+      {0, "conditional-file", &cond_fname, T_STR, "write the conditional sweep scan -- the likelihood ratio of one more sweep at every "
+                                                  "grid position, given the --given-sweep sweeps held fixed -- to this file"},
+      {0, "given-sweep", &given_sweep, T_LIST, "chr:pos:alpha of a sweep held fixed in --conditional-file (may be given several times; "
+                                               "default: the scan point of greatest CLR at its fitted alpha)"},
+      {0, "conditional-halfwidth", &cond_halfwidth_s, T_STR, "evaluate only the positions within this many bp of a given sweep "
+                                                           "(default 0: the whole chromosome)"},
+      {0, "conditional-step", &cond_step_s, T_STR, "spacing in bp of the --conditional-file positions (default: the -g spacing; at least 1)"},
+      {0, "conditional-alphas", &cond_alphas, T_STR, "LO:HI:N, the candidate's alpha grid (default: the --surface-alphas value)"},
+      {0, "conditional-rounds", &cond_rounds_s, T_STR, "forward selection: after a round each chromosome's position of greatest conditional "
+                                                     "CLR joins the given sweeps (1 .. 8, default 1)"},
+      {0, "conditional-min-clr", &cond_min_clr_s, T_STR, "a round's maximum joins the given sweeps only above this conditional CLR (default 0)"},
       {0, "jackknife-file", &jackknife_fname, T_STR, "write a delete-one-block jackknife of the scan points of greatest CLR (the "
                                                      "re-maximised position, alpha and CLR with each genomic block left out, and their "
                                                      "standard errors) to this file"},
@@ -357,6 +385,44 @@ int main(int argc, char **argv) {
       stop = 1;
     }
   }
+  if (cond_fname && dont_scan && given_sweep.n == 0) {
+    logmsg(MSG_ERROR, "Error: --conditional-file with --no-scan needs explicit --given-sweep sweeps.\n");
+    stop = 1;
+  }
+  if (!cond_fname && (given_sweep.n || cond_halfwidth_s || cond_step_s || cond_rounds_s || cond_min_clr_s || cond_alphas)) {
+    logmsg(MSG_ERROR, "Error: --given-sweep and the --conditional-* options need --conditional-file.\n");
+    stop = 1;
+  }
+  cond_step = small_grid_sp;
+  if (cond_step_s && !int_option(cond_step_s, &cond_step)) cond_step = 0;
+  if (cond_fname && cond_step < 1) { logmsg(MSG_ERROR, "Error: --conditional-step must be at least 1.\n"); stop = 1; }
+  if (cond_halfwidth_s && !int_option(cond_halfwidth_s, &cond_halfwidth)) cond_halfwidth = -1;
+  if (cond_halfwidth < 0) { logmsg(MSG_ERROR, "Error: --conditional-halfwidth must be >= 0.\n"); stop = 1; }
+  if (cond_rounds_s && !int_option(cond_rounds_s, &cond_rounds)) cond_rounds = 0;
+  if (cond_rounds < 1 || cond_rounds > FSCL_AMD_COND_MAX_ROUNDS) { logmsg(MSG_ERROR, "Error: --conditional-rounds must be 1 .. 8.\n"); stop = 1; }
+  if (cond_min_clr_s) {
+    char *end = NULL;
+    cond_min_clr = strtod(cond_min_clr_s, &end);
+    if (end == cond_min_clr_s || *end || !(cond_min_clr == cond_min_clr)) { logmsg(MSG_ERROR, "Error: --conditional-min-clr must be a number.\n"); stop = 1; }
+  }
+  if (cond_alphas) {
+    char tail_c = 0;
+    double probe[FSCL_AMD_SURFACE_MAX_LA];
+    if (sscanf(cond_alphas, "%lf:%lf:%d%c", &cond_lo, &cond_hi, &cond_n, &tail_c) != 3 ||
+        fscl_amd_surface_alphas(cond_lo, cond_hi, cond_n, NAN, probe) < 1) {
+      logmsg(MSG_ERROR, "Error: --conditional-alphas must be LO:HI:N with -20 <= LO <= HI <= 4 (natural-log alpha), 1 <= N <= 63, "
+                        "and LO < HI unless N is 1 (not \"%s\").\n", cond_alphas);
+      stop = 1;
+    }
+  }
+  for (i = 0; i < given_sweep.n; i++) { /* (the chromosome names are checked once the data is loaded, before the scan) */
+    const char *t = given_sweep.v[i], *c2 = strrchr(t, ':');
+    const double a = c2 ? atof(c2 + 1) : 0.0;
+    if (!c2 || !(a > 0.0) || !(log(a) >= LOG_AD_MIN && log(a) <= LOG_AD_MAX)) {
+      logmsg(MSG_ERROR, "Error: --given-sweep=%s: expected chr:pos:alpha, alpha positive with its natural log within [-20, 4].\n", t);
+      stop = 1;
+    }
+  }
   if (jackknife_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --jackknife-file needs the scan (not with --no-scan).\n"); stop = 1; }
   if (jackknife_top < 0) { logmsg(MSG_ERROR, "Error: --jackknife-top must be >= 0.\n"); stop = 1; }
   if (jackknife_block == -1) jackknife_block = large_grid_sp / 2 > 1 ? large_grid_sp / 2 : 1;
@@ -387,12 +453,20 @@ int main(int argc, char **argv) {
                : load_snp_input(snp_fname, include_invariant, minimum_obs_depth);
   fsp = background_fsp(s, force_neutral, bs_fname, include_invariant);
   if (output_bs_fname) output_background_fs(output_bs_fname, s, fsp);
-  need_tables = !dont_scan || simulate_fname || bootstrap_fname;
+  if (!cond_alphas) { cond_lo = surface_lo; cond_hi = surface_hi; cond_n = surface_n; }
+  need_tables = !dont_scan || simulate_fname || bootstrap_fname || cond_fname;
   if (need_tables) {
     sm_ptable_t *sm;
     const unsigned long long sim_seed = simulate_seed ? strtoull(simulate_seed, NULL, 0) : 0xFD821A6ull;
     fscl_amd_sweep_t *sim_sw = parse_sweeps(s, &simulate_sweep, "simulate-sweep");
     fscl_amd_sweep_t *boot_sw = parse_sweeps(s, &bootstrap_sweep, "bootstrap-sweep");
+    /* the given sweeps and every host-only refusal of the conditional scan, on every rank, before any device work */
+    fscl_amd_sweep_t *given_sw = parse_sweeps(s, &given_sweep, "given-sweep");
+    double cond_la[FSCL_AMD_SURFACE_MAX_LA];
+    const int cond_n_la = cond_fname ? fscl_amd_surface_alphas(cond_lo, cond_hi, cond_n, NAN, cond_la) : 0;
+    if (cond_fname && fscl_amd_conditional_check(s, given_sw, given_sweep.n, cond_halfwidth, cond_step, cond_la, cond_n_la, cond_rounds,
+                                                 cond_min_clr) != 0)
+      logmsg(MSG_FATAL, "fscl: %s", fscl_amd_conditional_error());
     int n_boot = bootstrap_sweep.n;
     const char *ws = getenv("WORLD_SIZE"), *rk = getenv("RANK");
     if (ws && rk && atoi(ws) > 1) {
@@ -505,6 +579,26 @@ int main(int argc, char **argv) {
              bk.n_terms, fscl_amd_blocks_last_ms());
       fscl_amd_blocks_free(&bk);
     }
+    if (cond_fname && !(ws && rk && atoi(ws) > 1 && atoi(rk) != 0)) {
+      /* the conditional sweep scan given fixed sweeps, of the data as loaded (rank 0 alone); no rand() draw */
+      fscl_amd_sweep_t *gsw = given_sw, top1;
+      fscl_amd_conditional_t cd;
+      int ng = given_sweep.n, r, bi = -1;
+      if (ng == 0) { /* the scan point of greatest CLR (the first on a tie, never a NaN), at its fitted alpha */
+        for (i = 0; i < s->n_scan_pts; i++)
+          if (s->scan_pts[i].clr == s->scan_pts[i].clr && (bi < 0 || s->scan_pts[i].clr > s->scan_pts[bi].clr)) bi = i;
+        if (bi >= 0) {
+          top1.chr = s->scan_pts[bi].chr; top1.pos = s->scan_pts[bi].sweep_pos; top1.alpha = exp(s->scan_pts[bi].lalpha);
+          gsw = &top1; ng = 1;
+        }
+      }
+      r = fscl_amd_scan_conditional(s, sm, eval_range, gsw, ng, cond_halfwidth, cond_step, cond_la, cond_n_la, cond_rounds, cond_min_clr, &cd);
+      if (r != 0) logmsg(MSG_FATAL, "fscl: conditional scan failed (code %d): %s", r, fscl_amd_conditional_error());
+      if (fscl_amd_conditional_output(cond_fname, s, &cd, prepend_label) != 0) logmsg(MSG_FATAL, "fscl: cannot write %s", cond_fname);
+      logmsg(MSG_STATUS, "Conditional scan: %llu positions, %llu terms, kernel %.3f ms, base folds %.3f s\n",
+             (unsigned long long)cd.n_rows, cd.n_terms, fscl_amd_conditional_last_ms(), cd.fold_s);
+      fscl_amd_conditional_free(&cd);
+    }
     if (dont_scan) {
       /* nothing to test or to write */
     } else if (n_permute > 0 && grid_mode)
@@ -543,7 +637,7 @@ int main(int argc, char **argv) {
                          "scan %.3f s)\n", n_boot, bootstrap_reps, tm[0], tm[1], tm[2], tm[3], tm[4]);
       free(bt);
     }
-    free(sim_sw); free(boot_sw);
+    free(sim_sw); free(boot_sw); free(given_sw);
     if (verbosity >= MSG_DEBUG1) {
       fscl_amd_stats_t st;
       fscl_amd_get_stats(&st);

@@ -2906,6 +2906,237 @@ int fscl_amd_surface_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, i
   return r;
 }
 
+/* ------------------------------------------------------ conditional sweep scan
+   The likelihood ratio of one more sweep given fixed sweeps (fsclg_cond_submit), on the data as
+   loaded.  Every refusal comes first, on the host.  Per round: the given sweeps' walks by
+   fscl_amd_scan_sites and their terms per site; per chromosome with a given sweep the grid's
+   positions in pieces of COND_PIECE, each position's clip from fscl_amd_cond_clip; the local
+   devices take contiguous shares of the pieces balanced by window size x cells, all are
+   submitted to before the first wait; then the base folds and the ratio on the host
+   (conditional.c), one position after another. */
+#define COND_PIECE 4096
+static double g_cond_ms;
+double fscl_amd_conditional_last_ms(void) { return g_cond_ms; }
+static int cond_iv_cmp(const void *a, const void *b) {
+  const long long *x = a, *y = b;
+  return x[0] < y[0] ? -1 : (x[0] > y[0] ? 1 : 0);
+}
+
+/* the grid indices k of a chromosome's positions start_pos + k * step to evaluate, as merged ascending
+   intervals iv[2 * i], iv[2 * i + 1] (at most n_given of them, or 1): the whole span [start_pos, bp_length]
+   (halfwidth 0), or its part within halfwidth of a given sweep of the chromosome; returns their number */
+static int cond_intervals(const scan_t *s, int chr, const fscl_amd_sweep_t *gv, int ng, int halfwidth, int step,
+                          long long *iv) {
+  const long long a = s->chr_limits[chr].start_pos, K = ((long long)s->chr_limits[chr].bp_length - a) / step;
+  int i, n = 0, m = 0;
+  if (s->chr_limits[chr].bp_length < a) return 0;
+  if (halfwidth <= 0) { iv[0] = 0; iv[1] = K; return 1; }
+  for (i = 0; i < ng; i++) {
+    long long lo, hi;
+    if (gv[i].chr != chr) continue;
+    lo = (long long)gv[i].pos - halfwidth - a; hi = (long long)gv[i].pos + halfwidth - a;
+    lo = lo <= 0 ? 0 : (lo + step - 1) / step;
+    hi = hi < 0 ? -1 : hi / step;
+    if (hi > K) hi = K;
+    if (lo > hi) continue;
+    iv[2 * n] = lo; iv[2 * n + 1] = hi; n++;
+  }
+  qsort(iv, (size_t)n, 2 * sizeof *iv, cond_iv_cmp);
+  for (i = 0; i < n; i++) {
+    if (m && iv[2 * i] <= iv[2 * m - 1] + 1) { if (iv[2 * i + 1] > iv[2 * m - 1]) iv[2 * m - 1] = iv[2 * i + 1]; }
+    else { iv[2 * m] = iv[2 * i]; iv[2 * m + 1] = iv[2 * i + 1]; m++; }
+  }
+  return m;
+}
+
+int fscl_amd_scan_conditional(scan_t *s, sm_ptable_t *sm, int eval_range, const fscl_amd_sweep_t *given, int n_given,
+                              int halfwidth, int step, const double *alphas, int n_la, int rounds, double min_clr,
+                              fscl_amd_conditional_t *out) {
+  fscl_amd_sweep_t *gv;
+  long long iv[2 * (FSCL_AMD_COND_MAX_GIVEN + FSCL_AMD_COND_MAX_ROUNDS)];
+  double dev_ms[FH_MAX_DEV], t0;
+  size_t rows_cap = 0, given_cap = 0;
+  int ng, i, j, l, k, c, round, r = FSCLG_OK, blk_cap = 0;
+  if (!sm || !out) return FSCLG_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (fscl_amd_conditional_check(s, given, n_given, halfwidth, step, alphas, n_la, rounds, min_clr) != 0) return FSCLG_E_ARG;
+  if (D.world > 1 && D.rank != 0) return FSCLG_OK; /* rank 0 alone evaluates, as the surfaces */
+  ng = n_given;
+  gv = fh_malloc(sizeof *gv * (size_t)(n_given + FSCL_AMD_COND_MAX_ROUNDS * (s->n_chromosomes > 0 ? s->n_chromosomes : 1)), "given sweeps");
+  if (n_given) memcpy(gv, given, sizeof *gv * (size_t)n_given);
+  g_cond_ms = 0.;
+  for (l = 0; l < FH_MAX_DEV; l++) dev_ms[l] = 0.;
+  for (round = 1; round <= rounds && r == FSCLG_OK; round++) {
+    fscl_amd_sites_t st;
+    fsclg_site_req_t *req = fh_malloc(sizeof *req * (size_t)(ng ? ng : 1), "given walks");
+    fsclg_run_t *runs = NULL;
+    fsclg_point_t *pts;
+    int32_t *clip, *want;
+    int *run_chr_first; /* per chromosome: its first run, or -1 */
+    double *cost, *lav, *smv, **g;
+    size_t np = 0, off;
+    int n_runs = 0, run_cap = 0, lo[FH_MAX_DEV], hi[FH_MAX_DEV], added = 0, blk0 = out->n_blocks;
+    for (i = 0; i < ng; i++) { req[i].chr = gv[i].chr; req[i].pos = gv[i].pos; req[i].lalpha = log(gv[i].alpha); }
+    r = fscl_amd_scan_sites(s, sm, eval_range, req, ng, &st); /* (prepare, the original rows in slot 0) */
+    free(req);
+    if (r != FSCLG_OK) break;
+    g = fh_calloc(s->n_chromosomes > 0 ? s->n_chromosomes : 1, sizeof *g, "given terms");
+    run_chr_first = fh_malloc(sizeof(int) * (size_t)(s->n_chromosomes + 1), "runs");
+    for (c = 0; c < s->n_chromosomes; c++) {
+      int m, has = 0;
+      run_chr_first[c] = n_runs;
+      for (i = 0; i < ng; i++) has |= gv[i].chr == c;
+      if (!has) continue;
+      g[c] = fh_malloc(sizeof(double) * (size_t)(s->chr_limits[c].n_snps > 0 ? s->chr_limits[c].n_snps : 1), "given terms");
+      if (fscl_amd_cond_given_terms(s, gv, ng, c, st.hdr, st.terms, g[c]) != 0) logmsg(MSG_FATAL, "fscl_amd: conditional scan: given terms");
+      m = cond_intervals(s, c, gv, ng, halfwidth, step, iv);
+      for (i = 0; i < m; i++) {
+        long long k0;
+        for (k0 = iv[2 * i]; k0 <= iv[2 * i + 1]; k0 += COND_PIECE) {
+          const long long cnt = iv[2 * i + 1] - k0 + 1 < COND_PIECE ? iv[2 * i + 1] - k0 + 1 : COND_PIECE;
+          if (n_runs == run_cap) { run_cap = run_cap ? 2 * run_cap : 64; runs = fh_realloc(runs, sizeof *runs * (size_t)run_cap, "runs"); }
+          runs[n_runs].chr = c; runs[n_runs].start_pos = (int)(s->chr_limits[c].start_pos + k0 * step);
+          runs[n_runs].step = step; runs[n_runs].count = (int)cnt;
+          n_runs++; np += (size_t)cnt;
+        }
+      }
+    }
+    run_chr_first[s->n_chromosomes] = n_runs;
+    fscl_amd_sites_free(&st);
+    clip = fh_malloc(sizeof(int32_t) * 2 * (np ? np : 1), "clips");
+    want = fh_malloc(sizeof(int32_t) * (np ? np : 1), "positions");
+    pts = fh_malloc(sizeof *pts * (np ? np : 1), "conditional points");
+    smv = fh_malloc(sizeof(double) * (np ? np : 1) * (size_t)n_la, "conditional values");
+    cost = fh_malloc(sizeof(double) * (size_t)(n_runs ? n_runs : 1), "cost");
+    lav = fh_malloc(sizeof(double) * (size_t)(n_runs ? n_runs : 1) * (size_t)n_la, "alphas");
+    for (i = 0, off = 0; i < n_runs; i++) {
+      memcpy(lav + (size_t)i * n_la, alphas, sizeof(double) * (size_t)n_la);
+      cost[i] = window_cost(runs[i].chr, eval_range) * runs[i].count * n_la;
+      for (j = 0; j < runs[i].count; j++, off++) {
+        int sp, a, b;
+        fscl_amd_cond_clip(s, gv, ng, runs[i].chr, runs[i].start_pos + j * runs[i].step, &sp, &a, &b);
+        want[off] = sp; clip[2 * off] = a; clip[2 * off + 1] = b;
+      }
+    }
+    for (l = 0; l < D.n_dev; l++) {
+      if (D.n_dev <= 1) { lo[l] = 0; hi[l] = n_runs; }
+      else fscl_amd_partition(cost, n_runs, l, D.n_dev, &lo[l], &hi[l]);
+    }
+    for (l = 0; l < D.n_dev; l++) out->n_terms -= dev_terms(l);
+    for (l = 0; l < D.n_dev && r == FSCLG_OK; l++) {
+      for (j = 0, off = 0; j < lo[l]; j++) off += (size_t)runs[j].count;
+      DBG("conditional: round %d, device %d, runs [%d, %d)\n", round, D.dev[l], lo[l], hi[l]);
+      r = fsclg_cond_submit(D.ctx[l], 0, 0, runs + lo[l], hi[l] - lo[l], lav + (size_t)lo[l] * n_la, n_la, clip + 2 * off, eval_range);
+    }
+    for (k = 0; k < l; k++) {
+      int rw;
+      if (k == l - 1 && r != FSCLG_OK) break; /* the submit that failed left nothing to wait for */
+      for (j = 0, off = 0; j < lo[k]; j++) off += (size_t)runs[j].count;
+      rw = fsclg_cond_wait(D.ctx[k], 0, pts + off, smv + off * n_la);
+      dev_ms[k] += fsclg_cond_last_ms(D.ctx[k], 0);
+      if (r == FSCLG_OK) r = rw;
+    }
+    for (l = 0; l < D.n_dev; l++) out->n_terms += dev_terms(l);
+    if (r == FSCLG_OK) {
+      for (off = 0; off < np; off++)
+        if (pts[off].sweep_pos != want[off])
+          logmsg(MSG_FATAL, "fscl_amd: conditional scan: the device evaluated position %d where the clip was computed for %d",
+                 pts[off].sweep_pos, want[off]);
+      if (out->n_rows + np > rows_cap) {
+        rows_cap = out->n_rows + np;
+        out->rows = fh_realloc(out->rows, sizeof *out->rows * (rows_cap ? rows_cap : 1), "conditional rows");
+      }
+      t0 = fh_now();
+      {
+        fscl_amd_cond_row_t *rows = out->rows + out->n_rows;
+        long long q, nq = (long long)np;
+        for (q = 0; q < nq; q++) {
+          const fsclg_point_t *p = pts + q;
+          fscl_amd_cond_row_t *w = rows + q;
+          int nt = 0;
+          memset(w, 0, sizeof *w);
+          w->pos = p->sweep_pos; w->lo = clip[2 * q]; w->hi = clip[2 * q + 1];
+          w->lalpha = p->lalpha; w->v = p->sm_logl; w->null_logl = p->null_logl;
+          w->base = fscl_amd_cond_base(g[p->chr], s->chr_limits[p->chr].start_index, w->lo, w->hi, p->window_start, p->window_end, &nt);
+          w->n_terms = nt;
+          w->cond_clr = 2.0 * ((w->v - w->null_logl) - w->base);
+        }
+      }
+      out->fold_s += fh_now() - t0;
+      for (c = 0; c < s->n_chromosomes; c++) { /* one block per chromosome with a given sweep */
+        fscl_amd_cond_block_t *h;
+        size_t row0 = out->n_rows, nrow = 0;
+        int best = -1, m = 0;
+        if (!g[c]) continue;
+        for (i = 0; i < run_chr_first[c]; i++) row0 += (size_t)runs[i].count;
+        for (i = run_chr_first[c]; i < run_chr_first[c + 1]; i++) nrow += (size_t)runs[i].count;
+        if (out->n_blocks == blk_cap) { blk_cap = blk_cap ? 2 * blk_cap : 16; out->blk = fh_realloc(out->blk, sizeof *out->blk * (size_t)blk_cap, "conditional blocks"); }
+        h = out->blk + out->n_blocks++;
+        memset(h, 0, sizeof *h);
+        for (i = 0; i < ng; i++) m += gv[i].chr == c;
+        if (out->n_given + (size_t)m > given_cap) {
+          given_cap = 2 * (out->n_given + (size_t)m);
+          out->given = fh_realloc(out->given, sizeof *out->given * given_cap, "given sweeps");
+        }
+        h->chr = c; h->round = round; h->n_pos = (int)nrow; h->n_given = m; h->row_off = row0; h->given_off = out->n_given;
+        for (i = 0; i < ng; i++)
+          if (gv[i].chr == c) out->given[out->n_given++] = gv[i];
+        for (i = 0; i < (int)nrow; i++) { /* the first position of greatest cond_clr, never a NaN */
+          const double v = out->rows[row0 + i].cond_clr;
+          if (v == v && (best < 0 || v > out->rows[row0 + best].cond_clr)) best = i;
+        }
+        h->max_row = best;
+        h->added = best >= 0 && out->rows[row0 + best].cond_clr > min_clr;
+      }
+      out->n_rows += np;
+      for (i = blk0; i < out->n_blocks; i++) { /* the rounds' maxima join the given sweeps */
+        const fscl_amd_cond_block_t *h = out->blk + i;
+        if (!h->added) continue;
+        gv[ng].chr = h->chr; gv[ng].pos = out->rows[h->row_off + h->max_row].pos;
+        gv[ng].alpha = exp(out->rows[h->row_off + h->max_row].lalpha);
+        ng++; added++;
+      }
+    }
+    for (c = 0; c < s->n_chromosomes; c++) free(g[c]);
+    free(g); free(run_chr_first); free(runs); free(clip); free(want); free(pts); free(smv); free(cost); free(lav);
+    if (!added) break;
+  }
+  for (l = 0; l < D.n_dev; l++)
+    if (dev_ms[l] > g_cond_ms) g_cond_ms = dev_ms[l]; /* the devices run side by side */
+  free(gv);
+  if (r != FSCLG_OK) fscl_amd_conditional_free(out);
+  return r;
+}
+
+/* the test handle of fsclg_cond_submit / fsclg_cond_wait on the first device: fscl_amd_surface_runs with
+   the positions' clips */
+int fscl_amd_cond_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int n_runs, const double *la, int n_la,
+                       const int32_t *clip, int eval_range, const uint32_t *rows, int batch, fsclg_point_t *pts,
+                       double *smv) {
+  int r, slot = 0;
+  if (!s || !sm || (!runs && n_runs) || n_runs < 0) return FSCLG_E_ARG;
+  prepare(s, sm);
+  g_cond_ms = 0.;
+  if (rows) {
+    double *nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
+    int i;
+    for (i = 0; i < s->n_snps; i++)
+      if (rows[i] >= (uint32_t)D.rm.n_dev_rows) { free(nul); return FSCLG_E_ARG; }
+    chr_null_sums_32(rows, nul);
+    slot = 1;
+    r = fsclg_slot_set_rows(D.ctx[0], slot, rows, nul);
+    free(nul);
+    if (r != FSCLG_OK) return r;
+  } else {
+    set_original_rows();
+  }
+  r = fsclg_cond_submit(D.ctx[0], batch, slot, runs, n_runs, la, n_la, clip, eval_range);
+  if (r != FSCLG_OK) return r;
+  r = fsclg_cond_wait(D.ctx[0], batch, pts, smv);
+  g_cond_ms = fsclg_cond_last_ms(D.ctx[0], batch);
+  return r;
+}
+
 /* ------------------------------------------------------ block sums (delete-one-block jackknife)
    The surface's terms summed per genomic block (fsclg_blocks_submit) for surface requests, on the
    data as loaded.  The size checks come first, on the host; then a surface evaluation of the same

@@ -709,6 +709,107 @@ void fscl_amd_bootstrap_output(const char *fname, const scan_t *scan_obj, const 
 void fscl_amd_sample_tables_build(const sm_ptable_t *sm_p, int n_depths, double **coef_t, double **neutral,
                                   int32_t *depth_n, int *n_iv);
 
+/* ---- conditional sweep scan given fixed sweeps (--conditional-file) ------------------
+   The composite likelihood of one more sweep at a candidate position, given sweeps held fixed, as
+   a likelihood ratio against the model with the given sweeps alone -- the fit of what
+   fscl_amd_simulate draws with several sweeps: every site belongs to its nearest sweep.
+
+   Ownership.  The candidate's position s is the position's sweep_pos after init_scan_result's
+   de-collision (the reference's rule, its comparison of a global index with the chromosome's count
+   included).  A site at x belongs to the sweep of least |x - position|, a tie to the lower
+   position, then to the first listed, the given sweeps listed before the candidate
+   (fscl_amd_nearest_sweep's rule).  Against a given sweep q > s the candidate owns the sites with
+   2x <= s + q, against q < s those with 2x > s + q (64-bit sums), with q = s nothing: its sites
+   are one interval [lo, hi] of global site indices, cut by the nearest given sweep on either side
+   and by the chromosome's ends; lo > hi when it is empty.  fscl_amd_cond_clip (host only) gives
+   *sweep_pos, *lo and *hi from the chromosome's given sweeps (entries of another chromosome are
+   skipped); -1 for a NULL argument or a bad chromosome.
+
+   Values.  V(s, a): the position's window null sum N plus, in the reference's walk order, the terms
+   of the walk at log alpha a whose sites lie in [lo, hi] (fsclg_cond_submit).  G_i: the term of
+   site i in the walk of the given sweep that owns it among the given sweeps, at that sweep's
+   log alpha -- the term fscl_amd_scan_sites returns for (chr, q, log alpha_q) -- and +0.0 where i is
+   not in that walk (fscl_amd_cond_given_terms, host only, from the sites result of the chromosome's
+   given sweeps in their order, into g[the chromosome's n_snps]).  A(s): the strictly sequential sum
+   of G_i over [lo, hi] cut to [window_start, window_end], ascending from +0.0
+   (fscl_amd_cond_base, host only; *n_terms: the sites of that interval).  The position's point is
+   the first strict maximum of V in list order, and cond_clr = 2.0 * ((V - N) - A) at it.
+   The given sweeps' positions and alphas are held fixed, ownership goes by distance alone, and the
+   likelihood is composite: the ratio describes, it is not a calibrated test.
+
+   fscl_amd_scan_conditional: per round (1 .. 8) and per chromosome that holds a given sweep, the
+   positions chr start_pos + k * step over [start_pos, bp_length]; with halfwidth > 0 only those
+   within halfwidth of a given sweep of the chromosome.  After a round each chromosome's position of
+   greatest cond_clr (the first in position order on a tie; NaN never) joins the given sweeps with
+   its alpha if it is strictly above min_clr, and the next round runs against the enlarged set; the
+   rounds end early when no chromosome adds one.  alphas: an ascending list of n_la log alphas,
+   1 .. 64 values in [-20, 4].  Runs on slot 0 as fscl_amd_scan_surface does (contiguous shares of
+   the local devices, all submitted to before the first wait; rank 0 alone evaluates with several
+   ranks).  Refused with FSCLG_E_ARG before any device work, fscl_amd_conditional_error() naming the
+   option: an unknown chromosome, alpha not positive or log alpha outside [-20, 4], more than 64
+   given sweeps on a chromosome (FSCL_AMD_COND_MAX_GIVEN), step < 1, rounds outside [1, 8], a bad
+   alpha list, or a result above fscl_amd_conditional_cap() bytes ($FSCL_AMD_COND_CAP, default 2^30).
+   A returned point whose sweep_pos is not the one its clip was computed from is fatal.
+
+   fscl_amd_conditional_output (fname NULL: stdout; host only): per block one row per position
+     [label TAB] chromosome TAB round TAB pos TAB alpha (%1.3e) TAB cond_CLR (%1.2f) TAB own_first_pos
+       TAB own_last_pos TAB n_terms TAB base (%1.4f)
+   then one summary row
+     [label TAB] chromosome TAB round TAB summary TAB n_pos TAB n_given TAB given (pos:alpha,...) TAB
+       max_pos TAB max_alpha TAB max_cond_clr TAB added
+   own_*: the positions of the first and last owned site, NA for an empty interval; max_*: NA when
+   no position has a cond_clr that is not NaN.  0, or -1 (a NULL argument, a block outside the
+   arrays, a file that cannot be written). */
+#define FSCL_AMD_COND_MAX_GIVEN 64
+#define FSCL_AMD_COND_MAX_ROUNDS 8
+typedef struct {
+  int32_t pos;              /* the candidate's sweep_pos */
+  int32_t lo, hi;           /* its sites, global indices; lo > hi: none */
+  int32_t n_terms;          /* sites of [lo, hi] inside the position's window */
+  double lalpha, cond_clr, base;
+  double v, null_logl;      /* V at lalpha and N */
+} fscl_amd_cond_row_t;
+typedef struct {
+  int32_t chr, round;       /* round 1 .. */
+  int32_t n_pos, n_given;
+  uint64_t row_off, given_off; /* the block's rows in rows[], its given sweeps in given[] */
+  int32_t max_row, added;   /* the row of greatest cond_clr within the block (-1: none); whether it joined */
+} fscl_amd_cond_block_t;
+typedef struct {
+  int n_blocks;
+  fscl_amd_cond_block_t *blk;
+  fscl_amd_cond_row_t *rows;
+  fscl_amd_sweep_t *given;     /* every block's given sweeps, alpha > 0 */
+  size_t n_rows, n_given;
+  unsigned long long n_terms; /* the device's walk terms */
+  double fold_s;              /* host seconds of the base folds */
+} fscl_amd_conditional_t;
+int fscl_amd_cond_clip(const scan_t *scan_obj, const fscl_amd_sweep_t *given, int n_given, int chr, int pos,
+                       int *sweep_pos, int *lo, int *hi);
+int fscl_amd_cond_given_terms(const scan_t *scan_obj, const fscl_amd_sweep_t *given, int n_given, int chr,
+                              const fscl_amd_site_hdr_t *hdr, const double *terms, double *g);
+double fscl_amd_cond_base(const double *g, int chr_start_index, int lo, int hi, int window_start, int window_end,
+                          int *n_terms);
+size_t fscl_amd_conditional_cap(void);
+const char *fscl_amd_conditional_error(void);
+/* every refusal of fscl_amd_scan_conditional, host only: 0, or -1 with fscl_amd_conditional_error() set */
+int fscl_amd_conditional_check(const scan_t *scan_obj, const fscl_amd_sweep_t *given, int n_given, int halfwidth, int step,
+                               const double *alphas, int n_la, int rounds, double min_clr);
+int fscl_amd_scan_conditional(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, const fscl_amd_sweep_t *given,
+                              int n_given, int halfwidth, int step, const double *alphas, int n_la, int rounds,
+                              double min_clr, fscl_amd_conditional_t *out);
+int fscl_amd_conditional_output(const char *fname, const scan_t *scan_obj, const fscl_amd_conditional_t *r,
+                                const char *prepend_label);
+void fscl_amd_conditional_free(fscl_amd_conditional_t *r);
+/* the kernel milliseconds of the last fscl_amd_scan_conditional / fscl_amd_cond_runs (the slowest device's, summed
+   over the rounds) */
+double fscl_amd_conditional_last_ms(void);
+/* the test handle of fsclg_cond_submit / fsclg_cond_wait on the first device: fscl_amd_surface_runs with the
+   positions' clips */
+int fscl_amd_cond_runs(scan_t *scan_obj, sm_ptable_t *sm_p, const fsclg_run_t *runs, int n_runs, const double *la,
+                       int n_la, const int32_t *clip, int eval_range, const uint32_t *rows, int batch,
+                       fsclg_point_t *pts, double *sm);
+
 /* ---- projected p-values from a noncentral chi-square fit (--tail-file) ----
    The permutation test's empirical p-value cannot go below 1 / permute_n.  Per scan point, the
    saved null CLRs x_1 .. x_m (m = min(permute_n, FSCL_AMD_TAIL_SAVE), the used prefix of

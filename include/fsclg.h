@@ -339,6 +339,26 @@ int fsclg_blocks_wait(fsclg_ctx *c, int batch, fsclg_point_t *pts /* sum(count) 
                       double *bs /* sum(count * nb) * n_la */, uint32_t *cnt /* as bs */);
 double fsclg_blocks_last_ms(fsclg_ctx *c, int batch);
 
+/* The conditional sweep scan: the surface with every walk cut to the sites a candidate sweep owns.
+   Runs, alpha lists, batch, slot, eval_range and window null sums are fsclg_surface_submit's; there is
+   one more argument, clip[2 * sum(count)]: per position, runs in order, a pair (lo, hi) of global site
+   indices (copied, like the runs; any int32, lo > hi: empty).  sm[p * n_la + k] is the position's
+   null_logl plus the terms of the walk of la[k] whose site index lies in [lo, hi], in the reference's
+   walk order (the nearest SNP if inside, then leftwards, then rightwards: sm-search.c:105-150), added
+   strictly in that order; an alpha whose nearest SNP is past its own cut has an empty walk whatever the
+   clip holds.  With [lo, hi] covering the window, points and values are fsclg_surface_wait's byte for
+   byte; with an empty interval every value is null_logl.  The point is the row's first strict maximum
+   as there; the device counters count the clipped walks' terms.  The same input gives the same bytes
+   on every batch and slot and for every chunking.  FSCLG_E_ARG for a NULL clip with positions; the
+   other error codes are fsclg_surface_submit's (FSCLG_E_STATE from the wait when the batch holds no
+   conditional scan).  fsclg_cond_last_ms: the kernel's own time of the batch's last launch. */
+int fsclg_cond_submit(fsclg_ctx *c, int batch, int slot, const fsclg_run_t *runs, int n_runs,
+                      const double *la /* [n_runs][n_la] */, int n_la, const int32_t *clip /* 2 * sum(count) */,
+                      int eval_range);
+int fsclg_cond_wait(fsclg_ctx *c, int batch, fsclg_point_t *pts /* sum(count) */,
+                    double *sm /* sum(count) * n_la, position-major */);
+double fsclg_cond_last_ms(fsclg_ctx *c, int batch);
+
 /* Per-site likelihood terms: the data axis of a sweep position.  A request is one walk of
    sm_likelihood (sm-search.c:105-150) -- a chromosome, a position and a log alpha, any double
    >= LOG_AD_MIN (-20), not only a value of the alpha grid -- on the rows a slot holds.  Its header's

@@ -581,19 +581,31 @@ def site_rows(scan, tables) -> np.ndarray:
     return out[:n]
 
 
+def _runs_rows(scan, runs, rows):
+    """What the *_runs handles share: the RunT array of ``runs`` (chr, start, step, count) and the pointer to
+    ``rows`` as uint32, one per site, or None (the pointer keeps its array alive)."""
+    arr = (RunT * max(len(runs), 1))(*[RunT(*[int(v) for v in r]) for r in runs])
+    if rows is None:
+        return arr, None
+    rows = np.ascontiguousarray(rows, dtype=np.uint32)
+    if len(rows) != scan.contents.n_snps:
+        raise ValueError("rows must hold one row per site")
+    return arr, rows.ctypes.data_as(C.c_void_p)
+
+
+def _run_alphas(runs, alphas):
+    """(la [len(runs)][n_la], sum(count), n_la) of one alpha list per run, all of one length."""
+    la = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(runs), -1) if len(runs) else np.zeros((0, 1))
+    return la, sum(max(int(r[3]), 0) for r in runs), la.shape[1]
+
+
 def cellmax_runs(scan, tables, runs, eval_range: int = 81920, rows=None) -> np.ndarray:
     """Per (chr, start, step, count) of ``runs`` the first position of strictly greatest CLR, through
     fsclg_cellmax_submit / fsclg_cellmax_wait on the scan's context: one POINT_DTYPE row per run (a
     zero-count run: a zeroed row).  ``rows``: a uint32 array of n_snps device rows (a rearrangement of
     site_rows) set into the slot first; None: the uploaded rows."""
-    arr = (RunT * max(len(runs), 1))(*[RunT(*[int(v) for v in r]) for r in runs])
     out = (PointT * max(len(runs), 1))()
-    rp = None
-    if rows is not None:
-        rows = np.ascontiguousarray(rows, dtype=np.uint32)
-        if len(rows) != scan.contents.n_snps:
-            raise ValueError("rows must hold one row per site")
-        rp = rows.ctypes.data
+    arr, rp = _runs_rows(scan, runs, rows)
     r = get_lib().fscl_amd_cellmax_runs(scan, tables, arr, len(runs), int(eval_range), rp, out)
     if r != 0:
         raise RuntimeError(f"fscl_amd_cellmax_runs: code {r}: {get_lib().fsclg_last_error().decode()}")
@@ -643,18 +655,12 @@ def curve_runs(scan, tables, runs, eval_range: int = 81920, rows=None, out=None)
     fsclg_curve_submit / fsclg_curve_wait on the scan's first device (the shim-level handle, next to
     cellmax_runs): a CURVE_DTYPE array in run order.  ``rows`` as for cellmax_runs; ``out``: a
     CURVE_DTYPE array to fill (tests pre-fill it)."""
-    arr = (RunT * max(len(runs), 1))(*[RunT(*[int(v) for v in r]) for r in runs])
     n = sum(max(int(r[3]), 0) for r in runs)
     if out is None:
         out = np.zeros(max(n, 1), dtype=CURVE_DTYPE)
     if out.dtype != CURVE_DTYPE or len(out) < n or not out.flags.c_contiguous:
         raise ValueError("out must be a contiguous CURVE_DTYPE array of sum(count) records")
-    rp = None
-    if rows is not None:
-        rows = np.ascontiguousarray(rows, dtype=np.uint32)
-        if len(rows) != scan.contents.n_snps:
-            raise ValueError("rows must hold one row per site")
-        rp = rows.ctypes.data
+    arr, rp = _runs_rows(scan, runs, rows)
     _curve_check(get_lib().fscl_amd_curve_runs(scan, tables, arr, len(runs), int(eval_range), rp, out.ctypes.data),
                  "fscl_amd_curve_runs")
     return out[:n]
@@ -896,9 +902,7 @@ def surface_runs(scan, tables, runs, alphas, eval_range: int = 81920, rows=None,
     """fsclg_surface_submit / fsclg_surface_wait on the scan's first device (the shim-level handle, next to
     curve_runs): ``alphas`` holds one ascending list per run, all of one length.  Returns (points
     [sum(count)], values [sum(count)][n_la]); ``pts`` / ``sm``: arrays to fill (tests pre-fill them)."""
-    arr = (RunT * max(len(runs), 1))(*[RunT(*[int(v) for v in r]) for r in runs])
-    la = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(runs), -1) if len(runs) else np.zeros((0, 1))
-    n, k = sum(max(int(r[3]), 0) for r in runs), la.shape[1]
+    la, n, k = _run_alphas(runs, alphas)
     if pts is None:
         pts = np.zeros(max(n, 1), dtype=_POINT_RAW)
     if sm is None:
@@ -906,12 +910,7 @@ def surface_runs(scan, tables, runs, alphas, eval_range: int = 81920, rows=None,
     if pts.dtype != _POINT_RAW or len(pts) < n or sm.dtype != np.float64 or sm.size < n * k or \
             not (pts.flags.c_contiguous and sm.flags.c_contiguous):
         raise ValueError("pts / sm must be contiguous arrays of sum(count) points and sum(count) * n_la values")
-    rp = None
-    if rows is not None:
-        rows = np.ascontiguousarray(rows, dtype=np.uint32)
-        if len(rows) != scan.contents.n_snps:
-            raise ValueError("rows must hold one row per site")
-        rp = rows.ctypes.data
+    arr, rp = _runs_rows(scan, runs, rows)
     _curve_check(get_lib().fscl_amd_surface_runs(scan, tables, arr, len(runs), la.ctypes.data, k, int(eval_range), rp,
                                                  int(batch), pts.ctypes.data, sm.ctypes.data), "fscl_amd_surface_runs")
     return pts[:n], sm.reshape(-1)[:n * k].reshape(n, k)
@@ -1062,12 +1061,10 @@ def blocks_runs(scan, tables, runs, alphas, blocks, eval_range: int = 81920, row
     surface_runs): ``alphas`` holds one ascending list per run, all of one length, ``blocks`` one
     (block_bp, b0, nb) per run.  Returns (points [sum(count)], sums, counts), the latter two flat,
     position-major, then block, then alpha; ``pts`` / ``bs`` / ``cnt``: arrays to fill (tests pre-fill them)."""
-    arr = (RunT * max(len(runs), 1))(*[RunT(*[int(v) for v in r]) for r in runs])
-    la = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(runs), -1) if len(runs) else np.zeros((0, 1))
+    la, n, k = _run_alphas(runs, alphas)
     blk = np.zeros(max(len(runs), 1), dtype=BLOCKSPEC_DTYPE)
     for q, b in zip(blk, blocks):
         q["block_bp"], q["b0"], q["nb"] = (int(v) for v in b)
-    n, k = sum(max(int(r[3]), 0) for r in runs), la.shape[1]
     nc = sum(max(int(r[3]), 0) * max(int(b[2]), 0) for r, b in zip(runs, blocks)) * k
     if pts is None:
         pts = np.zeros(max(n, 1), dtype=_POINT_RAW)
@@ -1078,12 +1075,7 @@ def blocks_runs(scan, tables, runs, alphas, blocks, eval_range: int = 81920, row
     if pts.dtype != _POINT_RAW or len(pts) < n or bs.dtype != np.float64 or bs.size < nc or cnt.dtype != np.uint32 or \
             cnt.size < nc or not (pts.flags.c_contiguous and bs.flags.c_contiguous and cnt.flags.c_contiguous):
         raise ValueError("pts / bs / cnt must be contiguous arrays of sum(count) points and sum(count * nb) * n_la cells")
-    rp = None
-    if rows is not None:
-        rows = np.ascontiguousarray(rows, dtype=np.uint32)
-        if len(rows) != scan.contents.n_snps:
-            raise ValueError("rows must hold one row per site")
-        rp = rows.ctypes.data
+    arr, rp = _runs_rows(scan, runs, rows)
     _curve_check(get_lib().fscl_amd_blocks_runs(scan, tables, arr, len(runs), la.ctypes.data, k, blk.ctypes.data, int(eval_range),
                                                 rp, int(batch), pts.ctypes.data, bs.ctypes.data, cnt.ctypes.data),
                  "fscl_amd_blocks_runs")
@@ -1279,9 +1271,7 @@ def cond_runs(scan, tables, runs, alphas, clip, eval_range: int = 81920, rows=No
     """fsclg_cond_submit / fsclg_cond_wait on the scan's first device (the shim-level handle, as surface_runs):
     ``clip`` holds one global site-index pair (lo, hi) per position.  Returns (points [sum(count)], values
     [sum(count)][n_la])."""
-    arr = (RunT * max(len(runs), 1))(*[RunT(*[int(v) for v in r]) for r in runs])
-    la = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(runs), -1) if len(runs) else np.zeros((0, 1))
-    n, k = sum(max(int(r[3]), 0) for r in runs), la.shape[1]
+    la, n, k = _run_alphas(runs, alphas)
     cl = np.ascontiguousarray(clip, dtype=np.int32).reshape(-1)
     if cl.size != 2 * n:
         raise ValueError("clip must hold one (lo, hi) pair per position")
@@ -1292,12 +1282,7 @@ def cond_runs(scan, tables, runs, alphas, clip, eval_range: int = 81920, rows=No
     if pts.dtype != _POINT_RAW or len(pts) < n or sm.dtype != np.float64 or sm.size < n * k or \
             not (pts.flags.c_contiguous and sm.flags.c_contiguous):
         raise ValueError("pts / sm must be contiguous arrays of sum(count) points and sum(count) * n_la values")
-    rp = None
-    if rows is not None:
-        rows = np.ascontiguousarray(rows, dtype=np.uint32)
-        if len(rows) != scan.contents.n_snps:
-            raise ValueError("rows must hold one row per site")
-        rp = rows.ctypes.data
+    arr, rp = _runs_rows(scan, runs, rows)
     _curve_check(get_lib().fscl_amd_cond_runs(scan, tables, arr, len(runs), la.ctypes.data, k, cl.ctypes.data if n else None,
                                               int(eval_range), rp, int(batch), pts.ctypes.data, sm.ctypes.data), "fscl_amd_cond_runs")
     return pts[:n], sm.reshape(-1)[:n * k].reshape(n, k)

@@ -609,6 +609,76 @@ static void dev_shares(const double *cost, int n, int *lo, int *hi) {
   }
 }
 
+/* the same among the local devices alone: the analysis scans, which rank 0 evaluates by itself */
+static void local_shares(const double *cost, int n, int *lo, int *hi) {
+  int l;
+  for (l = 0; l < D.n_dev; l++) fscl_amd_partition(cost, n, l, D.n_dev, &lo[l], &hi[l]);
+}
+
+static unsigned long long dev_terms(int l) {
+  fsclg_stats_t st;
+  return fsclg_get_stats(D.ctx[l], &st) == FSCLG_OK ? st.n_terms : 0ull;
+}
+
+/* One batch of an analysis scan (curves, surfaces, conditional scan, block sums) on the local
+   devices' shares lo[], hi[] of its runs.  A scan fills a dev_job_t with its arrays and gives its
+   submit (runs [lo, hi) to device l) and wait (device k's results to where run lo's belong); the
+   protocol is here alone: every device is submitted to before the first is waited for; the first
+   error ends the submits and is the one returned; every device submitted to is waited for, the one
+   whose submit failed never.  dev_ms[k] gains device k's kernel time (a scan of several batches
+   adds them up; the devices run side by side, so its time is dev_ms_max); *n_terms, if given,
+   gains the terms the devices counted meanwhile. */
+typedef struct {
+  const fsclg_run_t *runs;
+  const double *la;            /* [run][n_la] */
+  int n_la, eval_range;
+  const size_t *poff, *coff;   /* the positions / cells of the runs before run i (blocks alone have coff) */
+  const int32_t *clip;         /* conditional: 2 per position */
+  const fsclg_blocks_t *blk;   /* blocks: per run */
+  fscl_amd_curve_t *curves;    /* the results: per position; val and cnt per cell */
+  fsclg_point_t *pts;
+  double *val;
+  uint32_t *cnt;
+} dev_job_t;
+typedef int (*dev_submit_fn)(int l, int lo, int hi, const dev_job_t *j);
+typedef int (*dev_wait_fn)(int k, int lo, const dev_job_t *j);
+
+static int run_on_devices(const char *what, const int *lo, const int *hi, dev_submit_fn submit, dev_wait_fn wait,
+                          double (*last_ms)(fsclg_ctx *, int), const dev_job_t *j, double *dev_ms,
+                          unsigned long long *n_terms) {
+  int l, k, n_sub, r = FSCLG_OK;
+  for (l = 0; n_terms && l < D.n_dev; l++) *n_terms -= dev_terms(l);
+  for (l = 0; l < D.n_dev && r == FSCLG_OK; l++) {
+    DBG("%s: device %d, runs [%d, %d)\n", what, D.dev[l], lo[l], hi[l]);
+    r = submit(l, lo[l], hi[l], j);
+  }
+  n_sub = r == FSCLG_OK ? l : l - 1; /* the submit that failed left nothing to wait for */
+  for (k = 0; k < n_sub; k++) {
+    const int rw = wait(k, lo[k], j);
+    dev_ms[k] += last_ms(D.ctx[k], 0);
+    if (r == FSCLG_OK) r = rw;
+  }
+  for (l = 0; n_terms && l < D.n_dev; l++) *n_terms += dev_terms(l);
+  return r;
+}
+
+static double dev_ms_max(const double *dev_ms) {
+  double ms = 0.;
+  int l;
+  for (l = 0; l < D.n_dev; l++)
+    if (dev_ms[l] > ms) ms = dev_ms[l];
+  return ms;
+}
+
+/* off[i]: the positions of the runs before run i, i <= n (malloc'd) */
+static size_t *run_offsets(const fsclg_run_t *runs, int n) {
+  size_t *off = fh_malloc(sizeof(size_t) * ((size_t)n + 1), "run offsets");
+  int i;
+  off[0] = 0;
+  for (i = 0; i < n; i++) off[i + 1] = off[i] + (size_t)runs[i].count;
+  return off;
+}
+
 /* complete a batch's results on every rank: this process holds [lo, hi) of out[n].  With
    `flags` (this rank's flag word on entry, the OR over the ranks on return) the exchange is
    made even for an empty batch, and out[] must have room for n + 1 items (the torch
@@ -702,6 +772,27 @@ static void set_original_rows(void) {
     dev_check(fsclg_set_chr_null(D.ctx[l], nul), "set null sums");
   }
   free(nul);
+}
+
+/* what the fscl_amd_*_runs test handles begin with: the arguments, the scan on the devices, and the
+   rows the runs are evaluated on -- the uploaded ones (rows NULL: *slot 0) or `rows` (n_snps device
+   rows, set into slot 1 of the first device with their whole-chromosome null sums: *slot 1) */
+static int runs_handle_begin(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int n_runs, const uint32_t *rows,
+                             int *slot) {
+  double *nul;
+  int i, r;
+  if (!s || !sm || (!runs && n_runs) || n_runs < 0) return FSCLG_E_ARG;
+  prepare(s, sm);
+  *slot = 0;
+  if (!rows) { set_original_rows(); return FSCLG_OK; }
+  for (i = 0; i < s->n_snps; i++)
+    if (rows[i] >= (uint32_t)D.rm.n_dev_rows) return FSCLG_E_ARG;
+  nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
+  chr_null_sums_32(rows, nul);
+  *slot = 1;
+  r = fsclg_slot_set_rows(D.ctx[0], *slot, rows, nul);
+  free(nul);
+  return r;
 }
 
 /* the cell sequence one scan_thread walks (scan-chromosome.c:176-212) */
@@ -2540,23 +2631,9 @@ static void eval_cell_maxima(int slot, const fsclg_cell_t *cells, int n, int g, 
    into slot 1 with their whole-chromosome null sums; batch 1) */
 int fscl_amd_cellmax_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int n_runs, int eval_range,
                           const uint32_t *rows, fsclg_point_t *out) {
-  int r, slot = 0;
-  if (!s || !sm || (!runs && n_runs) || n_runs < 0) return FSCLG_E_ARG;
-  prepare(s, sm);
+  int slot, r = runs_handle_begin(s, sm, runs, n_runs, rows, &slot);
+  if (r != FSCLG_OK) return r;
   g_cellmax_ms = 0.;
-  if (rows) {
-    double *nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
-    int i;
-    for (i = 0; i < s->n_snps; i++)
-      if (rows[i] >= (uint32_t)D.rm.n_dev_rows) { free(nul); return FSCLG_E_ARG; }
-    chr_null_sums_32(rows, nul);
-    slot = 1;
-    r = fsclg_slot_set_rows(D.ctx[0], slot, rows, nul);
-    free(nul);
-    if (r != FSCLG_OK) return r;
-  } else {
-    set_original_rows();
-  }
   r = fsclg_cellmax_submit(D.ctx[0], slot, slot, runs, n_runs, eval_range);
   if (r != FSCLG_OK) return r;
   r = fsclg_cellmax_wait(D.ctx[0], slot, out);
@@ -2588,41 +2665,33 @@ unsigned long long fscl_amd_curve_forced(void) {
   return n;
 }
 
+static int curve_submit(int l, int lo, int hi, const dev_job_t *j) {
+  return fsclg_curve_submit(D.ctx[l], 0, 0, j->runs + lo, hi - lo, j->eval_range); /* (the runs are copied) */
+}
+static int curve_wait(int k, int lo, const dev_job_t *j) { return fsclg_curve_wait(D.ctx[k], 0, j->curves + lo); }
+
 int fscl_amd_scan_curves(scan_t *s, sm_ptable_t *sm, int eval_range, const int *chr, const int *pos, int n,
                          fscl_amd_curve_t *out) {
+  dev_job_t job = {0};
   fsclg_run_t *runs;
-  double *cost;
-  int lo[FH_MAX_DEV], hi[FH_MAX_DEV], i, l, k, r = FSCLG_OK;
+  double *cost, dev_ms[FH_MAX_DEV] = {0.};
+  int lo[FH_MAX_DEV], hi[FH_MAX_DEV], i, r;
   if (!s || !sm || n < 0 || (n && (!chr || !pos || !out))) return FSCLG_E_ARG;
   if (D.world > 1 && D.rank != 0) return FSCLG_OK; /* rank 0 alone evaluates, as the profile */
   prepare(s, sm);
   for (i = 0; i < n; i++)
     if (chr[i] < 0 || chr[i] >= D.n_chr) return FSCLG_E_ARG;
   set_original_rows();
-  g_curve_ms = 0.;
   runs = fh_malloc(sizeof(fsclg_run_t) * (n ? n : 1), "curve runs");
   cost = fh_malloc(sizeof(double) * (n ? n : 1), "cost");
   for (i = 0; i < n; i++) {
     runs[i].chr = chr[i]; runs[i].start_pos = pos[i]; runs[i].step = 1; runs[i].count = 1;
     cost[i] = window_cost(chr[i], eval_range);
   }
-  for (l = 0; l < D.n_dev; l++) {
-    if (D.n_dev <= 1) { lo[l] = 0; hi[l] = n; }
-    else fscl_amd_partition(cost, n, l, D.n_dev, &lo[l], &hi[l]);
-  }
-  for (l = 0; l < D.n_dev && r == FSCLG_OK; l++) {
-    DBG("curves: device %d, positions [%d, %d)\n", D.dev[l], lo[l], hi[l]);
-    r = fsclg_curve_submit(D.ctx[l], 0, 0, runs + lo[l], hi[l] - lo[l], eval_range); /* (the runs are copied) */
-  }
-  for (k = 0; k < l; k++) {
-    int rw;
-    double ms;
-    if (k == l - 1 && r != FSCLG_OK) break; /* the submit that failed left nothing to wait for */
-    rw = fsclg_curve_wait(D.ctx[k], 0, out + lo[k]);
-    ms = fsclg_curve_last_ms(D.ctx[k], 0);
-    if (r == FSCLG_OK) r = rw;
-    if (ms > g_curve_ms) g_curve_ms = ms; /* the devices run side by side */
-  }
+  local_shares(cost, n, lo, hi);
+  job.runs = runs; job.eval_range = eval_range; job.curves = out;
+  r = run_on_devices("curves", lo, hi, curve_submit, curve_wait, fsclg_curve_last_ms, &job, dev_ms, NULL);
+  g_curve_ms = dev_ms_max(dev_ms);
   free(runs); free(cost);
   return r;
 }
@@ -2643,23 +2712,9 @@ int fscl_amd_scan_point_curves(scan_t *s, sm_ptable_t *sm, int eval_range, fscl_
    fscl_amd_cellmax_runs */
 int fscl_amd_curve_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int n_runs, int eval_range,
                         const uint32_t *rows, fscl_amd_curve_t *out) {
-  int r, slot = 0;
-  if (!s || !sm || (!runs && n_runs) || n_runs < 0) return FSCLG_E_ARG;
-  prepare(s, sm);
+  int slot, r = runs_handle_begin(s, sm, runs, n_runs, rows, &slot);
+  if (r != FSCLG_OK) return r;
   g_curve_ms = 0.;
-  if (rows) {
-    double *nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
-    int i;
-    for (i = 0; i < s->n_snps; i++)
-      if (rows[i] >= (uint32_t)D.rm.n_dev_rows) { free(nul); return FSCLG_E_ARG; }
-    chr_null_sums_32(rows, nul);
-    slot = 1;
-    r = fsclg_slot_set_rows(D.ctx[0], slot, rows, nul);
-    free(nul);
-    if (r != FSCLG_OK) return r;
-  } else {
-    set_original_rows();
-  }
   r = fsclg_curve_submit(D.ctx[0], slot, slot, runs, n_runs, eval_range);
   if (r != FSCLG_OK) return r;
   r = fsclg_curve_wait(D.ctx[0], slot, out);
@@ -2752,11 +2807,6 @@ void fscl_amd_curve_output(const char *fname, const scan_t *s, const fscl_amd_cu
 static double g_surface_ms;
 double fscl_amd_surface_last_ms(void) { return g_surface_ms; }
 
-static unsigned long long dev_terms(int l) {
-  fsclg_stats_t st;
-  return fsclg_get_stats(D.ctx[l], &st) == FSCLG_OK ? st.n_terms : 0ull;
-}
-
 /* a list fsclg_surface_submit takes: 1 .. 64 values in [LOG_AD_MIN, LOG_AD_MAX], strictly ascending */
 static int surface_list_ok(const double *la, int n) {
   int k;
@@ -2766,11 +2816,18 @@ static int surface_list_ok(const double *la, int n) {
   return 1;
 }
 
+static int surface_submit(int l, int lo, int hi, const dev_job_t *j) {
+  return fsclg_surface_submit(D.ctx[l], 0, 0, j->runs + lo, hi - lo, j->la + (size_t)lo * j->n_la, j->n_la, j->eval_range);
+}
+static int surface_wait(int k, int lo, const dev_job_t *j) {
+  return fsclg_surface_wait(D.ctx[k], 0, j->pts + j->poff[lo], j->val + j->poff[lo] * j->n_la);
+}
+
 int fscl_amd_scan_surface(scan_t *s, sm_ptable_t *sm, int eval_range, const fscl_amd_surface_req_t *req, int n,
                           fscl_amd_surfaces_t *out) {
   fsclg_run_t *runs;
-  double *cost, *la, dev_ms[FH_MAX_DEV];
-  int *idx, lo[FH_MAX_DEV], hi[FH_MAX_DEV], i, j, l, k, m, nla, r = FSCLG_OK;
+  double *cost, dev_ms[FH_MAX_DEV] = {0.};
+  int *idx, lo[FH_MAX_DEV], hi[FH_MAX_DEV], i, j, m, nla, r = FSCLG_OK;
   uint64_t po = 0, co = 0;
   if (!s || !sm || !out || n < 0 || (n && !req)) return FSCLG_E_ARG;
   memset(out, 0, sizeof *out);
@@ -2794,66 +2851,49 @@ int fscl_amd_scan_surface(scan_t *s, sm_ptable_t *sm, int eval_range, const fscl
   out->pts = fh_calloc(po ? po : 1, sizeof *out->pts, "surface points");
   out->sm = fh_calloc(co ? co : 1, sizeof *out->sm, "surface values");
   set_original_rows();
-  g_surface_ms = 0.;
-  for (l = 0; l < FH_MAX_DEV; l++) dev_ms[l] = 0.;
   idx = fh_malloc(sizeof(int) * (n ? n : 1), "surface requests");
   cost = fh_malloc(sizeof(double) * (n ? n : 1), "cost");
   for (nla = 1; nla <= FSCL_AMD_SURFACE_MAX_LA && r == FSCLG_OK; nla++) {
+    dev_job_t job = {0};
     fsclg_run_t *gr;
     fsclg_point_t *gp;
-    double *gs;
-    size_t np = 0, off;
+    double *la, *gs;
+    size_t *poff, np;
     for (i = 0, m = 0; i < n; i++)
-      if (req[i].n_la == nla) { idx[m] = i; cost[m] = window_cost(req[i].chr, eval_range) * runs[i].count * nla; np += (size_t)runs[i].count; m++; }
+      if (req[i].n_la == nla) { idx[m] = i; cost[m] = window_cost(req[i].chr, eval_range) * runs[i].count * nla; m++; }
     if (m == 0) continue;
     gr = fh_malloc(sizeof *gr * (size_t)m, "surface runs");
     la = fh_malloc(sizeof(double) * (size_t)m * nla, "surface alphas");
+    for (j = 0; j < m; j++) { gr[j] = runs[idx[j]]; memcpy(la + (size_t)j * nla, req[idx[j]].la, sizeof(double) * (size_t)nla); }
+    poff = run_offsets(gr, m);
+    np = poff[m];
     gp = fh_malloc(sizeof *gp * (np ? np : 1), "surface points");
     gs = fh_malloc(sizeof(double) * (np ? np : 1) * nla, "surface values");
-    for (j = 0; j < m; j++) { gr[j] = runs[idx[j]]; memcpy(la + (size_t)j * nla, req[idx[j]].la, sizeof(double) * (size_t)nla); }
-    for (l = 0; l < D.n_dev; l++) {
-      if (D.n_dev <= 1) { lo[l] = 0; hi[l] = m; }
-      else fscl_amd_partition(cost, m, l, D.n_dev, &lo[l], &hi[l]);
-    }
-    for (l = 0; l < D.n_dev; l++) out->n_terms -= dev_terms(l);
-    for (l = 0; l < D.n_dev && r == FSCLG_OK; l++) {
-      DBG("surfaces: device %d, %d alphas, requests [%d, %d)\n", D.dev[l], nla, lo[l], hi[l]);
-      r = fsclg_surface_submit(D.ctx[l], 0, 0, gr + lo[l], hi[l] - lo[l], la + (size_t)lo[l] * nla, nla, eval_range);
-    }
-    for (k = 0; k < l; k++) {
-      int rw;
-      if (k == l - 1 && r != FSCLG_OK) break; /* the submit that failed left nothing to wait for */
-      for (j = 0, off = 0; j < lo[k]; j++) off += (size_t)gr[j].count;
-      rw = fsclg_surface_wait(D.ctx[k], 0, gp + off, gs + off * nla);
-      dev_ms[k] += fsclg_surface_last_ms(D.ctx[k], 0);
-      if (r == FSCLG_OK) r = rw;
-    }
-    for (l = 0; l < D.n_dev; l++) out->n_terms += dev_terms(l);
-    for (j = 0, off = 0; j < m && r == FSCLG_OK; j++) { /* back into request order */
+    local_shares(cost, m, lo, hi);
+    job.runs = gr; job.la = la; job.n_la = nla; job.eval_range = eval_range; job.poff = poff; job.pts = gp; job.val = gs;
+    r = run_on_devices("surfaces", lo, hi, surface_submit, surface_wait, fsclg_surface_last_ms, &job, dev_ms, &out->n_terms);
+    for (j = 0; j < m && r == FSCLG_OK; j++) { /* back into request order */
       const fscl_amd_surface_hdr_t *h = out->hdr + idx[j];
-      memcpy(out->pts + h->pos_off, gp + off, sizeof *gp * (size_t)h->n_pos);
-      memcpy(out->sm + h->cell_off, gs + off * nla, sizeof(double) * (size_t)h->n_pos * nla);
-      off += (size_t)h->n_pos;
+      memcpy(out->pts + h->pos_off, gp + poff[j], sizeof *gp * (size_t)h->n_pos);
+      memcpy(out->sm + h->cell_off, gs + poff[j] * nla, sizeof(double) * (size_t)h->n_pos * nla);
     }
-    free(gr); free(la); free(gp); free(gs);
+    free(gr); free(la); free(poff); free(gp); free(gs);
   }
-  for (l = 0; l < D.n_dev; l++)
-    if (dev_ms[l] > g_surface_ms) g_surface_ms = dev_ms[l]; /* the devices run side by side */
+  g_surface_ms = dev_ms_max(dev_ms); /* (a length after another on each device, the devices side by side) */
   free(runs); free(idx); free(cost);
   if (r != FSCLG_OK) fscl_amd_surfaces_free(out);
   return r;
 }
 
-int fscl_amd_scan_point_surfaces(scan_t *s, sm_ptable_t *sm, int eval_range, int top, int halfwidth, int step,
-                                 double la_lo, double la_hi, int n_grid, fscl_amd_surfaces_t *out) {
-  fscl_amd_surface_req_t *req;
-  char *used;
-  int n = 0, i, k, r;
-  if (!s || !sm || !out || (!s->scan_pts && s->n_scan_pts) || s->n_scan_pts < 0 || top < 0 || halfwidth < 0 || step < 1)
-    return FSCLG_E_ARG;
-  memset(out, 0, sizeof *out);
-  req = fh_calloc(top ? top : 1, sizeof *req, "surface requests");
-  used = fh_calloc(s->n_scan_pts ? s->n_scan_pts : 1, 1, "surface requests");
+/* the requests around the scan points of greatest CLR, `top` at most: by descending CLR (a NaN
+   never), none within `halfwidth` of one already taken, each centred on its point with the point's
+   lalpha inserted into the alpha grid.  Returns them malloc'd, *n_out their number; NULL: the
+   grid was refused */
+static fscl_amd_surface_req_t *top_peak_requests(const scan_t *s, int top, int halfwidth, int step, double la_lo,
+                                                 double la_hi, int n_grid, int *n_out) {
+  fscl_amd_surface_req_t *req = fh_calloc(top ? top : 1, sizeof *req, "peak requests");
+  char *used = fh_calloc(s->n_scan_pts ? s->n_scan_pts : 1, 1, "peak requests");
+  int n = 0, i, k;
   while (n < top) { /* descending CLR, as the --bootstrap-top points */
     int best = -1;
     for (i = 0; i < s->n_scan_pts; i++)
@@ -2869,10 +2909,23 @@ int fscl_amd_scan_point_surfaces(scan_t *s, sm_ptable_t *sm, int eval_range, int
     req[n].chr = s->scan_pts[best].chr; req[n].centre_pos = s->scan_pts[best].sweep_pos;
     req[n].halfwidth = halfwidth; req[n].step = step; req[n].point = best;
     req[n].n_la = fscl_amd_surface_alphas(la_lo, la_hi, n_grid, s->scan_pts[best].lalpha, req[n].la);
-    if (req[n].n_la < 1) { free(req); free(used); return FSCLG_E_ARG; }
+    if (req[n].n_la < 1) { free(req); free(used); return NULL; }
     n++;
   }
   free(used);
+  *n_out = n;
+  return req;
+}
+
+int fscl_amd_scan_point_surfaces(scan_t *s, sm_ptable_t *sm, int eval_range, int top, int halfwidth, int step,
+                                 double la_lo, double la_hi, int n_grid, fscl_amd_surfaces_t *out) {
+  fscl_amd_surface_req_t *req;
+  int n, r;
+  if (!s || !sm || !out || (!s->scan_pts && s->n_scan_pts) || s->n_scan_pts < 0 || top < 0 || halfwidth < 0 || step < 1)
+    return FSCLG_E_ARG;
+  memset(out, 0, sizeof *out);
+  req = top_peak_requests(s, top, halfwidth, step, la_lo, la_hi, n_grid, &n);
+  if (!req) return FSCLG_E_ARG;
   r = fscl_amd_scan_surface(s, sm, eval_range, req, n, out);
   free(req);
   return r;
@@ -2882,23 +2935,9 @@ int fscl_amd_scan_point_surfaces(scan_t *s, sm_ptable_t *sm, int eval_range, int
    and batch: on the uploaded rows (rows NULL: slot 0) or on `rows` (slot 1), as fscl_amd_cellmax_runs */
 int fscl_amd_surface_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int n_runs, const double *la, int n_la,
                           int eval_range, const uint32_t *rows, int batch, fsclg_point_t *pts, double *smv) {
-  int r, slot = 0;
-  if (!s || !sm || (!runs && n_runs) || n_runs < 0) return FSCLG_E_ARG;
-  prepare(s, sm);
+  int slot, r = runs_handle_begin(s, sm, runs, n_runs, rows, &slot);
+  if (r != FSCLG_OK) return r;
   g_surface_ms = 0.;
-  if (rows) {
-    double *nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
-    int i;
-    for (i = 0; i < s->n_snps; i++)
-      if (rows[i] >= (uint32_t)D.rm.n_dev_rows) { free(nul); return FSCLG_E_ARG; }
-    chr_null_sums_32(rows, nul);
-    slot = 1;
-    r = fsclg_slot_set_rows(D.ctx[0], slot, rows, nul);
-    free(nul);
-    if (r != FSCLG_OK) return r;
-  } else {
-    set_original_rows();
-  }
   r = fsclg_surface_submit(D.ctx[0], batch, slot, runs, n_runs, la, n_la, eval_range);
   if (r != FSCLG_OK) return r;
   r = fsclg_surface_wait(D.ctx[0], batch, pts, smv);
@@ -2949,14 +2988,22 @@ static int cond_intervals(const scan_t *s, int chr, const fscl_amd_sweep_t *gv, 
   return m;
 }
 
+static int cond_submit(int l, int lo, int hi, const dev_job_t *j) {
+  return fsclg_cond_submit(D.ctx[l], 0, 0, j->runs + lo, hi - lo, j->la + (size_t)lo * j->n_la, j->n_la,
+                           j->clip + 2 * j->poff[lo], j->eval_range);
+}
+static int cond_wait(int k, int lo, const dev_job_t *j) {
+  return fsclg_cond_wait(D.ctx[k], 0, j->pts + j->poff[lo], j->val + j->poff[lo] * j->n_la);
+}
+
 int fscl_amd_scan_conditional(scan_t *s, sm_ptable_t *sm, int eval_range, const fscl_amd_sweep_t *given, int n_given,
                               int halfwidth, int step, const double *alphas, int n_la, int rounds, double min_clr,
                               fscl_amd_conditional_t *out) {
   fscl_amd_sweep_t *gv;
   long long iv[2 * (FSCL_AMD_COND_MAX_GIVEN + FSCL_AMD_COND_MAX_ROUNDS)];
-  double dev_ms[FH_MAX_DEV], t0;
+  double dev_ms[FH_MAX_DEV] = {0.}, t0;
   size_t rows_cap = 0, given_cap = 0;
-  int ng, i, j, l, k, c, round, r = FSCLG_OK, blk_cap = 0;
+  int ng, i, j, c, round, r = FSCLG_OK, blk_cap = 0;
   if (!sm || !out) return FSCLG_E_ARG;
   memset(out, 0, sizeof *out);
   if (fscl_amd_conditional_check(s, given, n_given, halfwidth, step, alphas, n_la, rounds, min_clr) != 0) return FSCLG_E_ARG;
@@ -2964,9 +3011,8 @@ int fscl_amd_scan_conditional(scan_t *s, sm_ptable_t *sm, int eval_range, const 
   ng = n_given;
   gv = fh_malloc(sizeof *gv * (size_t)(n_given + FSCL_AMD_COND_MAX_ROUNDS * (s->n_chromosomes > 0 ? s->n_chromosomes : 1)), "given sweeps");
   if (n_given) memcpy(gv, given, sizeof *gv * (size_t)n_given);
-  g_cond_ms = 0.;
-  for (l = 0; l < FH_MAX_DEV; l++) dev_ms[l] = 0.;
   for (round = 1; round <= rounds && r == FSCLG_OK; round++) {
+    dev_job_t job = {0};
     fscl_amd_sites_t st;
     fsclg_site_req_t *req = fh_malloc(sizeof *req * (size_t)(ng ? ng : 1), "given walks");
     fsclg_run_t *runs = NULL;
@@ -2974,7 +3020,7 @@ int fscl_amd_scan_conditional(scan_t *s, sm_ptable_t *sm, int eval_range, const 
     int32_t *clip, *want;
     int *run_chr_first; /* per chromosome: its first run, or -1 */
     double *cost, *lav, *smv, **g;
-    size_t np = 0, off;
+    size_t *poff, np, off;
     int n_runs = 0, run_cap = 0, lo[FH_MAX_DEV], hi[FH_MAX_DEV], added = 0, blk0 = out->n_blocks;
     for (i = 0; i < ng; i++) { req[i].chr = gv[i].chr; req[i].pos = gv[i].pos; req[i].lalpha = log(gv[i].alpha); }
     r = fscl_amd_scan_sites(s, sm, eval_range, req, ng, &st); /* (prepare, the original rows in slot 0) */
@@ -2997,12 +3043,14 @@ int fscl_amd_scan_conditional(scan_t *s, sm_ptable_t *sm, int eval_range, const 
           if (n_runs == run_cap) { run_cap = run_cap ? 2 * run_cap : 64; runs = fh_realloc(runs, sizeof *runs * (size_t)run_cap, "runs"); }
           runs[n_runs].chr = c; runs[n_runs].start_pos = (int)(s->chr_limits[c].start_pos + k0 * step);
           runs[n_runs].step = step; runs[n_runs].count = (int)cnt;
-          n_runs++; np += (size_t)cnt;
+          n_runs++;
         }
       }
     }
     run_chr_first[s->n_chromosomes] = n_runs;
     fscl_amd_sites_free(&st);
+    poff = run_offsets(runs, n_runs);
+    np = poff[n_runs];
     clip = fh_malloc(sizeof(int32_t) * 2 * (np ? np : 1), "clips");
     want = fh_malloc(sizeof(int32_t) * (np ? np : 1), "positions");
     pts = fh_malloc(sizeof *pts * (np ? np : 1), "conditional points");
@@ -3018,25 +3066,10 @@ int fscl_amd_scan_conditional(scan_t *s, sm_ptable_t *sm, int eval_range, const 
         want[off] = sp; clip[2 * off] = a; clip[2 * off + 1] = b;
       }
     }
-    for (l = 0; l < D.n_dev; l++) {
-      if (D.n_dev <= 1) { lo[l] = 0; hi[l] = n_runs; }
-      else fscl_amd_partition(cost, n_runs, l, D.n_dev, &lo[l], &hi[l]);
-    }
-    for (l = 0; l < D.n_dev; l++) out->n_terms -= dev_terms(l);
-    for (l = 0; l < D.n_dev && r == FSCLG_OK; l++) {
-      for (j = 0, off = 0; j < lo[l]; j++) off += (size_t)runs[j].count;
-      DBG("conditional: round %d, device %d, runs [%d, %d)\n", round, D.dev[l], lo[l], hi[l]);
-      r = fsclg_cond_submit(D.ctx[l], 0, 0, runs + lo[l], hi[l] - lo[l], lav + (size_t)lo[l] * n_la, n_la, clip + 2 * off, eval_range);
-    }
-    for (k = 0; k < l; k++) {
-      int rw;
-      if (k == l - 1 && r != FSCLG_OK) break; /* the submit that failed left nothing to wait for */
-      for (j = 0, off = 0; j < lo[k]; j++) off += (size_t)runs[j].count;
-      rw = fsclg_cond_wait(D.ctx[k], 0, pts + off, smv + off * n_la);
-      dev_ms[k] += fsclg_cond_last_ms(D.ctx[k], 0);
-      if (r == FSCLG_OK) r = rw;
-    }
-    for (l = 0; l < D.n_dev; l++) out->n_terms += dev_terms(l);
+    local_shares(cost, n_runs, lo, hi);
+    job.runs = runs; job.la = lav; job.n_la = n_la; job.eval_range = eval_range; job.poff = poff; job.clip = clip;
+    job.pts = pts; job.val = smv;
+    r = run_on_devices("conditional", lo, hi, cond_submit, cond_wait, fsclg_cond_last_ms, &job, dev_ms, &out->n_terms);
     if (r == FSCLG_OK) {
       for (off = 0; off < np; off++)
         if (pts[off].sweep_pos != want[off])
@@ -3065,11 +3098,9 @@ int fscl_amd_scan_conditional(scan_t *s, sm_ptable_t *sm, int eval_range, const 
       out->fold_s += fh_now() - t0;
       for (c = 0; c < s->n_chromosomes; c++) { /* one block per chromosome with a given sweep */
         fscl_amd_cond_block_t *h;
-        size_t row0 = out->n_rows, nrow = 0;
+        const size_t row0 = out->n_rows + poff[run_chr_first[c]], nrow = poff[run_chr_first[c + 1]] - poff[run_chr_first[c]];
         int best = -1, m = 0;
         if (!g[c]) continue;
-        for (i = 0; i < run_chr_first[c]; i++) row0 += (size_t)runs[i].count;
-        for (i = run_chr_first[c]; i < run_chr_first[c + 1]; i++) nrow += (size_t)runs[i].count;
         if (out->n_blocks == blk_cap) { blk_cap = blk_cap ? 2 * blk_cap : 16; out->blk = fh_realloc(out->blk, sizeof *out->blk * (size_t)blk_cap, "conditional blocks"); }
         h = out->blk + out->n_blocks++;
         memset(h, 0, sizeof *h);
@@ -3098,11 +3129,10 @@ int fscl_amd_scan_conditional(scan_t *s, sm_ptable_t *sm, int eval_range, const 
       }
     }
     for (c = 0; c < s->n_chromosomes; c++) free(g[c]);
-    free(g); free(run_chr_first); free(runs); free(clip); free(want); free(pts); free(smv); free(cost); free(lav);
+    free(g); free(run_chr_first); free(runs); free(poff); free(clip); free(want); free(pts); free(smv); free(cost); free(lav);
     if (!added) break;
   }
-  for (l = 0; l < D.n_dev; l++)
-    if (dev_ms[l] > g_cond_ms) g_cond_ms = dev_ms[l]; /* the devices run side by side */
+  g_cond_ms = dev_ms_max(dev_ms); /* (a round after another on each device, the devices side by side) */
   free(gv);
   if (r != FSCLG_OK) fscl_amd_conditional_free(out);
   return r;
@@ -3113,23 +3143,9 @@ int fscl_amd_scan_conditional(scan_t *s, sm_ptable_t *sm, int eval_range, const 
 int fscl_amd_cond_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int n_runs, const double *la, int n_la,
                        const int32_t *clip, int eval_range, const uint32_t *rows, int batch, fsclg_point_t *pts,
                        double *smv) {
-  int r, slot = 0;
-  if (!s || !sm || (!runs && n_runs) || n_runs < 0) return FSCLG_E_ARG;
-  prepare(s, sm);
+  int slot, r = runs_handle_begin(s, sm, runs, n_runs, rows, &slot);
+  if (r != FSCLG_OK) return r;
   g_cond_ms = 0.;
-  if (rows) {
-    double *nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
-    int i;
-    for (i = 0; i < s->n_snps; i++)
-      if (rows[i] >= (uint32_t)D.rm.n_dev_rows) { free(nul); return FSCLG_E_ARG; }
-    chr_null_sums_32(rows, nul);
-    slot = 1;
-    r = fsclg_slot_set_rows(D.ctx[0], slot, rows, nul);
-    free(nul);
-    if (r != FSCLG_OK) return r;
-  } else {
-    set_original_rows();
-  }
   r = fsclg_cond_submit(D.ctx[0], batch, slot, runs, n_runs, la, n_la, clip, eval_range);
   if (r != FSCLG_OK) return r;
   r = fsclg_cond_wait(D.ctx[0], batch, pts, smv);
@@ -3145,13 +3161,21 @@ int fscl_amd_cond_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int 
 static double g_blocks_ms;
 double fscl_amd_blocks_last_ms(void) { return g_blocks_ms; }
 
+static int blocks_submit(int l, int lo, int hi, const dev_job_t *j) {
+  return fsclg_blocks_submit(D.ctx[l], 0, 0, j->runs + lo, hi - lo, j->la + (size_t)lo * j->n_la, j->n_la, j->blk + lo,
+                             j->eval_range);
+}
+static int blocks_wait(int k, int lo, const dev_job_t *j) {
+  return fsclg_blocks_wait(D.ctx[k], 0, j->pts + j->poff[lo], j->val + j->coff[lo], j->cnt + j->coff[lo]);
+}
+
 int fscl_amd_scan_blocks(scan_t *s, sm_ptable_t *sm, int eval_range, const fscl_amd_surface_req_t *req, int n,
                          int block_bp, fscl_amd_blocks_t *out) {
   fscl_amd_surfaces_t sf;
   fsclg_run_t *runs;
   fsclg_blocks_t *blk;
-  double *cost, *la, dev_ms[FH_MAX_DEV];
-  int *idx, lo[FH_MAX_DEV], hi[FH_MAX_DEV], i, j, l, k, m, nla, r = FSCLG_OK;
+  double *cost, dev_ms[FH_MAX_DEV] = {0.};
+  int *idx, lo[FH_MAX_DEV], hi[FH_MAX_DEV], i, j, m, nla, r = FSCLG_OK;
   uint64_t po = 0, co = 0;
   if (!s || !sm || !out || n < 0 || (n && !req) || block_bp < 1 || eval_range < 0) return FSCLG_E_ARG;
   memset(out, 0, sizeof *out);
@@ -3210,60 +3234,44 @@ int fscl_amd_scan_blocks(scan_t *s, sm_ptable_t *sm, int eval_range, const fscl_
   out->pts = fh_calloc(po ? po : 1, sizeof *out->pts, "block points");
   out->bs = fh_calloc(co ? co : 1, sizeof *out->bs, "block sums");
   out->cnt = fh_calloc(co ? co : 1, sizeof *out->cnt, "block counts");
-  g_blocks_ms = 0.;
-  for (l = 0; l < FH_MAX_DEV; l++) dev_ms[l] = 0.;
   idx = fh_malloc(sizeof(int) * (n ? n : 1), "block requests");
   cost = fh_malloc(sizeof(double) * (n ? n : 1), "cost");
   for (nla = 1; nla <= FSCL_AMD_SURFACE_MAX_LA && r == FSCLG_OK; nla++) {
+    dev_job_t job = {0};
     fsclg_run_t *gr;
     fsclg_blocks_t *gb;
     fsclg_point_t *gp;
-    double *gs;
+    double *la, *gs;
     uint32_t *gc;
-    size_t np = 0, ncell = 0, off, coff;
+    size_t *poff, *coff, np, ncell;
     for (i = 0, m = 0; i < n; i++)
-      if (req[i].n_la == nla) {
-        idx[m] = i; cost[m] = window_cost(req[i].chr, eval_range) * runs[i].count * nla;
-        np += (size_t)runs[i].count; ncell += (size_t)runs[i].count * blk[i].nb * nla; m++;
-      }
+      if (req[i].n_la == nla) { idx[m] = i; cost[m] = window_cost(req[i].chr, eval_range) * runs[i].count * nla; m++; }
     if (m == 0) continue;
     gr = fh_malloc(sizeof *gr * (size_t)m, "block runs");
     gb = fh_malloc(sizeof *gb * (size_t)m, "blocks");
     la = fh_malloc(sizeof(double) * (size_t)m * nla, "block alphas");
+    for (j = 0; j < m; j++) { gr[j] = runs[idx[j]]; gb[j] = blk[idx[j]]; memcpy(la + (size_t)j * nla, req[idx[j]].la, sizeof(double) * (size_t)nla); }
+    poff = run_offsets(gr, m);
+    coff = fh_malloc(sizeof(size_t) * ((size_t)m + 1), "run offsets"); /* the cells before run j: positions x blocks x alphas */
+    for (j = 0, coff[0] = 0; j < m; j++) coff[j + 1] = coff[j] + (size_t)gr[j].count * gb[j].nb * nla;
+    np = poff[m]; ncell = coff[m];
     gp = fh_malloc(sizeof *gp * (np ? np : 1), "block points");
     gs = fh_malloc(sizeof(double) * (ncell ? ncell : 1), "block sums");
     gc = fh_malloc(sizeof(uint32_t) * (ncell ? ncell : 1), "block counts");
-    for (j = 0; j < m; j++) { gr[j] = runs[idx[j]]; gb[j] = blk[idx[j]]; memcpy(la + (size_t)j * nla, req[idx[j]].la, sizeof(double) * (size_t)nla); }
-    for (l = 0; l < D.n_dev; l++) {
-      if (D.n_dev <= 1) { lo[l] = 0; hi[l] = m; }
-      else fscl_amd_partition(cost, m, l, D.n_dev, &lo[l], &hi[l]);
-    }
-    for (l = 0; l < D.n_dev; l++) out->n_terms -= dev_terms(l);
-    for (l = 0; l < D.n_dev && r == FSCLG_OK; l++) {
-      DBG("blocks: device %d, %d alphas, requests [%d, %d)\n", D.dev[l], nla, lo[l], hi[l]);
-      r = fsclg_blocks_submit(D.ctx[l], 0, 0, gr + lo[l], hi[l] - lo[l], la + (size_t)lo[l] * nla, nla, gb + lo[l], eval_range);
-    }
-    for (k = 0; k < l; k++) {
-      int rw;
-      if (k == l - 1 && r != FSCLG_OK) break; /* the submit that failed left nothing to wait for */
-      for (j = 0, off = 0, coff = 0; j < lo[k]; j++) { off += (size_t)gr[j].count; coff += (size_t)gr[j].count * gb[j].nb * nla; }
-      rw = fsclg_blocks_wait(D.ctx[k], 0, gp + off, gs + coff, gc + coff);
-      dev_ms[k] += fsclg_blocks_last_ms(D.ctx[k], 0);
-      if (r == FSCLG_OK) r = rw;
-    }
-    for (l = 0; l < D.n_dev; l++) out->n_terms += dev_terms(l);
-    for (j = 0, off = 0, coff = 0; j < m && r == FSCLG_OK; j++) { /* back into request order */
+    local_shares(cost, m, lo, hi);
+    job.runs = gr; job.la = la; job.n_la = nla; job.eval_range = eval_range; job.poff = poff; job.coff = coff; job.blk = gb;
+    job.pts = gp; job.val = gs; job.cnt = gc;
+    r = run_on_devices("blocks", lo, hi, blocks_submit, blocks_wait, fsclg_blocks_last_ms, &job, dev_ms, &out->n_terms);
+    for (j = 0; j < m && r == FSCLG_OK; j++) { /* back into request order */
       const fscl_amd_blocks_hdr_t *h = out->hdr + idx[j];
-      const size_t nc = (size_t)h->n_pos * h->nb * nla;
-      memcpy(out->pts + h->pos_off, gp + off, sizeof *gp * (size_t)h->n_pos);
-      memcpy(out->bs + h->cell_off, gs + coff, sizeof(double) * nc);
-      memcpy(out->cnt + h->cell_off, gc + coff, sizeof(uint32_t) * nc);
-      off += (size_t)h->n_pos; coff += nc;
+      const size_t nc = coff[j + 1] - coff[j];
+      memcpy(out->pts + h->pos_off, gp + poff[j], sizeof *gp * (size_t)h->n_pos);
+      memcpy(out->bs + h->cell_off, gs + coff[j], sizeof(double) * nc);
+      memcpy(out->cnt + h->cell_off, gc + coff[j], sizeof(uint32_t) * nc);
     }
-    free(gr); free(gb); free(la); free(gp); free(gs); free(gc);
+    free(gr); free(gb); free(la); free(poff); free(coff); free(gp); free(gs); free(gc);
   }
-  for (l = 0; l < D.n_dev; l++)
-    if (dev_ms[l] > g_blocks_ms) g_blocks_ms = dev_ms[l]; /* the devices run side by side */
+  g_blocks_ms = dev_ms_max(dev_ms); /* (as the surfaces) */
   free(runs); free(blk); free(idx); free(cost);
   if (r != FSCLG_OK) fscl_amd_blocks_free(out);
   return r;
@@ -3272,33 +3280,13 @@ int fscl_amd_scan_blocks(scan_t *s, sm_ptable_t *sm, int eval_range, const fscl_
 int fscl_amd_scan_point_jackknife(scan_t *s, sm_ptable_t *sm, int eval_range, int top, int halfwidth, int step,
                                   double la_lo, double la_hi, int n_grid, int block_bp, fscl_amd_blocks_t *out) {
   fscl_amd_surface_req_t *req;
-  char *used;
-  int n = 0, i, k, r;
+  int n, r;
   if (!s || !sm || !out || (!s->scan_pts && s->n_scan_pts) || s->n_scan_pts < 0 || top < 0 || halfwidth < 0 || step < 1 ||
       block_bp < 1)
     return FSCLG_E_ARG;
   memset(out, 0, sizeof *out);
-  req = fh_calloc(top ? top : 1, sizeof *req, "jackknife requests");
-  used = fh_calloc(s->n_scan_pts ? s->n_scan_pts : 1, 1, "jackknife requests");
-  while (n < top) { /* descending CLR, as the --surface-top and --bootstrap-top points */
-    int best = -1;
-    for (i = 0; i < s->n_scan_pts; i++)
-      if (!used[i] && s->scan_pts[i].clr == s->scan_pts[i].clr && (best < 0 || s->scan_pts[i].clr > s->scan_pts[best].clr))
-        best = i;
-    if (best < 0) break;
-    used[best] = 1;
-    for (k = 0; k < n; k++) {
-      long long d = (long long)s->scan_pts[best].sweep_pos - req[k].centre_pos;
-      if (req[k].chr == s->scan_pts[best].chr && (d < 0 ? -d : d) <= halfwidth) break;
-    }
-    if (k < n) continue;
-    req[n].chr = s->scan_pts[best].chr; req[n].centre_pos = s->scan_pts[best].sweep_pos;
-    req[n].halfwidth = halfwidth; req[n].step = step; req[n].point = best;
-    req[n].n_la = fscl_amd_surface_alphas(la_lo, la_hi, n_grid, s->scan_pts[best].lalpha, req[n].la);
-    if (req[n].n_la < 1) { free(req); free(used); return FSCLG_E_ARG; }
-    n++;
-  }
-  free(used);
+  req = top_peak_requests(s, top, halfwidth, step, la_lo, la_hi, n_grid, &n); /* the --surface-top points */
+  if (!req) return FSCLG_E_ARG;
   r = fscl_amd_scan_blocks(s, sm, eval_range, req, n, block_bp, out);
   free(req);
   return r;
@@ -3308,23 +3296,9 @@ int fscl_amd_scan_point_jackknife(scan_t *s, sm_ptable_t *sm, int eval_range, in
 int fscl_amd_blocks_runs(scan_t *s, sm_ptable_t *sm, const fsclg_run_t *runs, int n_runs, const double *la, int n_la,
                          const fsclg_blocks_t *blk, int eval_range, const uint32_t *rows, int batch, fsclg_point_t *pts,
                          double *bs, uint32_t *cnt) {
-  int r, slot = 0;
-  if (!s || !sm || (!runs && n_runs) || n_runs < 0) return FSCLG_E_ARG;
-  prepare(s, sm);
+  int slot, r = runs_handle_begin(s, sm, runs, n_runs, rows, &slot);
+  if (r != FSCLG_OK) return r;
   g_blocks_ms = 0.;
-  if (rows) {
-    double *nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
-    int i;
-    for (i = 0; i < s->n_snps; i++)
-      if (rows[i] >= (uint32_t)D.rm.n_dev_rows) { free(nul); return FSCLG_E_ARG; }
-    chr_null_sums_32(rows, nul);
-    slot = 1;
-    r = fsclg_slot_set_rows(D.ctx[0], slot, rows, nul);
-    free(nul);
-    if (r != FSCLG_OK) return r;
-  } else {
-    set_original_rows();
-  }
   r = fsclg_blocks_submit(D.ctx[0], batch, slot, runs, n_runs, la, n_la, blk, eval_range);
   if (r != FSCLG_OK) return r;
   r = fsclg_blocks_wait(D.ctx[0], batch, pts, bs, cnt);
@@ -3361,11 +3335,8 @@ int fscl_amd_scan_sites(scan_t *s, sm_ptable_t *sm, int eval_range, const fsclg_
   g_sites_ms = 0.;
   cost = fh_malloc(sizeof(double) * (n ? n : 1), "cost");
   for (i = 0; i < n; i++) cost[i] = window_cost(req[i].chr, eval_range);
-  for (l = 0; l < D.n_dev; l++) {
-    if (D.n_dev <= 1) { lo[l] = 0; hi[l] = n; }
-    else fscl_amd_partition(cost, n, l, D.n_dev, &lo[l], &hi[l]);
-    nt[l] = 0;
-  }
+  local_shares(cost, n, lo, hi);
+  for (l = 0; l < D.n_dev; l++) nt[l] = 0;
   free(cost);
   out->hdr = fh_malloc(sizeof(fscl_amd_site_hdr_t) * (n ? n : 1), "site headers");
   for (l = 0; l < D.n_dev && r == FSCLG_OK; l++) {

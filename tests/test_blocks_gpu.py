@@ -524,6 +524,38 @@ def test_golden_g2(built):
     assert not bad, f"{len(bad)} mismatches:\n" + "\n".join(bad[:12])
 
 
+def test_two_devices_give_the_same_blocks(built, tmp):
+    """The requests of test_golden_g2 on five scan points of g2, once on one device and once split over two:
+    the same headers, points, sums, counts and file.  One request takes the 5-alpha grid alone (no g2 point's
+    lalpha is a grid value), so of the 5-lists one device's share is empty; the four 6-lists go to both."""
+    step, bp = 500, 20000
+    scan, tab = setup(GOLD / "g2.snp")
+    fscl_amd.scan_chromosome(scan, tab)
+    pts = fscl_amd.points(scan)
+    assert len(pts) >= 5
+    las = [fscl_amd.surface_alphas(wr.LOG_AD_MIN, wr.LOG_AD_MAX, 5, float(pts["lalpha"][i])) for i in range(5)]
+    las[2] = fscl_amd.surface_alphas(wr.LOG_AD_MIN, wr.LOG_AD_MAX, 5)
+    assert [len(la) for la in las] == [6, 6, 5, 6, 6], "one 5-list between two pairs of 6-lists"
+    req = [(int(pts["chr"][i]), int(pts["sweep_pos"][i]), 2 * step, step, las[i], i) for i in range(5)]
+
+    def evaluate(path):
+        bks = fscl_amd.scan_blocks(scan, tab, req, bp)
+        fscl_amd.jackknife_output(path, scan, bks)
+        return bks
+    fscl_amd.set_devices([0, 0])
+    try:
+        two = evaluate(tmp / "two.txt")
+        assert fscl_amd.get_lib().fscl_amd_n_devices() == 2
+    finally:
+        fscl_amd.set_device(0)
+    one = evaluate(tmp / "one.txt")
+    assert len(one) == len(two) == 5 and all(int(b.hdr["nb"]) > 1 for b in one), "several blocks per request"
+    for a, b in zip(one, two):
+        assert a.hdr.tobytes() == b.hdr.tobytes() and a.pts.tobytes() == b.pts.tobytes()
+        assert a.bs.tobytes() == b.bs.tobytes() and a.cnt.tobytes() == b.cnt.tobytes()
+    assert (tmp / "two.txt").read_bytes() == (tmp / "one.txt").read_bytes() and (tmp / "one.txt").stat().st_size > 0
+
+
 # ------------------------------------------------------------------ 10. crafted influence
 @device_guard
 def test_crafted_influence(shim):

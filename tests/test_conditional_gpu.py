@@ -18,7 +18,7 @@ import cond_ref as cr
 import fscl_amd
 import walk_ref as wr
 from fscl_amd import synth
-from util import CLI, ROOT
+from util import CLI, GOLD, ROOT
 
 sys.path.insert(0, str(ROOT / "oracle"))
 import oracle as orc  # noqa: E402
@@ -462,6 +462,40 @@ def test_rounds(lib):
     assert len(blocks) >= 2, "the synthetic sweep's shoulder should add a second round"
     one = fscl_amd.scan_conditional(lib.scan, lib.tab, given, 0, STEP, LA, rounds=3, min_clr=1e9, eval_range=ER)
     assert len(one) == 1 and int(one[0].hdr["added"]) == 0 and one[0].rows.tobytes() == blocks[0].rows.tobytes()
+
+
+def test_two_devices_give_the_same_blocks(built, tmp):
+    """g2.snp, given its two highest scan points that lie well apart on its one chromosome, two rounds: each
+    sweep's interval of 5001 positions is two runs (a piece holds 4096), so a round's four or more runs are
+    split over the devices.  One device and two give the same blocks, rows, given sweeps, terms and file."""
+    halfwidth, step = 25000, 10
+    scan, tab = setup(GOLD / "g2.snp")
+    fscl_amd.scan_chromosome(scan, tab)
+    pts = fscl_amd.points(scan)
+    order = [int(i) for i in np.argsort(-pts["clr"], kind="stable")]
+    far = [i for i in order if abs(int(pts["sweep_pos"][i]) - int(pts["sweep_pos"][order[0]])) > 4 * halfwidth]
+    given = [(int(pts["chr"][i]), int(pts["sweep_pos"][i]), math.exp(float(pts["lalpha"][i]))) for i in (order[0], far[0])]
+    assert given[0][0] == given[1][0] == 0 and scan.contents.n_chromosomes == 1
+
+    def evaluate(path):
+        blocks = fscl_amd.scan_conditional(scan, tab, given, halfwidth, step, LA, rounds=2)
+        fscl_amd.conditional_output(path, scan, blocks)
+        return blocks, fscl_amd.conditional_last_terms()
+    fscl_amd.set_devices([0, 0])
+    try:
+        two, terms2 = evaluate(tmp / "two.txt")
+        assert fscl_amd.get_lib().fscl_amd_n_devices() == 2
+    finally:
+        fscl_amd.set_device(0)
+    one, terms1 = evaluate(tmp / "one.txt")
+    assert len(one) == len(two) and 1 <= len(one) <= 2 and [int(b.hdr["round"]) for b in one] == list(range(1, len(one) + 1))
+    assert 2 * 4096 < 2 * (2 * halfwidth // step) <= len(one[0].rows) <= 2 * (2 * halfwidth // step + 1), \
+        "two intervals of two runs each"
+    for a, b in zip(one, two):
+        assert a.hdr.tobytes() == b.hdr.tobytes() and a.rows.tobytes() == b.rows.tobytes() and a.given.tobytes() == b.given.tobytes()
+    print(f"conditional terms: one device {terms1}, two devices {terms2}")
+    assert terms1 == terms2 > 0
+    assert (tmp / "two.txt").read_bytes() == (tmp / "one.txt").read_bytes() and (tmp / "one.txt").stat().st_size > 0
 
 
 def test_refusals(lib, monkeypatch):

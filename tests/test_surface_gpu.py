@@ -364,6 +364,41 @@ def test_golden(built, name):
     assert not bad, f"{name}: {len(bad)} mismatches:\n" + "\n".join(bad[:12])
 
 
+def test_two_devices_give_the_same_surfaces(built, tmp):
+    """The requests of test_golden on five scan points of g2, once on one device and once split over two:
+    the same headers, points, values, terms and file.  Every g2 point's lalpha lies off the 5-alpha grid
+    (its list has 6 values), so one request takes the grid alone, the list of a point whose lalpha is a
+    grid value: of the 5-lists one device's share is empty, the 6-lists go to both devices and come back
+    into request order around it."""
+    step = 500
+    scan, tab = setup(GOLD / "g2.snp")
+    fscl_amd.scan_chromosome(scan, tab)
+    pts = fscl_amd.points(scan)
+    assert len(pts) >= 5
+    las = [fscl_amd.surface_alphas(wr.LOG_AD_MIN, wr.LOG_AD_MAX, 5, float(pts["lalpha"][i])) for i in range(5)]
+    las[2] = fscl_amd.surface_alphas(wr.LOG_AD_MIN, wr.LOG_AD_MAX, 5)
+    assert [len(la) for la in las] == [6, 6, 5, 6, 6], "one 5-list between two pairs of 6-lists"
+    req = [(int(pts["chr"][i]), int(pts["sweep_pos"][i]), 2 * step, step, las[i], i) for i in range(5)]
+
+    def evaluate(path):
+        sfs = fscl_amd.scan_surface(scan, tab, req)
+        fscl_amd.surface_output(path, scan, sfs, 2.0)
+        return sfs, fscl_amd.surface_last_terms()
+    fscl_amd.set_devices([0, 0])
+    try:
+        two, terms2 = evaluate(tmp / "two.txt")
+        assert fscl_amd.get_lib().fscl_amd_n_devices() == 2
+    finally:
+        fscl_amd.set_device(0)
+    one, terms1 = evaluate(tmp / "one.txt")
+    assert len(one) == len(two) == 5
+    for a, b in zip(one, two):
+        assert a.hdr.tobytes() == b.hdr.tobytes() and a.pts.tobytes() == b.pts.tobytes() and a.sm.tobytes() == b.sm.tobytes()
+    print(f"surface terms: one device {terms1}, two devices {terms2}")
+    assert terms1 == terms2 > 0
+    assert (tmp / "two.txt").read_bytes() == (tmp / "one.txt").read_bytes() and (tmp / "one.txt").stat().st_size > 0
+
+
 # ------------------------------------------------------------------ 6. determinism
 @device_guard
 def test_same_bytes_on_every_batch_and_slot(shim):

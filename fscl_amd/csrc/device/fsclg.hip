@@ -2614,6 +2614,21 @@ sites_kernel(Params P, int pass, const fsclg_site_req_t* __restrict__ req, fsclg
 // workgroup stores them with plain vector stores (host memory), and one thread per position takes the
 // row's first strict maximum in list order from the reference's (-DBL_MAX, LOG_AD_MAX) state and
 // stores the point.  No atomics on the result path, no workgroup waits for another.
+//
+// The conditional sweep scan (fsclg_cond_submit, cond_kernel) is the same body with CLIP: the surface with
+// every walk cut to the sites the candidate sweep owns.  Per position a global site-index interval
+// [lo, hi] comes with the runs (lo > hi: empty), and a walk's value is the null sum plus, in walk order,
+// the terms of its sites inside the interval.  The clip is the only difference between the two kernels:
+// it is intersected with the window when the chunk is set up (two more LDS arrays, which the unclipped
+// instantiation does not hold), and with the walk per item.  The walk bounds nl, nr are those of the
+// block's smallest alpha on the unclipped walk; the left part then runs from min(near, hi) down to
+// max(near - nl, lo) -- the nearest SNP is its first site iff lo <= near <= hi -- and the right part from
+// max(near + 1, lo) up to min(near + nr, hi).  A clipped part is a contiguous piece of the unclipped one,
+// so |d| stays nondecreasing along it once the nearest SNP is inside the alpha's cut (the argument above:
+// the sites the de-collision stepped over lie nearer than the nearest SNP), the lanes inside are still a
+// prefix of the trip, and exact_chunk_add folds them in walk order.  An alpha whose nearest SNP is past
+// its own cut has an empty walk, whether or not the clip holds the nearest SNP.  With the clip covering
+// the window every trip is the unclipped one's, site for site.  Results, point and counters as there.
 #ifndef FSCLG_SURF_B
 #define FSCLG_SURF_B 4  // alphas per wave item (1: no sharing, the A/B build)
 #endif
@@ -2631,6 +2646,9 @@ struct SurfSmem {
   double sm[SURF_CH][SURF_MAX_LA];
   uint32_t len[SURF_CH][SURF_MAX_LA];  // terms of each walk
 };
+struct CondSmem : SurfSmem {
+  int lo[SURF_CH], hi[SURF_CH];  // the clip of each position, cut to its window
+};
 
 // snp_likelihood at log(alpha d) = x for a site of device row r: term_dev's expression
 template <class SM>
@@ -2642,11 +2660,29 @@ __device__ __forceinline__ double surf_term(double x, uint32_t r, const SM& S, c
   return y - null_of<false>(r, S, P);
 }
 
+// The tail of one position of a list kernel (surface, conditional scan, block sums), by one thread: the
+// finished point (la, sm and clr set) goes out with one store (P.out is host memory: no
+// read-modify-write), its cost the position's terms / 1024, and the device counters take, as in any
+// launch, the terms, the null-sum elements and the walks
+__device__ __forceinline__ void store_list_point(const Params& P, int out, const Pt& pt, unsigned long long terms,
+                                                 int n_la) {
+  fsclg_point_t o;
+  write_point(o, pt);
+  o.cost = (uint32_t)min(terms >> 10, 0xFFFFFFFFull);
+  P.out[out] = o;
+  atomicAdd(&P.stats[0], terms);
+  atomicAdd(&P.stats[1], (unsigned long long)pt.n_snps);
+  atomicAdd(&P.stats[2], (unsigned long long)n_la);
+}
+
 // one item: the walks of nb <= SURF_B alphas la[0] < la[1] < ... at one position, by one wave
-__device__ __forceinline__ void surface_block(SurfSmem& S, const Params& P, int pi, const double* __restrict__ lap,
-                                              int k0, int nb, int lane) {
+template <bool CLIP, class SM>
+__device__ __forceinline__ void surface_block(SM& S, const Params& P, int pi, const double* __restrict__ lap, int k0,
+                                              int nb, int lane) {
   const Pt& pt = S.pt[pi];
   const int near = pt.nearest;
+  int clo = 0, chi = 0;  // the position's clip (CLIP)
+  if constexpr (CLIP) { clo = S.lo[pi]; chi = S.hi[pi]; }
   const uint32_t usweep = (uint32_t)pt.sweep ^ POS_BIAS;
   double la[SURF_B], acc[SURF_B];
   uint32_t len[SURF_B];
@@ -2659,7 +2695,7 @@ __device__ __forceinline__ void surface_block(SurfSmem& S, const Params& P, int 
     len[b] = 0;
     alive[b] = b < nb && !(lt0 + la[b] > LOG_AD_MAX);  // the nearest SNP outside: an empty walk
   }
-  if (alive[0]) {  // (la[0] is the block's smallest: no walk of the block otherwise)
+  if (alive[0] && clo <= chi) {  // (la[0] is the block's smallest: no walk of the block otherwise)
     const double la0 = la[0];
     auto outside = [&](int i) { return logt_dev(absdist(P.pr[phys(i)].x, usweep), P.logt3) + la0 > LOG_AD_MAX; };
     const int e = group_search<64>(pt.wstart - 1, near, lane, [&](int m) { return outside(m); });
@@ -2667,7 +2703,7 @@ __device__ __forceinline__ void surface_block(SurfSmem& S, const Params& P, int 
     const bool ok1 = near + 1 <= pt.wend && !outside(near + 1);
     const int f = group_search<64>(ok1 ? near + 1 : 0, ok1 ? pt.wend + 1 : 1, lane, [&](int m) { return !outside(m); });
     const int nr = ok1 ? f - 1 - near : 0;
-    // one trip: site i of this lane (valid: inside the smallest alpha's walk)
+    // one trip: site i of this lane (valid: inside the smallest alpha's walk, and the clip)
     auto trip = [&](int i, bool valid) {
       uint2 s = make_uint2(usweep, 0u);
       double lt = 0.0;
@@ -2689,145 +2725,37 @@ __device__ __forceinline__ void surface_block(SurfSmem& S, const Params& P, int 
         len[b] += (uint32_t)lim;
       }
     };
-    for (int j0 = 0; j0 <= nl; j0 += 64) trip(near - (j0 + lane), j0 + lane <= nl);
-    for (int j0 = 1; j0 <= nr; j0 += 64) trip(near + j0 + lane, j0 + lane <= nr);
-  }
-#pragma unroll
-  for (int b = 0; b < SURF_B; b++)
-    if (lane == b && b < nb) { S.sm[pi][k0 + b] = acc[b]; S.len[pi][k0 + b] = len[b]; }
-}
-
-__global__ void __launch_bounds__(64 * SURF_WAVES)
-surface_kernel(Params P, const SurfChunk* __restrict__ chunks, const double* __restrict__ la_all, int n_la,
-               double* __restrict__ sm_out) {
-  __shared__ SurfSmem S;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int k = (int)blockIdx.x;
-  if (k >= P.n_cells) return;
-  const SurfChunk c = chunks[k];
-  for (int i = wave; i < c.count; i += SURF_WAVES) init_point_wave(S.pt[i], c.chr, c.start_pos + i * c.step, P, lane);
-  __syncthreads();
-  const double* __restrict__ lap = la_all + (size_t)c.run * (size_t)n_la;
-  const int nblk = (n_la + SURF_B - 1) / SURF_B;
-  for (int it = wave; it < c.count * nblk; it += SURF_WAVES) {
-    const int pi = it / nblk, k0 = (it - pi * nblk) * SURF_B;
-    surface_block(S, P, pi, lap, k0, min(SURF_B, n_la - k0), lane);
-  }
-  __syncthreads();
-  for (int t = tid; t < c.count * n_la; t += 64 * SURF_WAVES) {  // consecutive lanes, consecutive doubles
-    const int pi = t / n_la;
-    sm_out[(size_t)c.out0 * (size_t)n_la + (size_t)t] = S.sm[pi][t - pi * n_la];
-  }
-  if (tid < c.count) {  // one store per point (P.out is host memory: no read-modify-write)
-    Pt& pt = S.pt[tid];
-    double best = -1.7976931348623157e308, bla = LOG_AD_MAX;
-    unsigned long long terms = 0;
-    for (int j = 0; j < n_la; j++) {
-      const double v = S.sm[tid][j];
-      if (v > best) { best = v; bla = lap[j]; }
-      terms += S.len[tid][j];
+    if constexpr (CLIP) {
+      // (wstart <= clo <= chi <= wend: every bound below is a site of the window)
+      const int l0 = min(near, chi), l1 = max(near - nl, clo);      // left part, downwards: l0 .. l1
+      const int r0 = max(near + 1, clo), r1 = min(near + nr, chi);  // right part, upwards: r0 .. r1
+      for (int j0 = 0; j0 <= l0 - l1; j0 += 64) trip(l0 - (j0 + lane), j0 + lane <= l0 - l1);
+      for (int j0 = 0; j0 <= r1 - r0; j0 += 64) trip(r0 + j0 + lane, j0 + lane <= r1 - r0);
+    } else {
+      for (int j0 = 0; j0 <= nl; j0 += 64) trip(near - (j0 + lane), j0 + lane <= nl);
+      for (int j0 = 1; j0 <= nr; j0 += 64) trip(near + j0 + lane, j0 + lane <= nr);
     }
-    pt.la = bla; pt.sm = best; pt.clr = 2.0 * (best - pt.N);
-    fsclg_point_t o;
-    write_point(o, pt);
-    o.cost = (uint32_t)min(terms >> 10, 0xFFFFFFFFull);  // the position's terms / 1024
-    P.out[c.out0 + tid] = o;
-    atomicAdd(&P.stats[0], terms);                                   // the device counters, as any launch:
-    atomicAdd(&P.stats[1], (unsigned long long)pt.n_snps);           // terms, null-sum elements, walks
-    atomicAdd(&P.stats[2], (unsigned long long)n_la);
-  }
-}
-
-// ------------------------------------------------------------ conditional sweep scan
-// The surface with every walk cut to the sites the candidate sweep owns (fsclg_cond_submit): per position
-// a global site-index interval [lo, hi] comes with the runs (lo > hi: empty), and a walk's value is the
-// null sum plus, in walk order, the terms of its sites inside the interval.  surface_kernel's
-// decomposition and trip, as a symbol of its own: the clip is intersected with the window when the chunk
-// is set up, and with the walk per item.  The walk bounds nl, nr are those of the block's smallest alpha
-// on the unclipped walk; the left part then runs from min(near, hi) down to max(near - nl, lo) -- the
-// nearest SNP is its first site iff lo <= near <= hi -- and the right part from max(near + 1, lo) up to
-// min(near + nr, hi).  A clipped part is a contiguous piece of the unclipped one, so |d| stays
-// nondecreasing along it once the nearest SNP is inside the alpha's cut (surface_kernel's argument: the
-// sites the de-collision stepped over lie nearer than the nearest SNP), the lanes inside are still a
-// prefix of the trip, and exact_chunk_add folds them in walk order.  An alpha whose nearest SNP is past
-// its own cut has an empty walk, whether or not the clip holds the nearest SNP.  With the clip covering
-// the window every trip is surface_kernel's, site for site.  Results, point and counters as there.
-struct CondSmem {
-  SurfSmem s;
-  int lo[SURF_CH], hi[SURF_CH];  // the clip of each position, cut to its window
-};
-
-__device__ __forceinline__ void cond_block(CondSmem& C, const Params& P, int pi, const double* __restrict__ lap,
-                                           int k0, int nb, int lane) {
-  SurfSmem& S = C.s;
-  const Pt& pt = S.pt[pi];
-  const int near = pt.nearest, clo = C.lo[pi], chi = C.hi[pi];
-  const uint32_t usweep = (uint32_t)pt.sweep ^ POS_BIAS;
-  double la[SURF_B], acc[SURF_B];
-  uint32_t len[SURF_B];
-  bool alive[SURF_B];
-  const double lt0 = logt_dev(absdist(P.pr[phys(near)].x, usweep), P.logt3);
-#pragma unroll
-  for (int b = 0; b < SURF_B; b++) {
-    la[b] = lap[k0 + min(b, nb - 1)];
-    acc[b] = pt.N;
-    len[b] = 0;
-    alive[b] = b < nb && !(lt0 + la[b] > LOG_AD_MAX);  // the nearest SNP outside: an empty walk
-  }
-  if (alive[0] && clo <= chi) {
-    const double la0 = la[0];
-    auto outside = [&](int i) { return logt_dev(absdist(P.pr[phys(i)].x, usweep), P.logt3) + la0 > LOG_AD_MAX; };
-    const int e = group_search<64>(pt.wstart - 1, near, lane, [&](int m) { return outside(m); });
-    const int nl = near - e;
-    const bool ok1 = near + 1 <= pt.wend && !outside(near + 1);
-    const int f = group_search<64>(ok1 ? near + 1 : 0, ok1 ? pt.wend + 1 : 1, lane, [&](int m) { return !outside(m); });
-    const int nr = ok1 ? f - 1 - near : 0;
-    // (wstart <= clo <= chi <= wend: every bound below is a site of the window)
-    const int l0 = min(near, chi), l1 = max(near - nl, clo);      // left part, downwards: l0 .. l1
-    const int r0 = max(near + 1, clo), r1 = min(near + nr, chi);  // right part, upwards: r0 .. r1
-    auto trip = [&](int i, bool valid) {
-      uint2 s = make_uint2(usweep, 0u);
-      double lt = 0.0;
-      if (valid) {
-        s = P.pr[phys(i)];
-        lt = logt_dev(absdist(s.x, usweep), P.logt3);
-      }
-#pragma unroll
-      for (int b = 0; b < SURF_B; b++) {
-        if (!alive[b]) continue;  // (wave-uniform)
-        const double x = lt + la[b];
-        const bool in = valid && !(x > LOG_AD_MAX);
-        const unsigned long long m = __ballot(in);
-        if (m == 0ull) continue;
-        double t = 0.0;
-        if (in) t = surf_term(x, s.y, S, P);
-        const int lim = __popcll(m);  // the lanes inside are the first lim
-        acc[b] = exact_chunk_add(acc[b], t, lim);
-        len[b] += (uint32_t)lim;
-      }
-    };
-    for (int j0 = 0; j0 <= l0 - l1; j0 += 64) trip(l0 - (j0 + lane), j0 + lane <= l0 - l1);
-    for (int j0 = 0; j0 <= r1 - r0; j0 += 64) trip(r0 + j0 + lane, j0 + lane <= r1 - r0);
   }
 #pragma unroll
   for (int b = 0; b < SURF_B; b++)
     if (lane == b && b < nb) { S.sm[pi][k0 + b] = acc[b]; S.len[pi][k0 + b] = len[b]; }
 }
 
-__global__ void __launch_bounds__(64 * SURF_WAVES)
-cond_kernel(Params P, const SurfChunk* __restrict__ chunks, const double* __restrict__ la_all, int n_la,
-            const int32_t* __restrict__ clip, double* __restrict__ sm_out) {
-  __shared__ CondSmem C;
-  SurfSmem& S = C.s;
+// (clip: the positions' (lo, hi) pairs under CLIP, not read otherwise; the wrappers' arguments are __restrict__)
+template <bool CLIP, class SM>
+__device__ __forceinline__ void surface_body(SM& S, const Params& P, const SurfChunk* chunks, const double* la_all,
+                                             int n_la, const int32_t* clip, double* sm_out) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int k = (int)blockIdx.x;
   if (k >= P.n_cells) return;
   const SurfChunk c = chunks[k];
   for (int i = wave; i < c.count; i += SURF_WAVES) {
     init_point_wave(S.pt[i], c.chr, c.start_pos + i * c.step, P, lane);
-    if (lane == 0) {  // (the lane that wrote the point)
-      C.lo[i] = max(clip[2 * (size_t)(c.out0 + i)], S.pt[i].wstart);
-      C.hi[i] = min(clip[2 * (size_t)(c.out0 + i) + 1], S.pt[i].wend);
+    if constexpr (CLIP) {
+      if (lane == 0) {  // (the lane that wrote the point)
+        S.lo[i] = max(clip[2 * (size_t)(c.out0 + i)], S.pt[i].wstart);
+        S.hi[i] = min(clip[2 * (size_t)(c.out0 + i) + 1], S.pt[i].wend);
+      }
     }
   }
   __syncthreads();
@@ -2835,14 +2763,14 @@ cond_kernel(Params P, const SurfChunk* __restrict__ chunks, const double* __rest
   const int nblk = (n_la + SURF_B - 1) / SURF_B;
   for (int it = wave; it < c.count * nblk; it += SURF_WAVES) {
     const int pi = it / nblk, k0 = (it - pi * nblk) * SURF_B;
-    cond_block(C, P, pi, lap, k0, min(SURF_B, n_la - k0), lane);
+    surface_block<CLIP>(S, P, pi, lap, k0, min(SURF_B, n_la - k0), lane);
   }
   __syncthreads();
   for (int t = tid; t < c.count * n_la; t += 64 * SURF_WAVES) {  // consecutive lanes, consecutive doubles
     const int pi = t / n_la;
     sm_out[(size_t)c.out0 * (size_t)n_la + (size_t)t] = S.sm[pi][t - pi * n_la];
   }
-  if (tid < c.count) {  // one store per point (P.out is host memory: no read-modify-write)
+  if (tid < c.count) {
     Pt& pt = S.pt[tid];
     double best = -1.7976931348623157e308, bla = LOG_AD_MAX;
     unsigned long long terms = 0;
@@ -2852,14 +2780,22 @@ cond_kernel(Params P, const SurfChunk* __restrict__ chunks, const double* __rest
       terms += S.len[tid][j];
     }
     pt.la = bla; pt.sm = best; pt.clr = 2.0 * (best - pt.N);
-    fsclg_point_t o;
-    write_point(o, pt);
-    o.cost = (uint32_t)min(terms >> 10, 0xFFFFFFFFull);  // the position's terms / 1024
-    P.out[c.out0 + tid] = o;
-    atomicAdd(&P.stats[0], terms);                                   // the device counters, as any launch:
-    atomicAdd(&P.stats[1], (unsigned long long)pt.n_snps);           // terms, null-sum elements, walks
-    atomicAdd(&P.stats[2], (unsigned long long)n_la);
+    store_list_point(P, c.out0 + tid, pt, terms, n_la);
   }
+}
+
+__global__ void __launch_bounds__(64 * SURF_WAVES)
+surface_kernel(Params P, const SurfChunk* __restrict__ chunks, const double* __restrict__ la_all, int n_la,
+               double* __restrict__ sm_out) {
+  __shared__ SurfSmem S;
+  surface_body<false>(S, P, chunks, la_all, n_la, nullptr, sm_out);
+}
+
+__global__ void __launch_bounds__(64 * SURF_WAVES)
+cond_kernel(Params P, const SurfChunk* __restrict__ chunks, const double* __restrict__ la_all, int n_la,
+            const int32_t* __restrict__ clip, double* __restrict__ sm_out) {
+  __shared__ CondSmem S;
+  surface_body<true>(S, P, chunks, la_all, n_la, clip, sm_out);
 }
 
 // ------------------------------------------------------------ block sums of the surface
@@ -2989,7 +2925,7 @@ blocks_kernel(Params P, const BlkChunk* __restrict__ chunks, const double* __res
     S.v[i][lane] = v;
     const int wl = S.lo[i][lane], wh = S.hi[i][lane];
     const unsigned long long terms = (unsigned long long)wave_sum64(wl <= wh ? (long long)(wh - wl + 1) : 0ll);
-    if (lane == 0) {  // one store per point (P.out is host memory: no read-modify-write)
+    if (lane == 0) {
       double best = -1.7976931348623157e308, bla = LOG_AD_MAX, bv = 0.0;
       bool have = false;
       const double* __restrict__ lap = la_all + (size_t)c.run * (size_t)n_la;
@@ -2998,13 +2934,7 @@ blocks_kernel(Params P, const BlkChunk* __restrict__ chunks, const double* __res
         if (w > best) { best = w; bla = lap[k]; bv = S.v[i][k]; have = true; }
       }
       pt.la = bla; pt.sm = best; pt.clr = have ? 2.0 * bv : 2.0 * (best - pt.N);
-      fsclg_point_t o;
-      write_point(o, pt);
-      o.cost = (uint32_t)min(terms >> 10, 0xFFFFFFFFull);  // the position's terms / 1024
-      P.out[c.out0 + i] = o;
-      atomicAdd(&P.stats[0], terms);                                   // the device counters, as any launch:
-      atomicAdd(&P.stats[1], (unsigned long long)pt.n_snps);           // terms, null-sum elements, walks
-      atomicAdd(&P.stats[2], (unsigned long long)n_la);
+      store_list_point(P, c.out0 + i, pt, terms, n_la);
     }
   }
 }
@@ -5730,6 +5660,15 @@ static int validate_runs(const fsclg_ctx* c, const fsclg_run_t* runs, int n_runs
   return FSCLG_OK;
 }
 
+// one covering cell per non-empty run: the cells whose window null sums the run kernels need
+static std::vector<fsclg_cell_t> run_cover(const fsclg_run_t* runs, int n_runs) {
+  std::vector<fsclg_cell_t> cover;
+  for (int i = 0; i < n_runs; i++)
+    if (runs[i].count > 0)
+      cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos, runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
+  return cover;
+}
+
 // the window null sums of every window the covering cells touch, for the slot's rows (a slot another
 // batch already runs on: only what is still missing)
 static int cover_windows(fsclg_ctx* c, Batch& B, int slot, const std::vector<fsclg_cell_t>& cover, int eval_range) {
@@ -5768,11 +5707,7 @@ static int launch_run_kernel(fsclg_ctx* c, Batch& B, RunKernel k, const Params& 
 static int launch_runs(fsclg_ctx* c, Batch& B, int slot, const fsclg_run_t* runs, int n_runs, int eval_range, int CH,
                        int nchunk, RunKernel k, bool by_chunk) {
   int r;
-  std::vector<fsclg_cell_t> cover;
-  for (int i = 0; i < n_runs; i++)
-    if (runs[i].count > 0)
-      cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos, runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
-  if ((r = cover_windows(c, B, slot, cover, eval_range))) return r;
+  if ((r = cover_windows(c, B, slot, run_cover(runs, n_runs), eval_range))) return r;
   if ((r = ensure_pinned(&B.p_cmchunks, &B.cmchunk_cap, nchunk))) return r;
   int nc = 0, o = 0;
   for (int i = 0; i < n_runs; i++)
@@ -5982,6 +5917,20 @@ unsigned long long fsclg_curve_forced(fsclg_ctx* c) {
 }
 
 // ------------------------------------------------------------ likelihood surface (host side)
+// n_runs ascending lists of n_la log alphas each: interval_of needs log(alpha d) >= LOG_AD_MIN; above
+// LOG_AD_MAX every walk is empty
+static int check_alpha_lists(const double* la, int n_runs, int n_la) {
+  for (long long i = 0; i < (long long)n_runs * n_la; i++) {
+    if (!(la[i] >= LOG_AD_MIN && la[i] <= LOG_AD_MAX)) return set_err(FSCLG_E_ARG, "log alpha outside [LOG_AD_MIN, LOG_AD_MAX]");
+    if (i % n_la && !(la[i] > la[i - 1])) return set_err(FSCLG_E_ARG, "alpha list not ascending");
+  }
+  return FSCLG_OK;
+}
+
+// positions per chunk of a list kernel, at most CH: as many as give a workgroup of `waves` waves about two
+// items per wave, a position holding n items (the result does not depend on it)
+static int list_chunk(int CH, int waves, int n) { return std::max(1, std::min(CH, (2 * waves + n - 1) / n)); }
+
 // The runs' position-by-alpha surfaces on the rows a slot holds: fsclg_cellmax_submit's checks, slot and
 // window null sums (one covering cell per run); surface_kernel stores n_la values and one point per
 // position.  A chunk holds as many positions as give its workgroup about two items per wave (the result
@@ -5999,15 +5948,11 @@ static int surface_like_submit(fsclg_ctx* c, int batch, int slot, const fsclg_ru
   if (!c->d_pr0 || !c->d_coef) return set_err(FSCLG_E_STATE, "tables/snps not set");
   Batch& B = c->batch[batch];
   if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
-  for (long long i = 0; i < (long long)n_runs * n_la; i++) {
-    // interval_of needs log(alpha d) >= LOG_AD_MIN; above LOG_AD_MAX every walk is empty
-    if (!(la[i] >= LOG_AD_MIN && la[i] <= LOG_AD_MAX)) return set_err(FSCLG_E_ARG, "log alpha outside [LOG_AD_MIN, LOG_AD_MAX]");
-    if (i % n_la && !(la[i] > la[i - 1])) return set_err(FSCLG_E_ARG, "alpha list not ascending");
-  }
-  const int nblk = (n_la + SURF_B - 1) / SURF_B;
-  const int CH = std::max(1, std::min(SURF_CH, (2 * SURF_WAVES + nblk - 1) / nblk));
-  long long total, nchunk;
   int r;
+  if ((r = check_alpha_lists(la, n_runs, n_la))) return r;
+  const int nblk = (n_la + SURF_B - 1) / SURF_B;
+  const int CH = list_chunk(SURF_CH, SURF_WAVES, nblk);
+  long long total, nchunk;
   if ((r = validate_runs(c, runs, n_runs, eval_range, CH, &total, &nchunk))) return r;
   if (total * n_la > 0x7FFFFFFFll / (long long)sizeof(double) || total > 0x7FFFFFFFll / (long long)sizeof(fsclg_point_t))
     return set_err(FSCLG_E_ARG, "too many surface cells");
@@ -6017,11 +5962,7 @@ static int surface_like_submit(fsclg_ctx* c, int batch, int slot, const fsclg_ru
   if (kind == BK_COND) B.cd_ms = 0.0;
   else B.sf_ms = 0.0;
   if (total > 0) {
-    std::vector<fsclg_cell_t> cover;
-    for (int i = 0; i < n_runs; i++)
-      if (runs[i].count > 0)
-        cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos, runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
-    if ((r = cover_windows(c, B, slot, cover, eval_range))) return r;
+    if ((r = cover_windows(c, B, slot, run_cover(runs, n_runs), eval_range))) return r;
     if ((r = ensure_io(B, (int)total))) return r;
     if ((r = ensure_pinned(&B.p_sfchunks, &B.sfchunk_cap, (int)nchunk))) return r;
     if ((r = ensure_pinned(&B.p_sfla, &B.sfla_cap, n_runs * n_la))) return r;
@@ -6119,10 +6060,8 @@ int fsclg_blocks_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* ru
   if (!c->d_pr0 || !c->d_coef) return set_err(FSCLG_E_STATE, "tables/snps not set");
   Batch& B = c->batch[batch];
   if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
-  for (long long i = 0; i < (long long)n_runs * n_la; i++) {
-    if (!(la[i] >= LOG_AD_MIN && la[i] <= LOG_AD_MAX)) return set_err(FSCLG_E_ARG, "log alpha outside [LOG_AD_MIN, LOG_AD_MAX]");
-    if (i % n_la && !(la[i] > la[i - 1])) return set_err(FSCLG_E_ARG, "alpha list not ascending");
-  }
+  int r;
+  if ((r = check_alpha_lists(la, n_runs, n_la))) return r;
   long long nbf = 0, nbmax = 1;
   for (int i = 0; i < n_runs; i++) {
     if (blk[i].block_bp < 1) return set_err(FSCLG_E_ARG, "block_bp < 1");
@@ -6132,7 +6071,6 @@ int fsclg_blocks_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* ru
     nbmax = std::max(nbmax, (long long)blk[i].nb);
   }
   long long total, nchunk;
-  int r;
   if ((r = validate_runs(c, runs, n_runs, eval_range, 1, &total, &nchunk))) return r;
   long long items = 0;
   for (int i = 0; i < n_runs; i++) items += (long long)runs[i].count * blk[i].nb;
@@ -6143,16 +6081,13 @@ int fsclg_blocks_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* ru
   B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
   B.eval_range = eval_range; B.bp_resl = 0; B.bk_ms = 0.0; B.bk_n = (int)total; B.bk_cells = (size_t)(items * n_la);
   if (total > 0) {
-    std::vector<fsclg_cell_t> cover;
     nchunk = 0;
     for (int i = 0; i < n_runs; i++) {
-      if (runs[i].count <= 0) continue;
-      cover.push_back(fsclg_cell_t{runs[i].chr, runs[i].start_pos, runs[i].start_pos + (runs[i].count - 1) * runs[i].step, 0});
-      const int CH = std::max(1, std::min(BLK_CH, (2 * BLK_WAVES + blk[i].nb - 1) / blk[i].nb));
-      nchunk += (runs[i].count + CH - 1) / CH;
+      const int CH = list_chunk(BLK_CH, BLK_WAVES, blk[i].nb);
+      nchunk += (runs[i].count + CH - 1) / CH;  // (count >= 0: validate_runs)
     }
     B.nu = (int)nchunk;
-    if ((r = cover_windows(c, B, slot, cover, eval_range))) return r;
+    if ((r = cover_windows(c, B, slot, run_cover(runs, n_runs), eval_range))) return r;
     if ((r = ensure_io(B, (int)total))) return r;
     if ((r = ensure_pinned(&B.p_bkchunks, &B.bkchunk_cap, (int)nchunk))) return r;
     if ((r = ensure_pinned(&B.p_bkla, &B.bkla_cap, n_runs * n_la))) return r;
@@ -6172,7 +6107,7 @@ int fsclg_blocks_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* ru
         const long long lim = ((long long)blk[i].b0 + j) * (long long)blk[i].block_bp;
         bf[j] = a + (int)(std::lower_bound(pos, pos + n, lim, [](int32_t x, long long v) { return (long long)x < v; }) - pos);
       }
-      const int CH = std::max(1, std::min(BLK_CH, (2 * BLK_WAVES + nb - 1) / nb));
+      const int CH = list_chunk(BLK_CH, BLK_WAVES, nb);
       for (int j = 0; j < runs[i].count; j += CH) {
         const int cnt = std::min(CH, runs[i].count - j);
         B.p_bkchunks[nc++] = BlkChunk{runs[i].chr, runs[i].start_pos + j * runs[i].step, runs[i].step, cnt, o, i, nb, bfo, item0, 0ull};

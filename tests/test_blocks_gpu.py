@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import blocks_ref as br
+import cond_ref as cr
 import fscl_amd
 import walk_ref as wr
 from fscl_amd import synth
@@ -280,6 +281,37 @@ def test_clamp_absorbs_both_sides(shim):
         if n > 600:
             assert ocnt[k][0][0, 0] > 100 and ocnt[k][0][-1, 0] > 100, k
     assert not bad, f"{len(bad)} mismatches:\n" + "\n".join(bad[:12])
+
+
+def test_device_counters(shim):
+    """One position per window of walk_ref's geometry with 5 alphas, the clamp test's blocks: the launch adds the
+    walks' terms (the edge blocks absorb what lies beyond them), the sites of the points' windows (the null-sum
+    elements) and 5 walks per position to the device counters."""
+    c = wr.cases()["edge-nonneg"]
+    T, N = c.tables, wr.N_TIE
+    g, _ = wr.geometry()
+    cs, cn = case_chromosomes()
+    runs = [(k, q.sweep, 1, 1) for k, q in enumerate(g)]
+    la, blk = grid(5), []
+    terms = null = 0
+    for k, q in enumerate(g):
+        near, sweep, ws, we = cr.init_point(T.pos, cs[k], cn[k], q.sweep, CASE_ER)
+        null += we - ws + 1
+        for a in la:
+            nl, nr = wr.walk_terms(T, wr.Point(near, sweep, ws, we, N), a)[1]
+            terms += 0 if nl < 0 else 1 + nl + nr
+        lo, hi = int(T.pos[cs[k]]), int(T.pos[cs[k] + cn[k] - 1])
+        third = max((hi - lo) // 3, 1)
+        blk.append((100, (lo + third) // 100, max(third // 100, 1)))
+
+    @device_guard
+    def go():
+        shim.upload(T, cs, cn)
+        c0 = shim.counters()
+        shim.blocks(runs, [la] * len(runs), blk, CASE_ER, N, len(cs))
+        return c0, shim.counters()
+    c0, c1 = go()
+    assert terms > 0 and tuple(b - a for a, b in zip(c0, c1)) == (terms, null, 5 * len(runs))
 
 
 # ------------------------------------------------------------------ 4. exact terms

@@ -217,6 +217,34 @@ def test_clips(shim, name, n_la):
             assert all(wr.same(float(v), N) for v in sm[i]), (k, i)
 
 
+def test_device_counters(shim):
+    """One position per window of walk_ref's geometry with 5 alphas, clipped to 70 sites on either side of the nearest
+    SNP: the launch adds the clipped walks' terms, the sites of the points' windows (the null-sum elements, which
+    no clip cuts) and 5 walks per position to the device counters."""
+    c = wr.cases()["edge-nonneg"]
+    T, N = c.tables, wr.N_TIE
+    g, _ = wr.geometry()
+    cs, cn = case_chromosomes()
+    runs = [(k, q.sweep, 1, 1) for k, q in enumerate(g)]
+    la = grid(5)
+    geom = [cr.init_point(T.pos, cs[k], cn[k], q.sweep, CASE_ER) for k, q in enumerate(g)]
+    clips = [(gm[0] - 70, gm[0] + 70) for gm in geom]
+    walks = [[wr.walk_terms(T, wr.Point(gm[0], gm[1], gm[2], gm[3], N), a) for a in la] for gm in geom]
+    want = expect_rows(T, geom, N, la, clips, walks)
+    terms, whole = sum(w[2] for w in want), sum(len(w[0]) for wk in walks for w in wk)
+    null = sum(gm[3] - gm[2] + 1 for gm in geom)
+
+    @device_guard
+    def go():
+        shim.upload(T, cs, cn)
+        c0 = shim.counters()
+        shim.run(runs, [la] * len(runs), clips, CASE_ER, N, len(cs))
+        return c0, shim.counters()
+    c0, c1 = go()
+    assert 0 < terms < whole, "the clips cut no walk"
+    assert tuple(b - a for a, b in zip(c0, c1)) == (terms, null, 5 * len(runs))
+
+
 def test_nan_rows_stay_in_their_clips(shim):
     """walk_ref's table with a NaN row far from the nearest SNP: a clip that leaves the site out gives finite values."""
     c = wr.cases()["row-nan"]

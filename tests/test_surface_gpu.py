@@ -15,6 +15,7 @@ import sys
 import numpy as np
 import pytest
 
+import cond_ref as cr
 import fscl_amd
 import walk_ref as wr
 from fscl_amd import synth
@@ -254,6 +255,34 @@ def test_exact_sums_n_list(shim):
         assert all(wr.same(float(q["null_logl"]), N) for q in pts)
         check_cells(pts, sm, c.tables, la, f"N={N!r}", bad)
     assert not bad, f"{len(bad)} mismatches:\n" + "\n".join(bad[:12])
+
+
+# ------------------------------------------------------------------ 4. the device counters
+def test_device_counters(shim):
+    """One position per window of walk_ref's geometry with 5 alphas: the launch adds the walks' terms, the sites of
+    the points' windows (the null-sum elements) and 5 walks per position to the device counters."""
+    c = wr.cases()["edge-nonneg"]
+    T, N = c.tables, wr.N_TIE
+    g, _ = wr.geometry()
+    cs, cn = case_chromosomes()
+    runs = [(k, q.sweep, 1, 1) for k, q in enumerate(g)]
+    la = grid(5)
+    terms = null = 0
+    for k, q in enumerate(g):
+        near, sweep, ws, we = cr.init_point(T.pos, cs[k], cn[k], q.sweep, CASE_ER)
+        null += we - ws + 1
+        for a in la:
+            nl, nr = wr.walk_terms(T, wr.Point(near, sweep, ws, we, N), a)[1]
+            terms += 0 if nl < 0 else 1 + nl + nr
+
+    @device_guard
+    def go():
+        shim.upload(T, cs, cn)
+        c0 = shim.counters()
+        shim.surface(runs, [la] * len(runs), CASE_ER, N, len(cs))
+        return c0, shim.counters()
+    c0, c1 = go()
+    assert terms > 0 and tuple(b - a for a, b in zip(c0, c1)) == (terms, null, 5 * len(runs))
 
 
 # ------------------------------------------------------------------ helpers of the whole-library tests

@@ -292,6 +292,12 @@ class Shim:
         self._ok(self.L.fsclg_get_stats(self.ctx, C.byref(st)), "fsclg_get_stats")
         return {k: int(getattr(st, k)) for k in ("n_unsafe", "n_slow", "n_ties", "n_walks", "n_maxalpha")}
 
+    def counters(self) -> tuple:
+        """The cumulative device counters every launch adds to: (terms, null-sum elements, walks)."""
+        st = StatsT()
+        self._ok(self.L.fsclg_get_stats(self.ctx, C.byref(st)), "fsclg_get_stats")
+        return int(st.n_terms), int(st.n_null), int(st.n_walks)
+
     def reset_stats(self):
         self._ok(self.L.fsclg_reset_stats(self.ctx), "fsclg_reset_stats")
 

@@ -3770,42 +3770,80 @@ static double g_hprof[12];
 static double hnow() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static bool hprof_on() { static const bool on = getenv("FSCLG_HOST_PROFILE") != nullptr; return on; }
 
+static thread_local char g_err[512];
+static int set_err(int code, const char* what, hipError_t e = hipSuccess) {
+  if (e != hipSuccess) snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
+  else snprintf(g_err, sizeof g_err, "%s", what);
+  return code;
+}
+#define HIPCHK(x, what) do { hipError_t e_ = (x); if (e_ != hipSuccess) return set_err(FSCLG_E_HIP, what, e_); } while (0)
+
+// A buffer of the shim, pointer and capacity together.  PINNED: pinned host memory the kernels read or
+// write directly (coherent: no cache flush needed between a kernel's stores and the host's reads after
+// its completion event); DEVICE: device memory.  It grows, never shrinks, and is freed with its owner
+// (a Slot, a Batch or the context): whoever adds a buffer declares it and calls ensure(), nothing else
+enum Where { PINNED, DEVICE };
+static constexpr unsigned HOSTMEM = hipHostMallocCoherent | hipHostMallocMapped;
+template <typename T, Where W>
+struct Buf {
+  T* p = nullptr;
+  size_t cap = 0;  // elements
+  Buf() = default;
+  Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }  // (fsclg_slot_swap; no copies)
+  Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+  ~Buf() { release(); }
+  operator T*() const { return p; }
+  void release() {
+    if (p) (void)(W == PINNED ? hipHostFree(p) : hipFree(p));
+    p = nullptr; cap = 0;
+  }
+  // room for n elements (the contents are not kept); a first allocation holds 1024 at least
+  int ensure(size_t n, const char* what = W == PINNED ? "hipHostMalloc" : "hipMalloc") {
+    if (n <= cap) return FSCLG_OK;
+    release();
+    const size_t k = n < 1024 ? 1024 : n;
+    T* q = nullptr;
+    HIPCHK(W == PINNED ? hipHostMalloc((void**)&q, sizeof(T) * k, HOSTMEM) : hipMalloc((void**)&q, sizeof(T) * k), what);
+    p = q; cap = k;
+    return FSCLG_OK;
+  }
+};
 
 // one trial's rows on the device (fsclg_slot_set_rows): the (position, row) array, the
-// whole-chromosome null sums and the per-window null sums of those rows
+// whole-chromosome null sums and the per-window null sums of those rows, with the slot's staging
+// buffers and chunk tables (every buffer a Buf: fsclg_close and fsclg_slot_swap name none of them)
 struct Slot {
-  uint2* d_pr = nullptr;          // (biased position, device row), n_snps + PAD
-  double* d_chr_null = nullptr;
-  double* d_win_null = nullptr;   // [n_snps], valid for (win_er, rows) while win_valid
+  Buf<uint2, DEVICE> d_pr;        // (biased position, device row), n_snps + PAD
+  Buf<double, DEVICE> d_chr_null;
+  Buf<double, DEVICE> d_win_null; // [n_snps], valid for (win_er, rows) while win_valid
   int win_er = -1;
   bool win_valid = false;         // win_null holds every window start, or (win_part) the ranges wdone
   bool win_part = false;
   std::vector<int2> wdone;        // window starts [x, y) summed for the slot's rows, sorted, disjoint
-  int2* p_wtasks = nullptr;       // pinned: the tasks of the slot's last partial window launch
-  int wtask_cap = 0;
-  uint32_t* h_rows = nullptr;     // pinned (coherent) staging of one trial's rows, read by scatter_rows_kernel
-  double* h_null = nullptr;       // pinned (coherent) whole-chromosome null sums, n_chr
-  int rows_cap = 0, null_cap = 0;
+  Buf<int2, PINNED> p_wtasks;     // the tasks of the slot's last partial window launch
+  Buf<uint32_t, PINNED> h_rows;   // staging of one trial's rows, read by scatter_rows_kernel
+  Buf<double, PINNED> h_null;     // whole-chromosome null sums, n_chr
   hipEvent_t ready = nullptr;     // recorded on the upload stream after the slot's last upload
   hipEvent_t wev0 = nullptr, wev1 = nullptr;  // bracket the slot's last window null-sum launch
   bool wpend = false;             // its time not yet added to window_ms (read without blocking later)
   int users = 0;                  // batches submitted on this slot and not yet waited for
-  double2* d_ctab = nullptr;      // chunk_table_kernel's table for the slot's rows (window_chunk_kernel)
-  double2* d_ctree = nullptr;     // chunk_tree_kernel's block maps over it
-  size_t ctree_cap = 0;
+  Buf<double2, DEVICE> d_ctab;    // chunk_table_kernel's table for the slot's rows (window_chunk_kernel)
+  Buf<double2, DEVICE> d_ctree;   // chunk_tree_kernel's block maps over it
   CTree ctree = {};
-  size_t ctab_cap = 0;            // entries
   bool ctab_valid = false;        // built for the slot's rows with (ctab_emin, ctab_ne)
   int ctab_emin = 0, ctab_ne = 0;
 };
 
 // what a batch holds between a submit and its wait
 enum BatchKind { BK_NONE, BK_SEARCH, BK_PROFILE, BK_CELLMAX, BK_CURVE, BK_SITES, BK_SAMPLE, BK_TAIL, BK_SURFACE,
-                 BK_BLOCKS, BK_COND };
+                 BK_BLOCKS, BK_COND, BK_COUNT };
 
-// one call of any kind in flight (a submit / wait pair: search, profile, cell maxima, curves, site
-// terms, sample, tail fit): its stream and events, the device and pinned host buffers of each kind,
-// and a search's host-side dedup / ordering of its cells
+// One call of any kind in flight (a submit / wait pair: search, profile, cell maxima, curves, site
+// terms, sample, tail fit, surface, block sums, conditional scan): its stream and events, the state
+// every kind shares (what it holds, on which slot, how many results, each kind's last kernel time),
+// a search's host-side dedup / ordering of its cells, and the buffers of each kind.  A kind adds its
+// buffers here and nothing else: the protocol is batch_reset / launch_bracket / batch_hold in its
+// submit and batch_finish in its wait (below)
 struct Batch {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;  // bracket the kernels
@@ -3813,15 +3851,11 @@ struct Batch {
   // the kernels read their inputs from and write their outputs to pinned coherent host memory
   // (a few bytes per workgroup): no copy-engine transfers on the batch streams, which would
   // order one stream's kernels behind another stream's copies and serialise the trials
-  fsclg_cell_t* p_cells = nullptr;
-  fsclg_point_t* p_out = nullptr;
-  int cap = 0;
-  fsclg_point_t* d_ept = nullptr;   // endpoint results: written by one launch, read by the next
-  int2* p_epos = nullptr;
-  int2* p_cell_ep = nullptr;
-  int ept_cap = 0, pep_cap = 0, pcep_cap = 0;
-  unsigned long long* p_ctrace = nullptr;  // FSCLG_CELL_TRACE=<file>: per-cell timing appended per launch
-  int ctrace_cap = 0;
+  Buf<fsclg_cell_t, PINNED> p_cells;
+  Buf<fsclg_point_t, PINNED> p_out;
+  Buf<fsclg_point_t, DEVICE> d_ept;  // endpoint results: written by one launch, read by the next
+  Buf<int2, PINNED> p_epos, p_cell_ep;
+  Buf<unsigned long long, PINNED> p_ctrace;  // FSCLG_CELL_TRACE=<file>: per-cell timing appended per launch
   int trace_n = 0;                  // cells of the traced launch (the event area follows them)
   unsigned long long* ivhist = nullptr;    // this launch measures the interval histogram (FSCLG_IVHIST)
   bool traced = false;
@@ -3835,76 +3869,52 @@ struct Batch {
   int split_max = 1;                // fsclg_set_batch_split
   int split = 1;                    // members per cell of the current launch
   int eval_range = 0, bp_resl = 0;  // of the submitted launch (a split launch re-run unsplit)
-  char* d_xacc = nullptr;           // split cells' accumulators and arrival counters
-  unsigned int* d_xcnt = nullptr;
-  size_t xacc_cap = 0;
-  int xcnt_cap = 0;
-  // fsclg_profile_submit (batch 0), fsclg_cellmax_submit: the launch's chunks (pinned, read by the
-  // kernel), the chunks of each run
-  ProfChunk* p_cmchunks = nullptr;
-  int cmchunk_cap = 0;
+  int n_res = 0;                    // results of the submitted call: the profile's points, curve records, site
+                                    // requests, sampled sites, tail points, surface or block-sum positions
+  double ms[BK_COUNT] = {};         // by kind: the kernel time of the batch's last call of that kind (fsclg_*_last_ms)
+  Buf<char, DEVICE> d_xacc;         // split cells' accumulators and arrival counters
+  Buf<unsigned int, DEVICE> d_xcnt;
+  // fsclg_profile_submit (batch 0), fsclg_cellmax_submit: the launch's chunks (read by the kernel), the
+  // chunks of each run
+  Buf<ProfChunk, PINNED> p_cmchunks;
   std::vector<int> cm_nchunk;
-  double cm_ms = 0.0;               // kernel time of the batch's last cell-maximum launch
-  // fsclg_curve_submit: the records (pinned, written by the kernel; the chunks are p_cmchunks)
-  fsclg_curve_t* p_curve = nullptr;
-  int curve_cap = 0;
-  int cv_n = 0;                     // records of the submitted launch
-  double cv_ms = 0.0;               // kernel time of the batch's last curve launch
-  // fsclg_sites_submit: requests and headers (pinned; read / written by pass 0), the tasks and the
-  // staging area of one term launch (pinned; read / written by pass 1)
-  fsclg_site_req_t* p_sreq = nullptr;
-  fsclg_site_hdr_t* p_shdr = nullptr;
-  SiteTask* p_stasks = nullptr;
-  double* p_sterms = nullptr;
-  int sreq_cap = 0, shdr_cap = 0, stask_cap = 0, sterm_cap = 0;
-  int st_n = 0;                     // requests of the submitted call
+  // fsclg_curve_submit: the records (written by the kernel; the chunks are p_cmchunks)
+  Buf<fsclg_curve_t, PINNED> p_curve;
+  // fsclg_sites_submit: requests and headers (read / written by pass 0), the tasks and the staging area of
+  // one term launch (read / written by pass 1)
+  Buf<fsclg_site_req_t, PINNED> p_sreq;
+  Buf<fsclg_site_hdr_t, PINNED> p_shdr;
+  Buf<SiteTask, PINNED> p_stasks;
+  Buf<double, PINNED> p_sterms;
   bool st_synced = false;           // the header launch has been waited for (a wait that only sized the buffer)
-  double st_ms = 0.0;               // kernel time of the batch's last sites call
-  // fsclg_sample_submit: the depth of every site and the drawn counts (pinned; read / written by the
-  // kernel), the sweeps (pinned staging, copied to d_sweeps on the batch's stream)
-  int32_t* p_sdepth = nullptr;
-  int32_t* p_sfreq = nullptr;
-  fsclg_sweep_t* p_ssweeps = nullptr;
-  fsclg_sweep_t* d_sweeps = nullptr;
-  int sdepth_cap = 0, sfreq_cap = 0, ssweep_cap = 0, dsweep_cap = 0;
-  int sm_n = 0;                     // sites of the submitted sample
-  double sm_ms = 0.0;               // kernel time of the batch's last sample
-  // fsclg_tail_submit: the samples (pinned staging, copied to d_tsamples on the batch's stream); offsets,
-  // counts, observed values and results (pinned; read / written by the kernel)
-  float* p_tsamples = nullptr;
-  float* d_tsamples = nullptr;
-  unsigned long long* p_toff = nullptr;
-  int32_t* p_tcnt = nullptr;
-  double* p_tx0 = nullptr;
-  fsclg_tail_t* p_tout = nullptr;
-  int tsamp_cap = 0, toff_cap = 0, tcnt_cap = 0, tx0_cap = 0, tout_cap = 0;
-  size_t dtsamp_cap = 0;
-  int tl_n = 0;                     // points of the submitted tail call
-  double tl_ms = 0.0;               // kernel time of the batch's last tail call
-  // fsclg_surface_submit: the chunks and the runs' alpha lists (pinned, read by the kernel), the values
-  // (pinned, written by the kernel; the points are p_out)
-  SurfChunk* p_sfchunks = nullptr;
-  double* p_sfla = nullptr;
-  double* p_sfsm = nullptr;
-  int sfchunk_cap = 0, sfla_cap = 0, sfsm_cap = 0;
-  int sf_n = 0, sf_nla = 0;         // positions and alphas per position of the submitted surfaces
-  double sf_ms = 0.0;               // kernel time of the batch's last surface launch
-  // fsclg_cond_submit: the surface call's buffers, and the positions' clips (pinned, read by the kernel)
-  int32_t* p_cdclip = nullptr;
-  int cdclip_cap = 0;
-  double cd_ms = 0.0;               // kernel time of the batch's last conditional launch
-  // fsclg_blocks_submit: the chunks, the alpha lists and the blocks' first sites (pinned, read by the kernel),
-  // the block sums and counts (pinned, written by the kernel; the points are p_out), the device copy of the sums
-  BlkChunk* p_bkchunks = nullptr;
-  double* p_bkla = nullptr;
-  int32_t* p_bkbf = nullptr;
-  double* p_bkbs = nullptr;
-  uint32_t* p_bkcnt = nullptr;
-  double* d_bkbs = nullptr;
-  int bkchunk_cap = 0, bkla_cap = 0, bkbf_cap = 0, bkbs_cap = 0, bkcnt_cap = 0, dbkbs_cap = 0;
-  int bk_n = 0;                     // positions of the submitted block sums
-  size_t bk_cells = 0;              // their (position, block, alpha) cells
-  double bk_ms = 0.0;               // kernel time of the batch's last block-sum launch
+  // fsclg_sample_submit: the depth of every site and the drawn counts (read / written by the kernel), the
+  // sweeps (staging, copied to d_sweeps on the batch's stream)
+  Buf<int32_t, PINNED> p_sdepth, p_sfreq;
+  Buf<fsclg_sweep_t, PINNED> p_ssweeps;
+  Buf<fsclg_sweep_t, DEVICE> d_sweeps;
+  // fsclg_tail_submit: the samples (staging, copied to d_tsamples on the batch's stream); offsets, counts,
+  // observed values and results (read / written by the kernel)
+  Buf<float, PINNED> p_tsamples;
+  Buf<float, DEVICE> d_tsamples;
+  Buf<unsigned long long, PINNED> p_toff;
+  Buf<int32_t, PINNED> p_tcnt;
+  Buf<double, PINNED> p_tx0;
+  Buf<fsclg_tail_t, PINNED> p_tout;
+  // fsclg_surface_submit: the chunks and the runs' alpha lists (read by the kernel), the values (written by
+  // the kernel; the points are p_out)
+  Buf<SurfChunk, PINNED> p_sfchunks;
+  Buf<double, PINNED> p_sfla, p_sfsm;
+  int sf_nla = 0;                   // alphas per position of the submitted surfaces
+  // fsclg_cond_submit: the surface call's buffers, and the positions' clips (read by the kernel)
+  Buf<int32_t, PINNED> p_cdclip;
+  // fsclg_blocks_submit: the chunks, the alpha lists and the blocks' first sites (read by the kernel), the
+  // block sums and counts (written by the kernel; the points are p_out), the device copy of the sums
+  Buf<BlkChunk, PINNED> p_bkchunks;
+  Buf<double, PINNED> p_bkla, p_bkbs;
+  Buf<int32_t, PINNED> p_bkbf;
+  Buf<uint32_t, PINNED> p_bkcnt;
+  Buf<double, DEVICE> d_bkbs;
+  size_t bk_cells = 0;              // the (position, block, alpha) cells of the submitted block sums
 };
 
 struct fsclg_ctx {
@@ -3931,14 +3941,13 @@ struct fsclg_ctx {
   double step = 0.0;
   // snps
   uint2* d_pr0 = nullptr;         // (biased position, device row) with the unpermuted rows
-  uint32_t* d_plan_tmp = nullptr; // fsclg_slot_set_rows_plan: the range of an overlapping block
-  int plan_tmp_cap = 0;
+  Buf<uint32_t, DEVICE> d_plan_tmp;  // fsclg_slot_set_rows_plan: the range of an overlapping block
   std::vector<uint2> h_pr0;
   int n_snps = 0;
   int32_t* d_chr_start = nullptr;
   int32_t* d_chr_n = nullptr;
-  int2* d_wtasks = nullptr;
-  int n_wtasks = 0, wtask_cap = 0, wtask_er = -1;
+  Buf<int2, DEVICE> d_wtasks;
+  int n_wtasks = 0, wtask_er = -1;
   int wtask_chunk = -1;                 // the dense task list is for window_chunk_kernel (256 per task) or not
   std::vector<double> h_nullrows;       // the uploaded null rows (chunk_params)
   double window_ms = 0.0;
@@ -3959,8 +3968,7 @@ struct fsclg_ctx {
   // LDS coefficient cache plan (fsclg_plan_cache)
   bool plan_dirty = true;
   bool hist_pending = false;          // the next search_maxpos launch measures the interval histogram
-  unsigned long long* d_ivhist = nullptr;
-  int ivhist_n = 0;
+  Buf<unsigned long long, DEVICE> d_ivhist;
   int c_ivc0 = 0, c_civ = 0, c_crow = 0;
   double c_cover = 0.0;
   int c_ivc0_b = 0, c_civ_b = 0;         // the window beside band mode's BandLds (Params::off_bd)
@@ -3984,18 +3992,8 @@ struct fsclg_ctx {
   int ci_guess = 5;                       // of split cells' speculative refine walks (Params::ci_guess)
   double kernel_ms = 0.0;
   unsigned long long launches = 0;
-  int prof_n = 0;                  // points of the submitted profile (batch 0 holds it)
-  double prof_ms = 0.0;            // kernel time of the last profile (fsclg_profile_last_ms)
   std::vector<std::pair<double, double>> busy;  // [start, end) ms of each batch's kernels since ev_ref
 };
-
-static thread_local char g_err[512];
-static int set_err(int code, const char* what, hipError_t e = hipSuccess) {
-  if (e != hipSuccess) snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
-  else snprintf(g_err, sizeof g_err, "%s", what);
-  return code;
-}
-#define HIPCHK(x, what) do { hipError_t e_ = (x); if (e_ != hipSuccess) return set_err(FSCLG_E_HIP, what, e_); } while (0)
 
 template <typename T>
 static int upload(T** dst, const T* src, size_t n, hipStream_t s) {
@@ -4009,6 +4007,13 @@ static int upload(T** dst, const T* src, size_t n, hipStream_t s) {
     if (e != hipSuccess) return set_err(FSCLG_E_HIP, "hipStreamSynchronize", e);
   }
   return FSCLG_OK;
+}
+template <typename T>  // the same into a slot's Buf: a new allocation of exactly n elements
+static int upload(Buf<T, DEVICE>& b, const T* src, size_t n, hipStream_t s) {
+  b.release();
+  const int r = upload(&b.p, src, n, s);
+  if (!r) b.cap = n ? n : 1;
+  return r;
 }
 
 static int update_dfail(fsclg_ctx* c);
@@ -4099,33 +4104,17 @@ int fsclg_close(fsclg_ctx* c) {
             g_hprof[7], g_hprof[8]);
   hipSetDevice(c->device);
   hipDeviceSynchronize();
-  void* ptrs[] = {c->d_ivhist, c->d_logt, c->d_coef, c->d_null, c->d_thr, c->d_pr0,
-                  c->d_chr_start, c->d_chr_n, c->d_wtasks, c->d_la_coarse, c->d_la_refine, c->d_n_refine,
-                  c->d_stats, c->d_dfail, c->d_dband, c->d_tpos, c->d_plan_tmp, c->d_lx,
+  void* ptrs[] = {c->d_logt, c->d_coef, c->d_null, c->d_thr, c->d_pr0,
+                  c->d_chr_start, c->d_chr_n, c->d_la_coarse, c->d_la_refine, c->d_n_refine,
+                  c->d_stats, c->d_dfail, c->d_dband, c->d_tpos, c->d_lx,
                   c->d_smp_coef, c->d_smp_prefix, c->d_smp_depth, c->d_smp_chr};
   for (void* p : ptrs) if (p) hipFree(p);
   for (Slot& S : c->slot) {
-    for (void* p : {(void*)S.d_pr, (void*)S.d_chr_null, (void*)S.d_win_null, (void*)S.d_ctab, (void*)S.d_ctree})
-      if (p) hipFree(p);
-    for (void* p : {(void*)S.h_rows, (void*)S.h_null, (void*)S.p_wtasks}) if (p) hipHostFree(p);
     hipEventDestroy(S.ready);
     if (S.wev0) hipEventDestroy(S.wev0);
     if (S.wev1) hipEventDestroy(S.wev1);
   }
   for (Batch& B : c->batch) {
-    if (B.d_ept) hipFree(B.d_ept);
-    if (B.d_xacc) hipFree(B.d_xacc);
-    if (B.d_xcnt) hipFree(B.d_xcnt);
-    if (B.d_sweeps) hipFree(B.d_sweeps);
-    if (B.d_tsamples) hipFree(B.d_tsamples);
-    for (void* p : {(void*)B.p_cells, (void*)B.p_out, (void*)B.p_epos, (void*)B.p_cell_ep, (void*)B.p_ctrace,
-                    (void*)B.p_cmchunks, (void*)B.p_curve, (void*)B.p_sreq, (void*)B.p_shdr, (void*)B.p_stasks,
-                    (void*)B.p_sterms, (void*)B.p_sdepth, (void*)B.p_sfreq, (void*)B.p_ssweeps,
-                    (void*)B.p_tsamples, (void*)B.p_toff, (void*)B.p_tcnt, (void*)B.p_tx0, (void*)B.p_tout,
-                    (void*)B.p_sfchunks, (void*)B.p_sfla, (void*)B.p_sfsm, (void*)B.p_bkchunks, (void*)B.p_bkla,
-                    (void*)B.p_bkbf, (void*)B.p_bkbs, (void*)B.p_bkcnt, (void*)B.p_cdclip})
-      if (p) hipHostFree(p);
-    if (B.d_bkbs) hipFree(B.d_bkbs);
     hipEventDestroy(B.ev0);
     hipEventDestroy(B.ev1);
     hipEventDestroy(B.ev2);
@@ -4135,7 +4124,7 @@ int fsclg_close(fsclg_ctx* c) {
   hipEventDestroy(c->wev0);
   hipEventDestroy(c->wev1);
   hipStreamDestroy(c->ustream);
-  delete c;
+  delete c;  // (every Buf of the slots, the batches and the context: the device is set and idle)
   return FSCLG_OK;
 }
 
@@ -4272,9 +4261,9 @@ int fsclg_upload_snps(fsclg_ctx* c, const int32_t* pos, const uint32_t* row, int
     if ((r = upload(&c->d_tpos, tp.data(), tp.size(), c->ustream))) return r;
   }
   for (Slot& S : c->slot) {
-    if ((r = upload(&S.d_pr, pr.data(), pr.size(), c->ustream))) return r;
-    if ((r = upload<double>(&S.d_chr_null, nullptr, (size_t)n_chr, c->ustream))) return r;
-    if ((r = upload<double>(&S.d_win_null, nullptr, (size_t)n_snps, c->ustream))) return r;
+    if ((r = upload(S.d_pr, pr.data(), pr.size(), c->ustream))) return r;
+    if ((r = upload<double>(S.d_chr_null, nullptr, (size_t)n_chr, c->ustream))) return r;
+    if ((r = upload<double>(S.d_win_null, nullptr, (size_t)n_snps, c->ustream))) return r;
     S.win_valid = false; S.win_er = -1; S.ctab_valid = false;
     HIPCHK(hipEventRecord(S.ready, c->ustream), "hipEventRecord");
   }
@@ -4307,28 +4296,11 @@ int fsclg_upload_snps(fsclg_ctx* c, const int32_t* pos, const uint32_t* row, int
   return FSCLG_OK;
 }
 
-// pinned host memory the kernels read or write directly (coherent: no cache flush needed
-// between a kernel's stores and the host's reads after its completion event)
-static constexpr unsigned HOSTMEM = hipHostMallocCoherent | hipHostMallocMapped;
-
-static int ensure_null_staging(fsclg_ctx* c, Slot& S) {
-  if (S.null_cap >= c->n_chr) return FSCLG_OK;
-  if (S.h_null) hipHostFree(S.h_null);
-  S.h_null = nullptr; S.null_cap = 0;
-  HIPCHK(hipHostMalloc((void**)&S.h_null, sizeof(double) * c->n_chr, HOSTMEM), "hipHostMalloc null sums");
-  S.null_cap = c->n_chr;
-  return FSCLG_OK;
-}
+static int ensure_null_staging(fsclg_ctx* c, Slot& S) { return S.h_null.ensure(c->n_chr, "hipHostMalloc null sums"); }
 
 static int ensure_row_staging(fsclg_ctx* c, Slot& S) {
-  int r;
-  if ((r = ensure_null_staging(c, S))) return r;
-  if (S.rows_cap >= c->n_snps) return FSCLG_OK;
-  if (S.h_rows) hipHostFree(S.h_rows);
-  S.h_rows = nullptr; S.rows_cap = 0;
-  HIPCHK(hipHostMalloc((void**)&S.h_rows, sizeof(uint32_t) * c->n_snps, HOSTMEM), "hipHostMalloc rows");
-  S.rows_cap = c->n_snps;
-  return FSCLG_OK;
+  const int r = ensure_null_staging(c, S);
+  return r ? r : S.h_rows.ensure(c->n_snps, "hipHostMalloc rows");
 }
 
 uint32_t* fsclg_slot_row_buffer(fsclg_ctx* c, int slot) {
@@ -4362,8 +4334,8 @@ int fsclg_slot_set_rows(fsclg_ctx* c, int slot, const uint32_t* row, const doubl
   }
   if (chr_null) memcpy(S.h_null, chr_null, sizeof(double) * c->n_chr);
   hipLaunchKernelGGL(scatter_rows_kernel<uint32_t>, dim3((c->n_snps + 255) / 256), dim3(64), 0, c->ustream,
-                     S.d_pr, row ? S.h_rows : nullptr, c->d_pr0, c->n_snps, S.d_chr_null,
-                     chr_null ? S.h_null : nullptr, c->n_chr);
+                     S.d_pr, row ? S.h_rows.p : nullptr, c->d_pr0, c->n_snps, S.d_chr_null,
+                     chr_null ? S.h_null.p : nullptr, c->n_chr);
   HIPCHK(hipGetLastError(), "launch scatter_rows_kernel");
   HIPCHK(hipEventRecord(S.ready, c->ustream), "hipEventRecord");
   return FSCLG_OK;
@@ -4449,7 +4421,7 @@ int fsclg_slot_set_rows_packed(fsclg_ctx* c, int slot, const void* row, int row_
   S.win_valid = false; S.ctab_valid = false;
   if (chr_null) memcpy(S.h_null, chr_null, sizeof(double) * c->n_chr);
   // read straight from the caller's portable pinned rows (one buffer can feed every device)
-  const double* cn = chr_null ? S.h_null : nullptr;
+  const double* cn = chr_null ? S.h_null.p : nullptr;
   const int per = 64 * (16 / row_bytes);  // sites per block (one wave)
   const dim3 grid((c->n_snps + per - 1) / per);
   if (row_bytes == 1)
@@ -4493,18 +4465,13 @@ int fsclg_slot_set_rows_plan(fsclg_ctx* c, int slot, const fsclg_swap_t* ent, co
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   int r;
   if ((r = ensure_null_staging(c, S))) return r;
-  if (max_rot > c->plan_tmp_cap) {
-    if (c->d_plan_tmp) HIPCHK(hipFree(c->d_plan_tmp), "hipFree");
-    c->d_plan_tmp = nullptr; c->plan_tmp_cap = 0;
-    HIPCHK(hipMalloc((void**)&c->d_plan_tmp, sizeof(uint32_t) * (size_t)max_rot), "hipMalloc plan");
-    c->plan_tmp_cap = max_rot;
-  }
+  if ((r = c->d_plan_tmp.ensure((size_t)max_rot, "hipMalloc plan"))) return r;
   HIPCHK(hipEventSynchronize(S.ready), "hipEventSynchronize");  // the slot's last upload has read h_null
   S.win_valid = false; S.ctab_valid = false;
   if (chr_null) memcpy(S.h_null, chr_null, sizeof(double) * c->n_chr);
   // the uploaded rows (and the null sums), then the groups in order on the same stream
   hipLaunchKernelGGL(scatter_rows_kernel<uint32_t>, dim3((c->n_snps + 255) / 256), dim3(64), 0, c->ustream, S.d_pr,
-                     nullptr, c->d_pr0, c->n_snps, S.d_chr_null, chr_null ? S.h_null : nullptr, c->n_chr);
+                     nullptr, c->d_pr0, c->n_snps, S.d_chr_null, chr_null ? S.h_null.p : nullptr, c->n_chr);
   for (int q = 0; q < n_grp; q++) {
     const fsclg_swap_t& x = ent[grp[q]];
     if (x.kind == 0) {
@@ -4634,14 +4601,8 @@ static int update_dband(fsclg_ctx* c) {
 }
 
 static int ensure_io(Batch& B, int n) {
-  if (n <= B.cap) return FSCLG_OK;
-  for (void* p : {(void*)B.p_cells, (void*)B.p_out}) if (p) hipHostFree(p);
-  B.p_cells = nullptr; B.p_out = nullptr; B.cap = 0;
-  const int cap = n < 1024 ? 1024 : n;
-  HIPCHK(hipHostMalloc((void**)&B.p_cells, sizeof(fsclg_cell_t) * cap, HOSTMEM), "hipHostMalloc cells");
-  HIPCHK(hipHostMalloc((void**)&B.p_out, sizeof(fsclg_point_t) * cap, HOSTMEM), "hipHostMalloc out");
-  B.cap = cap;
-  return FSCLG_OK;
+  const int r = B.p_cells.ensure(n, "hipHostMalloc cells");
+  return r ? r : B.p_out.ensure(n, "hipHostMalloc out");
 }
 
 // add a slot's pending window-kernel time to window_ms (blocks only if it is still running)
@@ -4698,13 +4659,8 @@ static int ensure_ctab(fsclg_ctx* c, Slot& S, int emin, int ne, long long W) {
   if (tree_on) while (lmax < CT_LMAX && (2ll << lmax) * WC <= W) lmax++;
   if (S.ctab_valid && S.ctab_emin == emin && S.ctab_ne == ne && S.ctree.lmax == lmax) return FSCLG_OK;
   const int nstride = ctab_stride(c);
-  const size_t need = (size_t)nstride * ne;
-  if (S.ctab_cap < need) {
-    if (S.d_ctab) hipFree(S.d_ctab);
-    S.d_ctab = nullptr; S.ctab_cap = 0;
-    HIPCHK(hipMalloc((void**)&S.d_ctab, sizeof(double2) * need), "hipMalloc chunk table");
-    S.ctab_cap = need;
-  }
+  int r;
+  if ((r = S.d_ctab.ensure((size_t)nstride * ne, "hipMalloc chunk table"))) return r;
   S.ctree = CTree{};
   S.ctree.lmax = lmax;
   if (lmax > 0) {
@@ -4715,12 +4671,7 @@ static int ensure_ctab(fsclg_ctx* c, Slot& S, int emin, int ne, long long W) {
       S.ctree.off[L] = (int)tot;
       tot += (size_t)ne * S.ctree.nb[L];
     }
-    if (S.ctree_cap < tot) {
-      if (S.d_ctree) hipFree(S.d_ctree);
-      S.d_ctree = nullptr; S.ctree_cap = 0;
-      HIPCHK(hipMalloc((void**)&S.d_ctree, sizeof(double2) * (tot ? tot : 1)), "hipMalloc chunk tree");
-      S.ctree_cap = tot;
-    }
+    if ((r = S.d_ctree.ensure(tot, "hipMalloc chunk tree"))) return r;
     S.ctree.p = S.d_ctree;
   }
   // FSCLG_CT_LDS=0: the table without LDS staging (one lane per chunk reading its sites), and every
@@ -4790,12 +4741,8 @@ static int ensure_windows(fsclg_ctx* c, int slot, int er, const fsclg_cell_t* ce
     // the other slot's window launch ran on this same stream)
     HIPCHK(hipStreamSynchronize(c->ustream), "hipStreamSynchronize");
     c->n_wtasks = (int)tasks.size();
-    if (c->n_wtasks > c->wtask_cap) {
-      if (c->d_wtasks) hipFree(c->d_wtasks);
-      c->d_wtasks = nullptr; c->wtask_cap = 0;
-      HIPCHK(hipMalloc((void**)&c->d_wtasks, sizeof(int2) * c->n_wtasks), "hipMalloc window tasks");
-      c->wtask_cap = c->n_wtasks;
-    }
+    int r;
+    if ((r = c->d_wtasks.ensure(tasks.size(), "hipMalloc window tasks"))) return r;
     if (c->n_wtasks)
       HIPCHK(hipMemcpyAsync(c->d_wtasks, tasks.data(), sizeof(int2) * tasks.size(), hipMemcpyHostToDevice, c->ustream),
              "copy window tasks");
@@ -4883,16 +4830,11 @@ static int launch_partial_windows(fsclg_ctx* c, Slot& S, int er, const std::vect
     HIPCHK(hipEventSynchronize(S.wev1), "hipEventSynchronize");
     if (hprof_on()) g_hprof[1] += hnow() - t0;
   }
-  if (S.wtask_cap < blocks) {
-    if (S.p_wtasks) hipHostFree(S.p_wtasks);
-    S.p_wtasks = nullptr; S.wtask_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&S.p_wtasks, sizeof(int2) * blocks, HOSTMEM), "hipHostMalloc window tasks");
-    S.wtask_cap = (int)blocks;
-  }
+  int r;
+  if ((r = S.p_wtasks.ensure((size_t)blocks, "hipHostMalloc window tasks"))) return r;
   int nt = 0;
   for (const int2& x : todo)
     for (int o = x.x; o < x.y; o += WN_WG) S.p_wtasks[nt++] = make_int2(o, std::min(WN_WG, x.y - o));
-  int r;
   if ((r = window_time(c, S))) return r;
   HIPCHK(hipEventRecord(S.wev0, c->ustream), "hipEventRecord");
   // the active cells' windows of one trial (the pruned tail, where each trial waits for them):
@@ -5133,12 +5075,7 @@ static Params make_params(fsclg_ctx* c, Batch& B, int slot, int n, int mode, int
   static const int lookahead = getenv("FSCLG_LOOKAHEAD") ? atoi(getenv("FSCLG_LOOKAHEAD")) : 1;
   P.lookahead = lookahead;
   if (getenv("FSCLG_CELL_TRACE")) {
-    if (B.ctrace_cap < n) {
-      if (B.p_ctrace) hipHostFree(B.p_ctrace);
-      B.p_ctrace = nullptr; B.ctrace_cap = 0;
-      if (hipHostMalloc((void**)&B.p_ctrace, sizeof(unsigned long long) * (8 * (size_t)n + 16008), HOSTMEM) == hipSuccess)
-        B.ctrace_cap = n;  // + the FSCLG_INST_TRACE event area
-    }
+    (void)B.p_ctrace.ensure(8 * (size_t)n + 16008);  // + the FSCLG_INST_TRACE event area (no memory: no trace)
     P.ctrace = B.p_ctrace;
   }
   P.n_coarse = c->n_coarse; P.n_iv = c->n_iv; P.step = c->step;
@@ -5196,41 +5133,53 @@ static int launch_blocks_impl(hipStream_t stream, const Params& P, int n) {
   return FSCLG_OK;
 }
 
-extern "C++" {
-template <typename T>
-static int ensure_buf(T** d, int* cap, int n) {
-  if (n <= *cap) return FSCLG_OK;
-  if (*d) hipFree(*d);
-  *d = nullptr; *cap = 0;
-  const int k = n < 1024 ? 1024 : n;
-  HIPCHK(hipMalloc((void**)d, sizeof(T) * k), "hipMalloc");
-  *cap = k;
+// ---- the protocol every submit / wait pair follows.  A kind's submit: its argument and state checks, in
+// its own order; batch_reset; its buffers (Buf::ensure) and inputs; launch_bracket around its kernel;
+// batch_hold.  Its wait: its checks; batch_finish; the copy of its results; flags_err.
+
+// a submit's first touch of the batch: nothing of an earlier call is left, the kind's time starts at zero
+static void batch_reset(Batch& B, BatchKind k, int slot, int eval_range = 0, int bp_resl = 0) {
+  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
+  B.eval_range = eval_range; B.bp_resl = bp_resl; B.n_res = 0; B.st_synced = false; B.ms[k] = 0.0;
+}
+
+// a submit's last step: the batch holds the call, and its slot (none: -1) has one more user
+static int batch_hold(fsclg_ctx* c, Batch& B, BatchKind k) {
+  B.holds = k;
+  if (B.slot >= 0) c->slot[B.slot].users++;
   return FSCLG_OK;
 }
-template <typename T>
-static int ensure_pinned(T** h, int* cap, int n) {
-  if (n <= *cap) return FSCLG_OK;
-  if (*h) hipHostFree(*h);
-  *h = nullptr; *cap = 0;
-  const int k = n < 1024 ? 1024 : n;
-  HIPCHK(hipHostMalloc((void**)h, sizeof(T) * k, hipHostMallocCoherent | hipHostMallocMapped), "hipHostMalloc");
-  *cap = k;
-  return FSCLG_OK;
-}
+static void batch_release(fsclg_ctx* c, Batch& B) {
+  B.holds = BK_NONE;
+  if (B.slot >= 0) c->slot[B.slot].users--;
 }
 
 // the time of the n launches bracketed by the batch's events (both reached), added to the context's
-// totals; *ms: that time
-static int batch_time(fsclg_ctx* c, const Batch& B, int n, double* ms = nullptr) {
+// totals; it is (add: is added to) the batch's time of kind k
+static int batch_time(fsclg_ctx* c, Batch& B, int n, BatchKind k, bool add = false) {
   float t = 0.f, t0 = 0.f, t1 = 0.f;
   HIPCHK(hipEventElapsedTime(&t, B.ev0, B.ev1), "hipEventElapsedTime");
   HIPCHK(hipEventElapsedTime(&t0, c->ev_ref, B.ev0), "hipEventElapsedTime");
   HIPCHK(hipEventElapsedTime(&t1, c->ev_ref, B.ev1), "hipEventElapsedTime");
-  if (ms) *ms = t;
+  B.ms[k] = add ? B.ms[k] + t : t;
   c->kernel_ms += t;
   c->launches += (unsigned long long)n;
   c->busy.emplace_back((double)t0, (double)t1);
   return FSCLG_OK;
+}
+
+// a wait past its checks: the batch is free from here on whatever follows; if the call launched its
+// kernel, that has finished and its time is the kind's
+static int batch_finish(fsclg_ctx* c, Batch& B, BatchKind k, bool launched) {
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  batch_release(c, B);
+  if (!launched) return FSCLG_OK;
+  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  return batch_time(c, B, 1, k);
+}
+
+static double last_ms(const fsclg_ctx* c, int batch, BatchKind k) {
+  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].ms[k] : 0.0;
 }
 
 // the flags of a call's points (their OR) as its return code
@@ -5238,6 +5187,46 @@ static int flags_err(int flags, const char* timeout_msg = "device flag") {
   if (!flags) return FSCLG_OK;
   return set_err(flags & PF_UNSUPPORTED ? FSCLG_E_UNSUPPORTED : FSCLG_E_KERNEL,
                  flags & PF_SPLIT_TIMEOUT ? timeout_msg : "device flag");
+}
+// ... of n points `stride` bytes apart (the records that begin with their point: curves, site headers)
+static int flags_err(const void* pts, size_t stride, int n) {
+  int flags = 0;
+  for (int i = 0; i < n; i++) flags |= reinterpret_cast<const fsclg_point_t*>(static_cast<const char*>(pts) + i * stride)->flags;
+  return flags_err(flags);
+}
+
+extern "C++" {
+// One launch of n workgroups on the batch's stream, between its events: the stream waits for the rows and
+// null sums of the batch's slot, launch(P) gets the parameters (mode 3) of the batch's slot and eval_range
+// (batch_reset set both) and starts the kernel; `what` names it in an error.  from: the parameters of an
+// earlier launch of the same call, whose slot wait still holds
+template <typename F>
+static int launch_bracket(fsclg_ctx* c, Batch& B, int n, const char* what, F&& launch, const Params* from = nullptr) {
+  if (!from) HIPCHK(hipStreamWaitEvent(B.stream, c->slot[B.slot].ready, 0), "hipStreamWaitEvent");
+  Params P = from ? *from : make_params(c, B, B.slot, n, 3, B.eval_range, 0);
+  P.n_cells = n;
+  HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
+  const int r = launch(P);
+  if (r) return r;
+  HIPCHK(hipGetLastError(), what);
+  HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+  return FSCLG_OK;
+}
+
+// the runs cut into chunks of at most CH(run) positions, in run order, then position order:
+// f(run, the chunk's first position, its positions, the positions before it, the chunks before it);
+// returns the number of chunks
+template <typename C, typename F>
+static int for_chunks(const fsclg_run_t* runs, int n_runs, C&& CH, F&& f) {
+  int nc = 0, o = 0;
+  for (int i = 0; i < n_runs; i++)
+    for (int j = 0, ch = CH(i); j < runs[i].count; j += ch) {
+      const int cnt = std::min(ch, runs[i].count - j);
+      f(i, runs[i].start_pos + j * runs[i].step, cnt, o, nc++);
+      o += cnt;
+    }
+  return nc;
+}
 }
 
 // the key of a cell's remembered cost (cell_cost), used only to order a launch longest first:
@@ -5272,13 +5261,9 @@ static int search_submit_impl(fsclg_ctx* c, int batch, int slot, const fsclg_cel
   }
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   int r;
-  B.n_cells = n_cells; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
-  B.eval_range = eval_range; B.bp_resl = bp_resl;
-  if (n_cells == 0) {
-    B.holds = BK_SEARCH;
-    c->slot[slot].users++;
-    return FSCLG_OK;
-  }
+  batch_reset(B, BK_SEARCH, slot, eval_range, bp_resl);
+  B.n_cells = n_cells;
+  if (n_cells == 0) return batch_hold(c, B, BK_SEARCH);
   {
     const double t0 = hprof_on() ? hnow() : 0.0;
     // the cells' windows (a check against what fsclg_slot_windows summed: each batch remembers its
@@ -5407,9 +5392,9 @@ static int search_submit_impl(fsclg_ctx* c, int batch, int slot, const fsclg_cel
   if (hprof_on()) g_hprof[8] += hnow() - t_or;
   if ((r = ensure_io(B, nl))) return r;
   if (use_ep) {
-    if ((r = ensure_buf(&B.d_ept, &B.ept_cap, ne))) return r;
-    if ((r = ensure_pinned(&B.p_epos, &B.pep_cap, ne))) return r;
-    if ((r = ensure_pinned(&B.p_cell_ep, &B.pcep_cap, nl))) return r;
+    if ((r = B.d_ept.ensure(ne))) return r;
+    if ((r = B.p_epos.ensure(ne))) return r;
+    if ((r = B.p_cell_ep.ensure(nl))) return r;
   }
   B.upos.resize(nu);
   for (int k = 0; k < nl; k++) {
@@ -5426,14 +5411,8 @@ static int search_submit_impl(fsclg_ctx* c, int batch, int slot, const fsclg_cel
   if (use_ep) memcpy(B.p_epos, B.epos.data(), sizeof(int2) * ne);
   if (G > 1) {  // the split cells' arrival counters, zeroed before the wait for the slot's rows (the
                 // fill then runs while the upload stream still works, off the blocking batch's path)
-    const size_t xb = (size_t)nl * 2 * sizeof(XAcc);
-    if (B.xacc_cap < xb) {
-      if (B.d_xacc) hipFree(B.d_xacc);
-      B.d_xacc = nullptr; B.xacc_cap = 0;
-      HIPCHK(hipMalloc((void**)&B.d_xacc, xb), "hipMalloc split accumulators");
-      B.xacc_cap = xb;
-    }
-    if ((r = ensure_buf(&B.d_xcnt, &B.xcnt_cap, nl))) return r;
+    if ((r = B.d_xacc.ensure((size_t)nl * 2 * sizeof(XAcc), "hipMalloc split accumulators"))) return r;
+    if ((r = B.d_xcnt.ensure(nl))) return r;
     HIPCHK(hipMemsetAsync(B.d_xcnt, 0, sizeof(unsigned int) * nl, B.stream), "hipMemsetAsync");  // the exchange
                                                                                                   // areas need no zeroing
   }
@@ -5442,7 +5421,7 @@ static int search_submit_impl(fsclg_ctx* c, int batch, int slot, const fsclg_cel
   Params P = make_params(c, B, slot, nl, 0, eval_range, bp_resl);
   if (c->hist_pending && P.n_civ > 0) {  // diagnostic builds (FSCLG_IVHIST): per phase key
     const int nh = (c->n_coarse + 2) * c->n_iv;
-    if ((r = ensure_buf(&c->d_ivhist, &c->ivhist_n, nh))) return r;
+    if ((r = c->d_ivhist.ensure(nh))) return r;
     HIPCHK(hipMemsetAsync(c->d_ivhist, 0, sizeof(unsigned long long) * nh, B.stream), "hipMemset ivhist");
     P.ivhist = c->d_ivhist;
     B.ivhist = c->d_ivhist;
@@ -5472,9 +5451,7 @@ static int search_submit_impl(fsclg_ctx* c, int batch, int slot, const fsclg_cel
   B.trace_n = nl;
   B.nu = nl;
   B.nlaunch = use_ep ? 2 : 1;
-  B.holds = BK_SEARCH;
-  c->slot[slot].users++;
-  return FSCLG_OK;
+  return batch_hold(c, B, BK_SEARCH);
 }
 
 int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
@@ -5489,14 +5466,13 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
   if (B.holds != BK_SEARCH) return set_err(FSCLG_E_STATE, other[B.holds]);
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.holds = BK_NONE;
-  c->slot[B.slot].users--;
+  batch_release(c, B);
   if (B.n_cells == 0) return FSCLG_OK;
   const int nu = B.nu;
   // the batch's own completion (its stream may hold later batches): the D2H after ev1
   HIPCHK(hipEventSynchronize(B.ev2), "hipEventSynchronize");
   int r;
-  if ((r = batch_time(c, B, B.nlaunch))) return r;
+  if ((r = batch_time(c, B, B.nlaunch, BK_SEARCH))) return r;
   if (B.ivhist) {  // re-plan the LDS window from the measured histogram
     const int nkey = c->n_coarse + 2;
     std::vector<unsigned long long> hk((size_t)nkey * c->n_iv), h(c->n_iv, 0);
@@ -5602,14 +5578,8 @@ int fsclg_search_points(fsclg_ctx* c, fsclg_point_t* pts, int n_pts) {
   if (G < 2) G = 1;
   if (G > 1) {
     const int nl = (n_pts + 7) / 8 * 8;
-    const size_t xb = (size_t)nl * 2 * sizeof(XAcc);
-    if (B.xacc_cap < xb) {
-      if (B.d_xacc) hipFree(B.d_xacc);
-      B.d_xacc = nullptr; B.xacc_cap = 0;
-      HIPCHK(hipMalloc((void**)&B.d_xacc, xb), "hipMalloc split accumulators");
-      B.xacc_cap = xb;
-    }
-    if ((r = ensure_buf(&B.d_xcnt, &B.xcnt_cap, nl))) return r;
+    if ((r = B.d_xacc.ensure((size_t)nl * 2 * sizeof(XAcc), "hipMalloc split accumulators"))) return r;
+    if ((r = B.d_xcnt.ensure(nl))) return r;
     HIPCHK(hipMemsetAsync(B.d_xcnt, 0, sizeof(unsigned int) * nl, B.stream), "hipMemsetAsync");
     P.split = G; P.xacc = B.d_xacc; P.xcnt = B.d_xcnt;
     P.spec_refine = spec_refine_on();
@@ -5625,7 +5595,7 @@ int fsclg_search_points(fsclg_ctx* c, fsclg_point_t* pts, int n_pts) {
     if (pts[i].flags & (PF_UNSUPPORTED | PF_SPLIT_TIMEOUT))
       return flags_err(pts[i].flags & (PF_UNSUPPORTED | PF_SPLIT_TIMEOUT),
                        "device flag: a point's members were not resident together");
-  return batch_time(c, B, 1);
+  return batch_time(c, B, 1, BK_SEARCH);
 }
 
 // Chunk length of the profile kernel: positions per workgroup, i.e. per LDS prologue
@@ -5704,34 +5674,23 @@ static int launch_run_kernel(fsclg_ctx* c, Batch& B, RunKernel k, const Params& 
   return FSCLG_OK;
 }
 }
-static int launch_runs(fsclg_ctx* c, Batch& B, int slot, const fsclg_run_t* runs, int n_runs, int eval_range, int CH,
-                       int nchunk, RunKernel k, bool by_chunk) {
+static int launch_runs(fsclg_ctx* c, Batch& B, const fsclg_run_t* runs, int n_runs, int CH, int nchunk, RunKernel k,
+                       bool by_chunk) {
   int r;
-  if ((r = cover_windows(c, B, slot, run_cover(runs, n_runs), eval_range))) return r;
-  if ((r = ensure_pinned(&B.p_cmchunks, &B.cmchunk_cap, nchunk))) return r;
-  int nc = 0, o = 0;
-  for (int i = 0; i < n_runs; i++)
-    for (int j = 0; j < runs[i].count; j += CH) {
-      const int cnt = std::min(CH, runs[i].count - j);
-      B.p_cmchunks[nc] = ProfChunk{runs[i].chr, runs[i].start_pos + j * runs[i].step, runs[i].step, cnt, by_chunk ? nc : o,
-                                   {0, 0, 0}};
-      nc++;
-      o += cnt;
-    }
-  HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
-  Params P = make_params(c, B, slot, nc, 3, eval_range, 0);
-  P.band_th = -1;
-  lds_layout(c, P, WIN_WALK);
-  P.ctrace = nullptr;
-  const int dyn = lds_dyn_bytes(P);
-  HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
-  // (tables too large for the LDS copies: every coefficient from the global table, as the cell path)
-  if ((r = STAT_M + dyn <= LDS_WG ? launch_run_kernel<true>(c, B, k, P, dyn) : launch_run_kernel<false>(c, B, k, P, 0)))
-    return r;
+  if ((r = cover_windows(c, B, B.slot, run_cover(runs, n_runs), B.eval_range))) return r;
+  if ((r = B.p_cmchunks.ensure(nchunk))) return r;
+  const int nc = for_chunks(runs, n_runs, [CH](int) { return CH; }, [&](int i, int pos, int cnt, int o, int ch) {
+    B.p_cmchunks[ch] = ProfChunk{runs[i].chr, pos, runs[i].step, cnt, by_chunk ? ch : o, {0, 0, 0}};
+  });
   static const char* const what[] = {"launch profile_kernel", "launch cellmax_kernel", "launch curve_kernel"};
-  HIPCHK(hipGetLastError(), what[k]);
-  HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
-  return FSCLG_OK;
+  return launch_bracket(c, B, nc, what[k], [&](Params& P) {
+    P.band_th = -1;
+    lds_layout(c, P, WIN_WALK);
+    P.ctrace = nullptr;
+    const int dyn = lds_dyn_bytes(P);
+    // (tables too large for the LDS copies: every coefficient from the global table, as the cell path)
+    return STAT_M + dyn <= LDS_WG ? launch_run_kernel<true>(c, B, k, P, dyn) : launch_run_kernel<false>(c, B, k, P, 0);
+  });
 }
 
 int fsclg_profile_submit(fsclg_ctx* c, const fsclg_run_t* runs, int n_runs, int eval_range) {
@@ -5745,35 +5704,28 @@ int fsclg_profile_submit(fsclg_ctx* c, const fsclg_run_t* runs, int n_runs, int 
   if ((r = validate_runs(c, runs, n_runs, eval_range, CH, &total, &nchunk))) return r;
   if (total > 0x7FFFFFFFll / (long long)sizeof(fsclg_point_t)) return set_err(FSCLG_E_ARG, "too many profile points");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  c->prof_n = (int)total; c->prof_ms = 0.0;
-  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = 0; B.ivhist = nullptr; B.traced = false;
+  batch_reset(B, BK_PROFILE, 0, eval_range);
+  B.n_res = (int)total;
   if (total > 0) {
     // the profile is of the data as uploaded: the unpermuted rows into slot 0 (its whole-chromosome
     // null sums are the caller's, fsclg_set_chr_null, as for fsclg_search_maxpos); no batch runs on
     // the slot then, so its window null sums are made by fsclg_slot_windows
     if ((r = fsclg_slot_set_rows(c, 0, nullptr, nullptr))) return r;
     if ((r = ensure_io(B, (int)total))) return r;
-    if ((r = launch_runs(c, B, 0, runs, n_runs, eval_range, CH, (int)nchunk, RUN_PROFILE, false))) return r;
+    if ((r = launch_runs(c, B, runs, n_runs, CH, (int)nchunk, RUN_PROFILE, false))) return r;
   }
-  B.holds = BK_PROFILE;
-  c->slot[0].users++;
-  return FSCLG_OK;
+  return batch_hold(c, B, BK_PROFILE);
 }
 
 int fsclg_profile_wait(fsclg_ctx* c, fsclg_point_t* out) {
   if (!c) return set_err(FSCLG_E_ARG, "context");
   Batch& B = c->batch[0];
   if (B.holds != BK_PROFILE) return set_err(FSCLG_E_STATE, "no profile submitted");
-  if (!out && c->prof_n) return set_err(FSCLG_E_ARG, "out");
-  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.holds = BK_NONE;
-  c->slot[0].users--;
-  const int n = c->prof_n;
-  if (n == 0) return FSCLG_OK;
-  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
-  memcpy(out, B.p_out, sizeof(fsclg_point_t) * (size_t)n);
+  const int n = B.n_res;
+  if (!out && n) return set_err(FSCLG_E_ARG, "out");
   int r;
-  if ((r = batch_time(c, B, 1, &c->prof_ms))) return r;
+  if ((r = batch_finish(c, B, BK_PROFILE, n > 0)) || n == 0) return r;
+  memcpy(out, B.p_out, sizeof(fsclg_point_t) * (size_t)n);
   note_alphas(c, out, n);
   for (int i = 0; i < n; i++)
     if (out[i].flags) return flags_err(out[i].flags);  // the first flagged point's
@@ -5791,7 +5743,7 @@ int fsclg_profile(fsclg_ctx* c, const fsclg_run_t* runs, int n_runs, int eval_ra
   return fsclg_profile_wait(c, out);
 }
 
-double fsclg_profile_last_ms(fsclg_ctx* c) { return c ? c->prof_ms : 0.0; }
+double fsclg_profile_last_ms(fsclg_ctx* c) { return last_ms(c, 0, BK_PROFILE); }
 
 // The runs' maxima on the rows a slot holds: fsclg_profile_submit's chunks, evaluated by
 // cellmax_kernel on any batch and slot, one stored point per chunk (fsclg_cellmax_wait folds them)
@@ -5807,17 +5759,15 @@ int fsclg_cellmax_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* r
   if ((r = validate_runs(c, runs, n_runs, eval_range, CH, &total, &nchunk))) return r;
   if (nchunk > 0x7FFFFFFFll / (long long)sizeof(fsclg_point_t)) return set_err(FSCLG_E_ARG, "too many chunks");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.n_cells = n_runs; B.nu = (int)nchunk; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
-  B.eval_range = eval_range; B.bp_resl = 0; B.cm_ms = 0.0;
+  batch_reset(B, BK_CELLMAX, slot, eval_range);
+  B.n_cells = n_runs; B.nu = (int)nchunk;
   B.cm_nchunk.resize((size_t)n_runs);
   for (int i = 0; i < n_runs; i++) B.cm_nchunk[i] = (runs[i].count + CH - 1) / CH;
   if (nchunk > 0) {
     if ((r = ensure_io(B, (int)nchunk))) return r;
-    if ((r = launch_runs(c, B, slot, runs, n_runs, eval_range, CH, (int)nchunk, RUN_CELLMAX, true))) return r;
+    if ((r = launch_runs(c, B, runs, n_runs, CH, (int)nchunk, RUN_CELLMAX, true))) return r;
   }
-  B.holds = BK_CELLMAX;
-  c->slot[slot].users++;
-  return FSCLG_OK;
+  return batch_hold(c, B, BK_CELLMAX);
 }
 
 int fsclg_cellmax_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
@@ -5825,15 +5775,9 @@ int fsclg_cellmax_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
   Batch& B = c->batch[batch];
   if (B.holds != BK_CELLMAX) return set_err(FSCLG_E_STATE, "no cell maxima submitted on the batch");
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
-  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.holds = BK_NONE;
-  c->slot[B.slot].users--;
-  const int n_runs = B.n_cells, nc = B.nu;
-  if (nc > 0) {
-    int r;
-    HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
-    if ((r = batch_time(c, B, 1, &B.cm_ms))) return r;
-  }
+  const int n_runs = B.n_cells;
+  int r;
+  if ((r = batch_finish(c, B, BK_CELLMAX, B.nu > 0))) return r;
   // a run's chunk maxima in chunk order, strict >: the first position of the greatest clr
   int flags = 0;
   for (int i = 0, k = 0; i < n_runs; i++) {
@@ -5856,9 +5800,7 @@ int fsclg_cellmax_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
   return flags_err(flags);
 }
 
-double fsclg_cellmax_last_ms(fsclg_ctx* c, int batch) {
-  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].cm_ms : 0.0;
-}
+double fsclg_cellmax_last_ms(fsclg_ctx* c, int batch) { return last_ms(c, batch, BK_CELLMAX); }
 
 // The runs' alpha likelihood curves on the rows a slot holds: fsclg_cellmax_submit's checks, chunks,
 // slot and window null sums; curve_kernel stores one record per position
@@ -5875,39 +5817,29 @@ int fsclg_curve_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* run
   if ((r = validate_runs(c, runs, n_runs, eval_range, CH, &total, &nchunk))) return r;
   if (total > 0x7FFFFFFFll / (long long)sizeof(fsclg_curve_t)) return set_err(FSCLG_E_ARG, "too many curve positions");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.n_cells = 0; B.nu = (int)nchunk; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
-  B.eval_range = eval_range; B.bp_resl = 0; B.cv_ms = 0.0; B.cv_n = (int)total;
+  batch_reset(B, BK_CURVE, slot, eval_range);
+  B.nu = (int)nchunk; B.n_res = (int)total;
   if (total > 0) {
     if ((r = ensure_io(B, 1))) return r;  // (make_params' cells and points: unused by this kernel)
-    if ((r = ensure_pinned(&B.p_curve, &B.curve_cap, (int)total))) return r;
-    if ((r = launch_runs(c, B, slot, runs, n_runs, eval_range, CH, (int)nchunk, RUN_CURVE, false))) return r;
+    if ((r = B.p_curve.ensure(total))) return r;
+    if ((r = launch_runs(c, B, runs, n_runs, CH, (int)nchunk, RUN_CURVE, false))) return r;
   }
-  B.holds = BK_CURVE;
-  c->slot[slot].users++;
-  return FSCLG_OK;
+  return batch_hold(c, B, BK_CURVE);
 }
 
 int fsclg_curve_wait(fsclg_ctx* c, int batch, fsclg_curve_t* out) {
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
   if (B.holds != BK_CURVE) return set_err(FSCLG_E_STATE, "no curves submitted on the batch");
-  if (!out && B.cv_n) return set_err(FSCLG_E_ARG, "out");
-  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.holds = BK_NONE;
-  c->slot[B.slot].users--;
-  const int n = B.cv_n;
-  if (n == 0) return FSCLG_OK;
-  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  const int n = B.n_res;
+  if (!out && n) return set_err(FSCLG_E_ARG, "out");
+  int r;
+  if ((r = batch_finish(c, B, BK_CURVE, n > 0)) || n == 0) return r;
   memcpy(out, B.p_curve, sizeof(fsclg_curve_t) * (size_t)n);
-  int r, flags = 0;
-  if ((r = batch_time(c, B, 1, &B.cv_ms))) return r;
-  for (int i = 0; i < n; i++) flags |= out[i].pt.flags;
-  return flags_err(flags);
+  return flags_err(out, sizeof *out, n);  // (a record begins with its point)
 }
 
-double fsclg_curve_last_ms(fsclg_ctx* c, int batch) {
-  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].cv_ms : 0.0;
-}
+double fsclg_curve_last_ms(fsclg_ctx* c, int batch) { return last_ms(c, batch, BK_CURVE); }
 
 unsigned long long fsclg_curve_forced(fsclg_ctx* c) {
   unsigned long long h = 0;
@@ -5957,43 +5889,34 @@ static int surface_like_submit(fsclg_ctx* c, int batch, int slot, const fsclg_ru
   if (total * n_la > 0x7FFFFFFFll / (long long)sizeof(double) || total > 0x7FFFFFFFll / (long long)sizeof(fsclg_point_t))
     return set_err(FSCLG_E_ARG, "too many surface cells");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.n_cells = 0; B.nu = (int)nchunk; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
-  B.eval_range = eval_range; B.bp_resl = 0; B.sf_n = (int)total; B.sf_nla = n_la;
-  if (kind == BK_COND) B.cd_ms = 0.0;
-  else B.sf_ms = 0.0;
+  batch_reset(B, kind, slot, eval_range);
+  B.nu = (int)nchunk; B.n_res = (int)total; B.sf_nla = n_la;
   if (total > 0) {
     if ((r = cover_windows(c, B, slot, run_cover(runs, n_runs), eval_range))) return r;
     if ((r = ensure_io(B, (int)total))) return r;
-    if ((r = ensure_pinned(&B.p_sfchunks, &B.sfchunk_cap, (int)nchunk))) return r;
-    if ((r = ensure_pinned(&B.p_sfla, &B.sfla_cap, n_runs * n_la))) return r;
-    if ((r = ensure_pinned(&B.p_sfsm, &B.sfsm_cap, (int)(total * n_la)))) return r;
+    if ((r = B.p_sfchunks.ensure(nchunk))) return r;
+    if ((r = B.p_sfla.ensure((size_t)n_runs * n_la))) return r;
+    if ((r = B.p_sfsm.ensure(total * n_la))) return r;
     memcpy(B.p_sfla, la, sizeof(double) * (size_t)n_runs * (size_t)n_la);
     if (kind == BK_COND) {
-      if ((r = ensure_pinned(&B.p_cdclip, &B.cdclip_cap, (int)(2 * total)))) return r;
+      if ((r = B.p_cdclip.ensure(2 * total))) return r;
       memcpy(B.p_cdclip, clip, sizeof(int32_t) * 2 * (size_t)total);
     }
-    int nc = 0, o = 0;
-    for (int i = 0; i < n_runs; i++)
-      for (int j = 0; j < runs[i].count; j += CH) {
-        const int cnt = std::min(CH, runs[i].count - j);
-        B.p_sfchunks[nc++] = SurfChunk{runs[i].chr, runs[i].start_pos + j * runs[i].step, runs[i].step, cnt, o, i, {0, 0}};
-        o += cnt;
-      }
-    HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
-    Params P = make_params(c, B, slot, nc, 3, eval_range, 0);
-    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
-    if (kind == BK_COND)
-      hipLaunchKernelGGL(cond_kernel, dim3(nc), dim3(64 * SURF_WAVES), 0, B.stream, P, (const SurfChunk*)B.p_sfchunks,
-                         (const double*)B.p_sfla, n_la, (const int32_t*)B.p_cdclip, B.p_sfsm);
-    else
-      hipLaunchKernelGGL(surface_kernel, dim3(nc), dim3(64 * SURF_WAVES), 0, B.stream, P, (const SurfChunk*)B.p_sfchunks,
-                         (const double*)B.p_sfla, n_la, B.p_sfsm);
-    HIPCHK(hipGetLastError(), kind == BK_COND ? "launch cond_kernel" : "launch surface_kernel");
-    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+    const int nc = for_chunks(runs, n_runs, [CH](int) { return CH; }, [&](int i, int pos, int cnt, int o, int ch) {
+      B.p_sfchunks[ch] = SurfChunk{runs[i].chr, pos, runs[i].step, cnt, o, i, {0, 0}};
+    });
+    r = launch_bracket(c, B, nc, kind == BK_COND ? "launch cond_kernel" : "launch surface_kernel", [&](const Params& P) {
+      if (kind == BK_COND)
+        hipLaunchKernelGGL(cond_kernel, dim3(nc), dim3(64 * SURF_WAVES), 0, B.stream, P, (const SurfChunk*)B.p_sfchunks,
+                           (const double*)B.p_sfla, n_la, (const int32_t*)B.p_cdclip, B.p_sfsm);
+      else
+        hipLaunchKernelGGL(surface_kernel, dim3(nc), dim3(64 * SURF_WAVES), 0, B.stream, P, (const SurfChunk*)B.p_sfchunks,
+                           (const double*)B.p_sfla, n_la, B.p_sfsm);
+      return FSCLG_OK;
+    });
+    if (r) return r;
   }
-  B.holds = kind;
-  c->slot[slot].users++;
-  return FSCLG_OK;
+  return batch_hold(c, B, kind);
 }
 
 int fsclg_surface_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* runs, int n_runs, const double* la,
@@ -6006,28 +5929,20 @@ static int surface_like_wait(fsclg_ctx* c, int batch, fsclg_point_t* pts, double
   Batch& B = c->batch[batch];
   if (B.holds != kind)
     return set_err(FSCLG_E_STATE, kind == BK_COND ? "no conditional scan submitted on the batch" : "no surfaces submitted on the batch");
-  if ((!pts || !sm) && B.sf_n) return set_err(FSCLG_E_ARG, "out");
-  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.holds = BK_NONE;
-  c->slot[B.slot].users--;
-  const int n = B.sf_n;
-  if (n == 0) return FSCLG_OK;
-  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  const int n = B.n_res;
+  if ((!pts || !sm) && n) return set_err(FSCLG_E_ARG, "out");
+  int r;
+  if ((r = batch_finish(c, B, kind, n > 0)) || n == 0) return r;
   memcpy(pts, B.p_out, sizeof(fsclg_point_t) * (size_t)n);
   memcpy(sm, B.p_sfsm, sizeof(double) * (size_t)n * (size_t)B.sf_nla);
-  int r, flags = 0;
-  if ((r = batch_time(c, B, 1, kind == BK_COND ? &B.cd_ms : &B.sf_ms))) return r;
-  for (int i = 0; i < n; i++) flags |= pts[i].flags;
-  return flags_err(flags);
+  return flags_err(pts, sizeof *pts, n);
 }
 
 int fsclg_surface_wait(fsclg_ctx* c, int batch, fsclg_point_t* pts, double* sm) {
   return surface_like_wait(c, batch, pts, sm, BK_SURFACE);
 }
 
-double fsclg_surface_last_ms(fsclg_ctx* c, int batch) {
-  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].sf_ms : 0.0;
-}
+double fsclg_surface_last_ms(fsclg_ctx* c, int batch) { return last_ms(c, batch, BK_SURFACE); }
 
 // ------------------------------------------------------------ conditional sweep scan (host side)
 // fsclg_surface_submit with one site-index pair (lo, hi) per position, copied like the runs: cond_kernel
@@ -6042,9 +5957,7 @@ int fsclg_cond_wait(fsclg_ctx* c, int batch, fsclg_point_t* pts, double* sm) {
   return surface_like_wait(c, batch, pts, sm, BK_COND);
 }
 
-double fsclg_cond_last_ms(fsclg_ctx* c, int batch) {
-  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].cd_ms : 0.0;
-}
+double fsclg_cond_last_ms(fsclg_ctx* c, int batch) { return last_ms(c, batch, BK_COND); }
 
 // ------------------------------------------------------------ block sums of the surface (host side)
 // fsclg_surface_submit's checks, slot and window null sums; per run the table of each block's first site:
@@ -6078,80 +5991,63 @@ int fsclg_blocks_submit(fsclg_ctx* c, int batch, int slot, const fsclg_run_t* ru
       nbf > 0x7FFFFFFFll / 4)
     return set_err(FSCLG_E_ARG, "too many block cells");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
-  B.eval_range = eval_range; B.bp_resl = 0; B.bk_ms = 0.0; B.bk_n = (int)total; B.bk_cells = (size_t)(items * n_la);
+  batch_reset(B, BK_BLOCKS, slot, eval_range);
+  B.n_res = (int)total; B.bk_cells = (size_t)(items * n_la);
   if (total > 0) {
-    nchunk = 0;
-    for (int i = 0; i < n_runs; i++) {
-      const int CH = list_chunk(BLK_CH, BLK_WAVES, blk[i].nb);
-      nchunk += (runs[i].count + CH - 1) / CH;  // (count >= 0: validate_runs)
-    }
-    B.nu = (int)nchunk;
+    const auto CH = [blk](int i) { return list_chunk(BLK_CH, BLK_WAVES, blk[i].nb); };
+    B.nu = for_chunks(runs, n_runs, CH, [](int, int, int, int, int) {});
     if ((r = cover_windows(c, B, slot, run_cover(runs, n_runs), eval_range))) return r;
     if ((r = ensure_io(B, (int)total))) return r;
-    if ((r = ensure_pinned(&B.p_bkchunks, &B.bkchunk_cap, (int)nchunk))) return r;
-    if ((r = ensure_pinned(&B.p_bkla, &B.bkla_cap, n_runs * n_la))) return r;
-    if ((r = ensure_pinned(&B.p_bkbf, &B.bkbf_cap, (int)nbf))) return r;
-    if ((r = ensure_pinned(&B.p_bkbs, &B.bkbs_cap, (int)B.bk_cells))) return r;
-    if ((r = ensure_pinned(&B.p_bkcnt, &B.bkcnt_cap, (int)B.bk_cells))) return r;
-    if ((r = ensure_buf(&B.d_bkbs, &B.dbkbs_cap, (int)B.bk_cells))) return r;
+    if ((r = B.p_bkchunks.ensure(B.nu))) return r;
+    if ((r = B.p_bkla.ensure((size_t)n_runs * n_la))) return r;
+    if ((r = B.p_bkbf.ensure(nbf))) return r;
+    if ((r = B.p_bkbs.ensure(B.bk_cells))) return r;
+    if ((r = B.p_bkcnt.ensure(B.bk_cells))) return r;
+    if ((r = B.d_bkbs.ensure(B.bk_cells))) return r;
     memcpy(B.p_bkla, la, sizeof(double) * (size_t)n_runs * (size_t)n_la);
-    int nc = 0, o = 0, bfo = 0;
-    unsigned long long item0 = 0;
-    for (int i = 0; i < n_runs; i++) {
+    std::vector<int> bfo((size_t)n_runs);  // the runs' tables one after another in p_bkbf
+    for (int i = 0, o = 0; i < n_runs; i++) {
       const int a = c->h_chr_start[runs[i].chr], n = c->h_chr_n[runs[i].chr], nb = blk[i].nb;
       const int32_t* pos = c->h_pos.data() + a;
-      int32_t* bf = B.p_bkbf + bfo;
+      int32_t* bf = B.p_bkbf + o;
       bf[0] = a; bf[nb] = a + n;
       for (int j = 1; j < nb; j++) {  // (positions ascend within a chromosome; the bound as long long: no overflow)
         const long long lim = ((long long)blk[i].b0 + j) * (long long)blk[i].block_bp;
         bf[j] = a + (int)(std::lower_bound(pos, pos + n, lim, [](int32_t x, long long v) { return (long long)x < v; }) - pos);
       }
-      const int CH = list_chunk(BLK_CH, BLK_WAVES, nb);
-      for (int j = 0; j < runs[i].count; j += CH) {
-        const int cnt = std::min(CH, runs[i].count - j);
-        B.p_bkchunks[nc++] = BlkChunk{runs[i].chr, runs[i].start_pos + j * runs[i].step, runs[i].step, cnt, o, i, nb, bfo, item0, 0ull};
-        o += cnt;
-        item0 += (unsigned long long)cnt * (unsigned long long)nb;
-      }
-      bfo += nb + 1;
+      bfo[i] = o;
+      o += nb + 1;
     }
-    HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
-    Params P = make_params(c, B, slot, nc, 3, eval_range, 0);
-    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
-    hipLaunchKernelGGL(blocks_kernel, dim3(nc), dim3(64 * BLK_WAVES), 0, B.stream, P, (const BlkChunk*)B.p_bkchunks,
-                       (const double*)B.p_bkla, (const int32_t*)B.p_bkbf, n_la, B.p_bkbs, B.p_bkcnt, B.d_bkbs);
-    HIPCHK(hipGetLastError(), "launch blocks_kernel");
-    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+    unsigned long long item0 = 0;
+    const int nc = for_chunks(runs, n_runs, CH, [&](int i, int pos, int cnt, int o, int ch) {
+      B.p_bkchunks[ch] = BlkChunk{runs[i].chr, pos, runs[i].step, cnt, o, i, blk[i].nb, bfo[i], item0, 0ull};
+      item0 += (unsigned long long)cnt * (unsigned long long)blk[i].nb;
+    });
+    r = launch_bracket(c, B, nc, "launch blocks_kernel", [&](const Params& P) {
+      hipLaunchKernelGGL(blocks_kernel, dim3(nc), dim3(64 * BLK_WAVES), 0, B.stream, P, (const BlkChunk*)B.p_bkchunks,
+                         (const double*)B.p_bkla, (const int32_t*)B.p_bkbf, n_la, B.p_bkbs, B.p_bkcnt, B.d_bkbs);
+      return FSCLG_OK;
+    });
+    if (r) return r;
   }
-  B.holds = BK_BLOCKS;
-  c->slot[slot].users++;
-  return FSCLG_OK;
+  return batch_hold(c, B, BK_BLOCKS);
 }
 
 int fsclg_blocks_wait(fsclg_ctx* c, int batch, fsclg_point_t* pts, double* bs, uint32_t* cnt) {
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
   if (B.holds != BK_BLOCKS) return set_err(FSCLG_E_STATE, "no block sums submitted on the batch");
-  if ((!pts || !bs || !cnt) && B.bk_n) return set_err(FSCLG_E_ARG, "out");
-  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.holds = BK_NONE;
-  c->slot[B.slot].users--;
-  const int n = B.bk_n;
-  if (n == 0) return FSCLG_OK;
-  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  const int n = B.n_res;
+  if ((!pts || !bs || !cnt) && n) return set_err(FSCLG_E_ARG, "out");
+  int r;
+  if ((r = batch_finish(c, B, BK_BLOCKS, n > 0)) || n == 0) return r;
   memcpy(pts, B.p_out, sizeof(fsclg_point_t) * (size_t)n);
   memcpy(bs, B.p_bkbs, sizeof(double) * B.bk_cells);
   memcpy(cnt, B.p_bkcnt, sizeof(uint32_t) * B.bk_cells);
-  int r, flags = 0;
-  if ((r = batch_time(c, B, 1, &B.bk_ms))) return r;
-  for (int i = 0; i < n; i++) flags |= pts[i].flags;
-  return flags_err(flags);
+  return flags_err(pts, sizeof *pts, n);
 }
 
-double fsclg_blocks_last_ms(fsclg_ctx* c, int batch) {
-  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].bk_ms : 0.0;
-}
+double fsclg_blocks_last_ms(fsclg_ctx* c, int batch) { return last_ms(c, batch, BK_BLOCKS); }
 
 // ------------------------------------------------------------ per-site terms (host side)
 // terms per launch of sites_kernel's pass 1 = doubles of the pinned staging area.  Default 2^22
@@ -6180,8 +6076,8 @@ int fsclg_sites_submit(fsclg_ctx* c, int batch, int slot, const fsclg_site_req_t
     if (!(req[i].lalpha >= LOG_AD_MIN)) return set_err(FSCLG_E_ARG, "request lalpha below LOG_AD_MIN or NaN");
   }
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
-  B.eval_range = eval_range; B.bp_resl = 0; B.st_ms = 0.0; B.st_n = n_req; B.st_synced = false;
+  batch_reset(B, BK_SITES, slot, eval_range);
+  B.n_res = n_req;
   int r;
   if (n_req > 0) {
     {  // one covering cell per request
@@ -6190,30 +6086,26 @@ int fsclg_sites_submit(fsclg_ctx* c, int batch, int slot, const fsclg_site_req_t
       if ((r = cover_windows(c, B, slot, cover, eval_range))) return r;
     }
     if ((r = ensure_io(B, 1))) return r;  // (make_params' cells and points: unused by this kernel)
-    if ((r = ensure_pinned(&B.p_sreq, &B.sreq_cap, n_req))) return r;
-    if ((r = ensure_pinned(&B.p_shdr, &B.shdr_cap, n_req))) return r;
+    if ((r = B.p_sreq.ensure(n_req))) return r;
+    if ((r = B.p_shdr.ensure(n_req))) return r;
     memcpy(B.p_sreq, req, sizeof(fsclg_site_req_t) * (size_t)n_req);
-    HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
-    Params P = make_params(c, B, slot, n_req, 3, eval_range, 0);
-    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
-    hipLaunchKernelGGL(sites_kernel, dim3(n_req), dim3(WG), 0, B.stream, P, 0, (const fsclg_site_req_t*)B.p_sreq,
-                       B.p_shdr, (const SiteTask*)nullptr, (double*)nullptr);
-    HIPCHK(hipGetLastError(), "launch sites_kernel");
-    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+    r = launch_bracket(c, B, n_req, "launch sites_kernel", [&](const Params& P) {
+      hipLaunchKernelGGL(sites_kernel, dim3(n_req), dim3(WG), 0, B.stream, P, 0, (const fsclg_site_req_t*)B.p_sreq,
+                         B.p_shdr, (const SiteTask*)nullptr, (double*)nullptr);
+      return FSCLG_OK;
+    });
+    if (r) return r;
   }
-  B.holds = BK_SITES;
-  c->slot[slot].users++;
-  return FSCLG_OK;
+  return batch_hold(c, B, BK_SITES);
 }
 
 static int sites_wait_impl(fsclg_ctx* c, Batch& B, fsclg_site_hdr_t* hdr, double* terms) {
-  const int n = B.st_n;
+  const int n = B.n_res;
   const size_t cap = fsclg_sites_cap();
-  int r, flags = 0;
-  if ((r = ensure_pinned(&B.p_sterms, &B.sterm_cap, (int)cap))) return r;
-  for (int i = 0; i < n; i++) flags |= B.p_shdr[i].pt.flags;
+  int r;
+  if ((r = B.p_sterms.ensure(cap))) return r;
   memcpy(hdr, B.p_shdr, sizeof(fsclg_site_hdr_t) * (size_t)n);
-  if (flags) return flags_err(flags);
+  if ((r = flags_err(hdr, sizeof *hdr, n))) return r;  // (a header begins with its point)
   const Params P0 = make_params(c, B, B.slot, 0, 3, B.eval_range, 0);
   std::vector<SiteTask> tasks;
   int i = 0, k = 0;  // the next term: term k of walk i
@@ -6230,22 +6122,19 @@ static int sites_wait_impl(fsclg_ctx* c, Batch& B, fsclg_site_hdr_t* hdr, double
       k = k1;
     }
     if (tasks.empty()) break;
-    if ((r = ensure_pinned(&B.p_stasks, &B.stask_cap, (int)tasks.size()))) return r;
+    if ((r = B.p_stasks.ensure(tasks.size()))) return r;
     memcpy(B.p_stasks, tasks.data(), sizeof(SiteTask) * tasks.size());
-    Params P = P0;
-    P.n_cells = (int)tasks.size();
-    HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
-    hipLaunchKernelGGL(sites_kernel, dim3((unsigned)tasks.size()), dim3(WG), 0, B.stream, P, 1,
-                       (const fsclg_site_req_t*)nullptr, (fsclg_site_hdr_t*)nullptr, (const SiteTask*)B.p_stasks,
-                       B.p_sterms);
-    HIPCHK(hipGetLastError(), "launch sites_kernel");
-    HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+    r = launch_bracket(c, B, (int)tasks.size(), "launch sites_kernel", [&](const Params& P) {
+      hipLaunchKernelGGL(sites_kernel, dim3((unsigned)tasks.size()), dim3(WG), 0, B.stream, P, 1,
+                         (const fsclg_site_req_t*)nullptr, (fsclg_site_hdr_t*)nullptr, (const SiteTask*)B.p_stasks,
+                         B.p_sterms);
+      return FSCLG_OK;
+    }, &P0);
+    if (r) return r;
     HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
     memcpy(terms + done, B.p_sterms, sizeof(double) * fill);
     done += fill;
-    double ms = 0.0;
-    if ((r = batch_time(c, B, 1, &ms))) return r;
-    B.st_ms += ms;
+    if ((r = batch_time(c, B, 1, BK_SITES, true))) return r;
   }
   return FSCLG_OK;
 }
@@ -6254,7 +6143,7 @@ int fsclg_sites_wait(fsclg_ctx* c, int batch, fsclg_site_hdr_t* hdr, double* ter
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
   if (B.holds != BK_SITES) return set_err(FSCLG_E_STATE, "no site terms submitted on the batch");
-  const int n = B.st_n;
+  const int n = B.n_res;
   if (!hdr && n) return set_err(FSCLG_E_ARG, "hdr");  // (the batch stays submitted)
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   int r = FSCLG_OK;
@@ -6262,13 +6151,11 @@ int fsclg_sites_wait(fsclg_ctx* c, int batch, fsclg_site_hdr_t* hdr, double* ter
   if (n > 0 && !B.st_synced) {
     hipError_t e = hipEventSynchronize(B.ev1);
     if (e != hipSuccess) {  // the batch ends here
-      B.holds = BK_NONE; c->slot[B.slot].users--;
+      batch_release(c, B);
       return set_err(FSCLG_E_HIP, "hipEventSynchronize");
     }
     B.st_synced = true;
-    double ms = 0.0;
-    r = batch_time(c, B, 1, &ms);
-    B.st_ms += ms;
+    r = batch_time(c, B, 1, BK_SITES, true);
     uint64_t off = 0;  // the offsets: a running sum in request order
     for (int i = 0; i < n && r == FSCLG_OK; i++) { B.p_shdr[i].off = off; off += (uint64_t)B.p_shdr[i].len; }
   }
@@ -6277,14 +6164,11 @@ int fsclg_sites_wait(fsclg_ctx* c, int batch, fsclg_site_hdr_t* hdr, double* ter
   if (r == FSCLG_OK && (terms_cap < total || (!terms && total)))  // (the batch stays submitted)
     return set_err(FSCLG_E_ARG, "terms_cap below the walks' terms");
   if (r == FSCLG_OK && n > 0) r = sites_wait_impl(c, B, hdr, terms);
-  B.holds = BK_NONE;
-  c->slot[B.slot].users--;
+  batch_release(c, B);
   return r;
 }
 
-double fsclg_sites_last_ms(fsclg_ctx* c, int batch) {
-  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].st_ms : 0.0;
-}
+double fsclg_sites_last_ms(fsclg_ctx* c, int batch) { return last_ms(c, batch, BK_SITES); }
 
 // ------------------------------------------------------------ sweep-model sampler (host side)
 int fsclg_sample_tables(fsclg_ctx* c, const double* coef_t, const double* neutral, const int32_t* depth_n, int n_depths,
@@ -6353,16 +6237,10 @@ int fsclg_sample_submit(fsclg_ctx* c, int batch, const int32_t* depth_of_site, c
     if ((r = upload(&c->d_smp_chr, chr_of.data(), chr_of.size(), c->ustream))) return r;
     c->smp_chr_valid = true;
   }
-  if ((r = ensure_pinned(&B.p_sdepth, &B.sdepth_cap, n))) return r;
-  if ((r = ensure_pinned(&B.p_sfreq, &B.sfreq_cap, n))) return r;
-  if ((r = ensure_pinned(&B.p_ssweeps, &B.ssweep_cap, n_sweeps))) return r;
-  if (B.dsweep_cap < std::max(n_sweeps, 1)) {
-    if (B.d_sweeps) hipFree(B.d_sweeps);
-    B.d_sweeps = nullptr; B.dsweep_cap = 0;
-    const int k = std::max(n_sweeps, 64);
-    HIPCHK(hipMalloc((void**)&B.d_sweeps, sizeof(fsclg_sweep_t) * (size_t)k), "hipMalloc sweeps");
-    B.dsweep_cap = k;
-  }
+  if ((r = B.p_sdepth.ensure(n))) return r;
+  if ((r = B.p_sfreq.ensure(n))) return r;
+  if ((r = B.p_ssweeps.ensure(n_sweeps))) return r;
+  if ((r = B.d_sweeps.ensure(std::max(n_sweeps, 1), "hipMalloc sweeps"))) return r;  // (never NULL)
   memcpy(B.p_sdepth, depth_of_site, sizeof(int32_t) * (size_t)n);
   if (n_sweeps) {
     memcpy(B.p_ssweeps, sweeps, sizeof(fsclg_sweep_t) * (size_t)n_sweeps);
@@ -6380,14 +6258,13 @@ int fsclg_sample_submit(fsclg_ctx* c, int batch, const int32_t* depth_of_site, c
   int nw = SAMPLE_WAVES;
   while (nw > 1 && (size_t)nw * (size_t)c->smp_max_m * 8 > 65536) nw >>= 1;
   const size_t lds = (size_t)nw * (size_t)c->smp_max_m * 8;
-  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = -1; B.ivhist = nullptr; B.traced = false;
-  B.sm_n = n; B.sm_ms = 0.0;
+  batch_reset(B, BK_SAMPLE, -1);
+  B.n_res = n;
   HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
   hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((n + nw - 1) / nw)), dim3(64 * nw), lds, B.stream, P);
   HIPCHK(hipGetLastError(), "launch sample_kernel");
   HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
-  B.holds = BK_SAMPLE;
-  return FSCLG_OK;
+  return batch_hold(c, B, BK_SAMPLE);
 }
 
 int fsclg_sample_wait(fsclg_ctx* c, int batch, int32_t* freq_out, unsigned long long* n_degenerate) {
@@ -6395,13 +6272,10 @@ int fsclg_sample_wait(fsclg_ctx* c, int batch, int32_t* freq_out, unsigned long 
   Batch& B = c->batch[batch];
   if (B.holds != BK_SAMPLE) return set_err(FSCLG_E_STATE, "no sample submitted on the batch");
   if (!freq_out) return set_err(FSCLG_E_ARG, "freq_out");  // (the batch stays submitted)
-  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.holds = BK_NONE;
-  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
   int r;
-  if ((r = batch_time(c, B, 1, &B.sm_ms))) return r;
+  if ((r = batch_finish(c, B, BK_SAMPLE, true))) return r;
   unsigned long long deg = 0;
-  for (int i = 0; i < B.sm_n; i++) {
+  for (int i = 0; i < B.n_res; i++) {
     freq_out[i] = B.p_sfreq[i];
     deg += B.p_sfreq[i] < 0;
   }
@@ -6409,9 +6283,7 @@ int fsclg_sample_wait(fsclg_ctx* c, int batch, int32_t* freq_out, unsigned long 
   return FSCLG_OK;
 }
 
-double fsclg_sample_last_ms(fsclg_ctx* c, int batch) {
-  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].sm_ms : 0.0;
-}
+double fsclg_sample_last_ms(fsclg_ctx* c, int batch) { return last_ms(c, batch, BK_SAMPLE); }
 
 // ------------------------------------------------------------ projected tail (host side)
 int fsclg_tail_submit(fsclg_ctx* c, int batch, const float* samples, size_t n_samples, const unsigned long long* offsets,
@@ -6428,18 +6300,12 @@ int fsclg_tail_submit(fsclg_ctx* c, int batch, const float* samples, size_t n_sa
       return set_err(FSCLG_E_ARG, "tail: a point's samples lie outside the array");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   int r;
-  if ((r = ensure_pinned(&B.p_tsamples, &B.tsamp_cap, (int)n_samples))) return r;
-  if ((r = ensure_pinned(&B.p_toff, &B.toff_cap, n_points))) return r;
-  if ((r = ensure_pinned(&B.p_tcnt, &B.tcnt_cap, n_points))) return r;
-  if ((r = ensure_pinned(&B.p_tx0, &B.tx0_cap, n_points))) return r;
-  if ((r = ensure_pinned(&B.p_tout, &B.tout_cap, n_points))) return r;
-  if (B.dtsamp_cap < std::max(n_samples, (size_t)1)) {
-    if (B.d_tsamples) hipFree(B.d_tsamples);
-    B.d_tsamples = nullptr; B.dtsamp_cap = 0;
-    const size_t k = std::max(n_samples, (size_t)1024);
-    HIPCHK(hipMalloc((void**)&B.d_tsamples, sizeof(float) * k), "hipMalloc tail samples");
-    B.dtsamp_cap = k;
-  }
+  if ((r = B.p_tsamples.ensure(n_samples))) return r;
+  if ((r = B.p_toff.ensure(n_points))) return r;
+  if ((r = B.p_tcnt.ensure(n_points))) return r;
+  if ((r = B.p_tx0.ensure(n_points))) return r;
+  if ((r = B.p_tout.ensure(n_points))) return r;
+  if ((r = B.d_tsamples.ensure(std::max(n_samples, (size_t)1), "hipMalloc tail samples"))) return r;  // (never NULL)
   if (n_samples) {
     memcpy(B.p_tsamples, samples, sizeof(float) * n_samples);
     HIPCHK(hipMemcpyAsync(B.d_tsamples, B.p_tsamples, sizeof(float) * n_samples, hipMemcpyHostToDevice, B.stream),
@@ -6453,8 +6319,8 @@ int fsclg_tail_submit(fsclg_ctx* c, int batch, const float* samples, size_t n_sa
   TailParams P;
   P.samples = B.d_tsamples; P.off = B.p_toff; P.cnt = B.p_tcnt; P.x0 = B.p_tx0; P.out = B.p_tout;
   P.n_points = n_points; P.h = df / 2; P.min_n = min_n;
-  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = -1; B.ivhist = nullptr; B.traced = false;
-  B.tl_n = n_points; B.tl_ms = 0.0;
+  batch_reset(B, BK_TAIL, -1);
+  B.n_res = n_points;
   HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
   if (n_points) {
     hipLaunchKernelGGL(tail_kernel, dim3((unsigned)((n_points + TAIL_WAVES - 1) / TAIL_WAVES)), dim3(64 * TAIL_WAVES), 0,
@@ -6462,27 +6328,21 @@ int fsclg_tail_submit(fsclg_ctx* c, int batch, const float* samples, size_t n_sa
     HIPCHK(hipGetLastError(), "launch tail_kernel");
   }
   HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
-  B.holds = BK_TAIL;
-  return FSCLG_OK;
+  return batch_hold(c, B, BK_TAIL);
 }
 
 int fsclg_tail_wait(fsclg_ctx* c, int batch, fsclg_tail_t* out) {
   if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
   Batch& B = c->batch[batch];
   if (B.holds != BK_TAIL) return set_err(FSCLG_E_STATE, "no tail fit submitted on the batch");
-  if (!out && B.tl_n) return set_err(FSCLG_E_ARG, "out");  // (the batch stays submitted)
-  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
-  B.holds = BK_NONE;
-  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  if (!out && B.n_res) return set_err(FSCLG_E_ARG, "out");  // (the batch stays submitted)
   int r;
-  if ((r = batch_time(c, B, 1, &B.tl_ms))) return r;
-  if (B.tl_n) memcpy(out, B.p_tout, sizeof(fsclg_tail_t) * (size_t)B.tl_n);
+  if ((r = batch_finish(c, B, BK_TAIL, true))) return r;  // (the events are recorded around no launch too)
+  if (B.n_res) memcpy(out, B.p_tout, sizeof(fsclg_tail_t) * (size_t)B.n_res);
   return FSCLG_OK;
 }
 
-double fsclg_tail_last_ms(fsclg_ctx* c, int batch) {
-  return c && batch >= 0 && batch < NBATCH ? c->batch[batch].tl_ms : 0.0;
-}
+double fsclg_tail_last_ms(fsclg_ctx* c, int batch) { return last_ms(c, batch, BK_TAIL); }
 
 int fsclg_interval_thresholds(double log_ad_step, int n_iv, double* thr) {
   if (!thr || n_iv <= 0 || !(log_ad_step > 0)) return set_err(FSCLG_E_ARG, "thresholds");

@@ -33,6 +33,8 @@ __all__ = [
     "curve_forced", "CURVE_DTYPE",
     "scan_sites", "scan_point_sites", "sites_summary", "sites_output", "sites_last_ms", "sites_cap", "SitesT",
     "SITES_DTYPE", "SITE_REQ_DTYPE", "SITES_SUMMARY_DTYPE",
+    "scan_expect", "scan_point_expect", "expect_output", "expect_last_ms", "expect_runs", "ExpectT", "EXPECT_DTYPE",
+    "EXPECT_SITE_DTYPE",
     "simulate", "simulate_scan", "simulate_output", "simulate_last_ms", "scan_free", "bootstrap", "bootstrap_output",
     "bootstrap_times", "parse_sweep", "nearest_sweep", "SWEEP_DTYPE", "BOOT_DTYPE",
     "tail_fit", "tail_runs", "tail_output", "tail_last_ms", "tail_summary", "tail_records", "TAIL_DTYPE", "TAIL_FLAGS",
@@ -109,6 +111,12 @@ class ProfileT(C.Structure):  # fscl_amd_profile_t
 
 class RunT(C.Structure):  # fsclg_run_t
     _fields_ = [("chr", C.c_int32), ("start_pos", C.c_int32), ("step", C.c_int32), ("count", C.c_int32)]
+
+
+class ExpectT(C.Structure):  # fscl_amd_expect_t
+    _fields_ = [("n", C.c_int), ("n_tasks", C.c_int), ("n_bins", C.c_int), ("req", C.c_void_p), ("first", C.c_void_p),
+                ("own", C.c_void_p), ("la", C.c_void_p), ("hdr", C.c_void_p), ("tot", C.c_void_p), ("point", C.c_void_p),
+                ("kernel_ms", C.c_double)]
 
 
 class SitesT(C.Structure):  # fscl_amd_sites_t
@@ -192,6 +200,10 @@ EXPORTS = [
     "fscl_amd_cond_clip", "fscl_amd_cond_given_terms", "fscl_amd_cond_base", "fscl_amd_conditional_cap",
     "fscl_amd_conditional_error", "fscl_amd_conditional_check", "fscl_amd_scan_conditional", "fscl_amd_conditional_output", "fscl_amd_conditional_free",
     "fscl_amd_conditional_last_ms", "fscl_amd_cond_runs",
+    "fsclg_expect_tables", "fsclg_expect_submit", "fsclg_expect_count", "fsclg_expect_wait", "fsclg_expect_last_ms",
+    "fscl_amd_scan_expect", "fscl_amd_scan_point_expect", "fscl_amd_expect_runs", "fscl_amd_expect_check",
+    "fscl_amd_expect_error", "fscl_amd_expect_cap", "fscl_amd_expect_bin", "fscl_amd_expect_tables_build",
+    "fscl_amd_expect_output", "fscl_amd_expect_free", "fscl_amd_expect_last_ms",
 ]
 
 
@@ -321,6 +333,19 @@ def _load() -> C.CDLL:
         "fscl_amd_conditional_last_ms": (C.c_double, []),
         "fscl_amd_cond_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(RunT), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+        "fscl_amd_scan_expect": (C.c_int, [P(ScanT), P(SmPtableT), P(P(C.c_double)), C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_int, C.c_int, P(ExpectT)]),
+        "fscl_amd_scan_point_expect": (C.c_int, [P(ScanT), P(SmPtableT), P(P(C.c_double)), C.c_int, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_int, C.c_int, P(ExpectT)]),
+        "fscl_amd_expect_runs": (C.c_int, [P(ScanT), P(SmPtableT), P(P(C.c_double)), C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, P(C.c_void_p), P(C.c_size_t)]),
+        "fscl_amd_expect_check": (C.c_int, [P(ScanT), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+        "fscl_amd_expect_error": (C.c_char_p, []),
+        "fscl_amd_expect_cap": (C.c_size_t, []),
+        "fscl_amd_expect_bin": (C.c_int, [C.c_double, C.c_int]),
+        "fscl_amd_expect_output": (C.c_int, [C.c_char_p, P(ScanT), P(ExpectT), C.c_char_p]),
+        "fscl_amd_expect_free": (None, [P(ExpectT)]),
+        "fscl_amd_expect_last_ms": (C.c_double, []),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -742,6 +767,122 @@ def scan_point_sites(scan, tables, top: int = 10, eval_range: int = 81920):
     _curve_check(get_lib().fscl_amd_scan_point_sites(scan, tables, int(eval_range), int(top), C.byref(res)),
                  "fscl_amd_scan_point_sites")
     return _sites_take(res)
+
+
+# fsclg_expect_site_t: one site of a walk -- its index, 1 if degenerate, x = logt(|d|) + log alpha, the observed
+# term, the first two moments of the term under the sweep and under neutrality, the probability lost to
+# unusable classes (include/fsclg.h)
+EXPECT_SITE_DTYPE = np.dtype([("site", "i4"), ("degenerate", "i2"), ("bin", "i2"), ("x", "f8"), ("obs", "f8"), ("m1_s", "f8"),
+                              ("m2_s", "f8"), ("m1_0", "f8"), ("m2_0", "f8"), ("lost_s", "f8"), ("lost_0", "f8")])
+# fsclg_expect_tot_t: the totals of a walk's sites in one bin (or in all): sums of log-likelihood terms
+EXPECT_DTYPE = np.dtype([("n_sites", "u4"), ("n_degenerate", "u4"), ("obs", "f8"), ("e_s", "f8"), ("v_s", "f8"),
+                         ("e_0", "f8"), ("v_0", "f8"), ("max_lost_s", "f8"), ("max_lost_0", "f8")])
+assert EXPECT_SITE_DTYPE.itemsize == 72 and EXPECT_DTYPE.itemsize == 64
+
+
+def _expect_check(r: int, what: str) -> None:
+    if r != 0:
+        msg = get_lib().fscl_amd_expect_error() or get_lib().fsclg_last_error() or b""
+        raise ValueError(f"{what} failed (code {r}): {msg.decode()}") if r == -1 else RuntimeError(
+            f"{what} failed (code {r}): {msg.decode()}")
+
+
+def _expect_take(res: ExpectT) -> dict:
+    n, nt, nb = int(res.n), int(res.n_tasks), int(res.n_bins)
+    out = {"n_bins": nb, "kernel_ms": float(res.kernel_ms), "evaluated": bool(res.hdr),
+           "req": np.zeros(n, dtype=SITE_REQ_DTYPE), "first": np.zeros(n + 1, dtype=np.int32),
+           "own": np.zeros(n, dtype=np.int32), "la": np.zeros(nt, dtype=np.float64),
+           "hdr": np.zeros(nt, dtype=SITES_DTYPE), "tot": np.zeros((nt, nb + 1), dtype=EXPECT_DTYPE),
+           "point": None}
+    if res.hdr:
+        for key, ptr in (("req", res.req), ("first", res.first), ("own", res.own), ("la", res.la), ("hdr", res.hdr),
+                         ("tot", res.tot)):
+            if out[key].nbytes:
+                C.memmove(out[key].ctypes.data, ptr, out[key].nbytes)
+        if res.point:
+            out["point"] = np.zeros(n, dtype=np.int32)
+            if n:
+                C.memmove(out["point"].ctypes.data, res.point, 4 * n)
+    return out
+
+
+def _expect_res(d: dict):
+    res = ExpectT()
+    keep = {k: np.ascontiguousarray(d[k]) for k in ("req", "first", "own", "la", "hdr", "tot")}
+    res.n, res.n_tasks, res.n_bins = len(keep["req"]), len(keep["la"]), int(d["n_bins"])
+    for k, a in keep.items():
+        setattr(res, k, a.ctypes.data)
+    return res, keep
+
+
+def scan_expect(scan, tables, fsp, requests, alphas, n_bins: int = 24, eval_range: int = 81920) -> dict:
+    """The expected terms under the model (include/fscl_amd.h, --expect-file) of one sweep per (chromosome
+    index, position, log alpha) of ``requests``: each at the ascending log alphas ``alphas`` with its own inserted
+    in order.  A dict: ``first`` / ``own`` index the tasks of a request, ``la`` their log alphas, ``hdr`` their
+    walks (SITES_DTYPE), ``tot[task, b]`` (EXPECT_DTYPE) the totals of bin b, ``tot[task, n_bins]`` of the walk."""
+    req = np.zeros(len(requests), dtype=SITE_REQ_DTYPE)
+    for q, r in zip(req, requests):
+        q["chr"], q["pos"], q["lalpha"] = int(r[0]), int(r[1]), float(r[2])
+    la = np.ascontiguousarray(alphas, dtype=np.float64)
+    res = ExpectT()
+    _expect_check(get_lib().fscl_amd_scan_expect(scan, tables, fsp, int(eval_range), req.ctypes.data if len(req) else None,
+                                                 len(req), la.ctypes.data if len(la) else None, len(la), int(n_bins),
+                                                 C.byref(res)), "fscl_amd_scan_expect")
+    out = _expect_take(res)
+    get_lib().fscl_amd_expect_free(C.byref(res))
+    return out
+
+
+def scan_point_expect(scan, tables, fsp, alphas, top: int = 3, spacing: int = 100000, n_bins: int = 24,
+                      eval_range: int = 81920) -> dict:
+    """scan_expect at the ``top`` scan points of greatest CLR at their fitted alpha, none within ``spacing`` bp of
+    one already taken; ``point`` holds each request's scan point."""
+    la = np.ascontiguousarray(alphas, dtype=np.float64)
+    res = ExpectT()
+    _expect_check(get_lib().fscl_amd_scan_point_expect(scan, tables, fsp, int(eval_range), int(top), int(spacing),
+                                                       la.ctypes.data if len(la) else None, len(la), int(n_bins),
+                                                       C.byref(res)), "fscl_amd_scan_point_expect")
+    out = _expect_take(res)
+    get_lib().fscl_amd_expect_free(C.byref(res))
+    return out
+
+
+def expect_output(path, scan, result: dict, label=None) -> None:
+    """The --expect-file format (include/fscl_amd.h, README) of a scan_expect result."""
+    res, keep = _expect_res(result)
+    if get_lib().fscl_amd_expect_output(_b(path), scan, C.byref(res), _b(label)) != 0:
+        raise OSError(f"cannot write {path}")
+    del keep
+
+
+def expect_last_ms() -> float:
+    return float(get_lib().fscl_amd_expect_last_ms())
+
+
+def expect_runs(scan, tables, fsp, requests, alphas, n_bins: int = 24, eval_range: int = 81920, batch: int = 0):
+    """The raw handle of fsclg_expect_submit / fsclg_expect_wait on the first device: ``alphas`` is one list of log
+    alphas per request, all of one length.  (totals [task, n_bins + 1], headers [task], site records), the tasks
+    request-major, the site records task after task (hdr["off"], hdr["len"])."""
+    req = np.zeros(len(requests), dtype=SITE_REQ_DTYPE)
+    for q, r in zip(req, requests):
+        q["chr"], q["pos"], q["lalpha"] = int(r[0]), int(r[1]), float(r[2])
+    la = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(req), -1)
+    n_la = la.shape[1]
+    nt = len(req) * n_la
+    tot = np.zeros((nt, int(n_bins) + 1), dtype=EXPECT_DTYPE)
+    hdr = np.zeros(nt, dtype=SITES_DTYPE)
+    ptr, ns = C.c_void_p(), C.c_size_t()
+    r = get_lib().fscl_amd_expect_runs(scan, tables, fsp, req.ctypes.data if len(req) else None, len(req),
+                                       la.ctypes.data if la.size else None, n_la, int(n_bins), int(eval_range), int(batch),
+                                       tot.ctypes.data, hdr.ctypes.data, C.byref(ptr), C.byref(ns))
+    if r != 0:
+        raise (ValueError if r == -1 else RuntimeError)(
+            f"fscl_amd_expect_runs failed (code {r}): {(get_lib().fsclg_last_error() or b'').decode()}")
+    sites = np.zeros(ns.value, dtype=EXPECT_SITE_DTYPE)
+    if ns.value:
+        C.memmove(sites.ctypes.data, ptr, sites.nbytes)
+    _libc_free(ptr)
+    return tot, hdr, sites
 
 
 def _sites_view(hdr, terms):
@@ -1540,7 +1681,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         surface_step=None, surface_alphas=(LOG_AD_MIN, LOG_AD_MAX, 33), surface_drop=2.0,
         jackknife_file=None, jackknife_top=3, jackknife_block=None, jackknife_halfwidth=None, jackknife_step=None,
         jackknife_alphas=None, conditional_file=None, given_sweeps=(), conditional_halfwidth=0, conditional_step=None,
-        conditional_alphas=None, conditional_rounds=1, conditional_min_clr=0.0):
+        conditional_alphas=None, conditional_rounds=1, conditional_min_clr=0.0,
+        expect_file=None, expect_top=3, expect_sweeps=(), expect_alphas=None, expect_bins=24):
     """The fscl main() pipeline (fscl.c:316-337) in-process; returns the scan_t
     pointer (points(scan) reads the results).  permute_mode "throughput": the
     counter-based permutation test (set_permute_mode).  scan_mode "grid": the CLI's
@@ -1583,6 +1725,13 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         if int(conditional_halfwidth) < 0 or not 1 <= int(conditional_rounds) <= COND_MAX_ROUNDS:
             raise ValueError("conditional_halfwidth must be >= 0 and conditional_rounds 1 .. 8")
         _surface_grid(*conditional_alphas)  # (raises ValueError)
+    if expect_file is None and (expect_sweeps or expect_alphas is not None or expect_top != 3 or expect_bins != 24):
+        raise ValueError("expect_sweeps, expect_top, expect_alphas and expect_bins need expect_file")
+    if expect_file is not None:
+        expect_alphas = surface_alphas if expect_alphas is None else expect_alphas
+        if int(expect_top) < 0 or not 1 <= int(expect_bins) <= 64:
+            raise ValueError("expect_top must be >= 0 and expect_bins 1 .. 64")
+        _surface_grid(*expect_alphas)  # (raises ValueError)
     if tail_file is not None:
         _tail_df(tail_df)
         if int(n_permute) <= 0:
@@ -1637,6 +1786,12 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
                            scan_conditional(scan, tab, given, conditional_halfwidth, conditional_step,
                                             _surface_grid(*conditional_alphas), conditional_rounds, conditional_min_clr,
                                             eval_range), label)
+    if expect_file is not None:  # the CLI's --expect-file: what the model expects at the sweeps
+        grid = _surface_grid(*expect_alphas)
+        sw = [as_sweep(w) for w in expect_sweeps]
+        res = (scan_expect(scan, tab, fsp, [(c, q, math.log(a)) for c, q, a in sw], grid, expect_bins, eval_range) if sw else
+               scan_point_expect(scan, tab, fsp, grid, expect_top, large_grid_sp, expect_bins, eval_range))
+        expect_output(expect_file, scan, res, label)
     if n_permute > 0 and scan_mode == "grid":
         scan_permute_grid(scan, tab, n_permute, permute_nbp, eval_range, small_grid_sp, large_grid_sp, scan_width_mb)
     elif n_permute > 0:

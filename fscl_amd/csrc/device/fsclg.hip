@@ -3061,6 +3061,158 @@ sample_kernel(SampleParams P) {
   if (lane == 0) P.out[i] = f_out;
 }
 
+// ------------------------------------------------------------ expected terms under the model
+// The moments of a site's term over the model spectrum (fsclg_expect_submit).  Phase 0, one wave per
+// (task, site), EXPECT_WAVES per workgroup, blockIdx.y the task: the site's set-up -- x = logt(|d|) +
+// lalpha, the interval with sample_kernel's clamp, its depth and folding from the class of its device
+// row, its observed term by term_dev -- is the same in every lane.  Lane l of trip j has f = 1 + 64 j +
+// l and reads the 32-byte record (interval, f) of the sampler's interval-major table, consecutive lanes
+// consecutive records; on a folded site it reads the record (interval, min(f, n - f)) of the folded
+// table as well.  A lane adds its classes in ascending f from +0.0; the 64 lane sums meet in an xor
+// butterfly (lane distances 32 .. 1: every lane ends with the same bits) and lane 0 stores the site's
+// record in device memory.  Phase 1, one workgroup per task: thread b < n_bins folds the sites of bin b,
+// thread n_bins all of them, in ascending site index from +0.0, EXPECT_STAGE records at a time through
+// LDS, and stores its total with plain vector stores (host memory).  No exponential but the spectrum's,
+// no log, no atomic.
+constexpr int EXPECT_WAVES = 4;
+constexpr int EXPECT_MAX_LA = 64, EXPECT_MAX_BINS = 64, EXPECT_MAX_TASKS = 65535;
+constexpr int EXPECT_FOLD_WG = 128;  // >= EXPECT_MAX_BINS + 1 threads
+constexpr int EXPECT_STAGE = 64;
+static_assert(EXPECT_FOLD_WG > EXPECT_MAX_BINS, "one thread per bin and one for the total");
+struct ExpectDepth {
+  int32_t n, pad;
+  unsigned long long coef_off;   // doubles from ExpectParams::coef_u to the depth's [interval][f][4] (the sampler's)
+  unsigned long long fold_off;   // doubles from ExpectParams::coef_f to the depth's [interval][c][4]
+  unsigned long long unf_off;    // doubles from neutral / null_u to the depth's n - 1 entries
+  unsigned long long nf_off;     // doubles from null_f to the depth's n / 2 entries
+};
+struct ExpectTask {
+  int32_t i0, len, sweep, pad;   // the walk's sites [i0, i0 + len), its de-collided sweep position
+  double la;
+  unsigned long long rec;        // index of the task's first site record
+};
+struct ExpectParams {
+  const double* coef_u;
+  const double* coef_f;
+  const double* neutral;
+  const double* null_u;
+  const double* null_f;
+  const ExpectDepth* depth;
+  const uint32_t* row_class;     // [n_rows]: depth index, bit 31: folded
+  const ExpectTask* tasks;       // (host memory)
+  fsclg_expect_site_t* rec;      // (device memory)
+  fsclg_expect_tot_t* tot;       // [n_tasks][n_bins + 1] (host memory)
+  int n_tasks, n_bins, n_rows, pad;
+};
+
+__device__ __forceinline__ double expect_clean(double v) {  // not finite or not positive: 0
+  return v > 0.0 && v <= 1.7976931348623157e308 ? v : 0.0;
+}
+
+__global__ void __launch_bounds__(64 * EXPECT_WAVES)
+expect_kernel(Params P, ExpectParams E, int phase) {
+  const int task = (int)blockIdx.y;
+  if (task >= E.n_tasks) return;
+  const ExpectTask T = E.tasks[task];
+  if (phase == 1) {
+    __shared__ fsclg_expect_site_t st[EXPECT_STAGE];
+    const int b = (int)threadIdx.x;
+    const bool mine = b <= E.n_bins;
+    fsclg_expect_tot_t o;
+    o.n_sites = 0; o.n_degenerate = 0;
+    o.obs = 0.0; o.e_s = 0.0; o.v_s = 0.0; o.e_0 = 0.0; o.v_0 = 0.0; o.max_lost_s = 0.0; o.max_lost_0 = 0.0;
+    for (int j0 = 0; j0 < T.len; j0 += EXPECT_STAGE) {
+      const int cnt = min(EXPECT_STAGE, T.len - j0);
+      __syncthreads();
+      {  // the records as 8-byte words, consecutive threads consecutive words
+        const unsigned long long* __restrict__ src = reinterpret_cast<const unsigned long long*>(E.rec + T.rec + j0);
+        unsigned long long* dst = reinterpret_cast<unsigned long long*>(st);
+        const int nw = cnt * (int)(sizeof(fsclg_expect_site_t) / 8);
+        for (int w = (int)threadIdx.x; w < nw; w += (int)blockDim.x) dst[w] = src[w];
+      }
+      __syncthreads();
+      if (mine)
+        for (int j = 0; j < cnt; j++) {
+          const fsclg_expect_site_t& s = st[j];
+          if (b != E.n_bins && b != (int)s.bin) continue;  // (phase 0 stored the site's bin)
+          o.n_sites++;
+          o.obs += s.obs;
+          if (s.degenerate) { o.n_degenerate++; continue; }
+          o.e_s += s.m1_s; o.v_s += fmax(s.m2_s - s.m1_s * s.m1_s, 0.0);
+          o.e_0 += s.m1_0; o.v_0 += fmax(s.m2_0 - s.m1_0 * s.m1_0, 0.0);
+          o.max_lost_s = fmax(o.max_lost_s, s.lost_s);
+          o.max_lost_0 = fmax(o.max_lost_0, s.lost_0);
+        }
+    }
+    if (mine) E.tot[(size_t)task * (size_t)(E.n_bins + 1) + b] = o;
+    return;
+  }
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int j = (int)blockIdx.x * EXPECT_WAVES + wave;
+  if (j >= T.len) return;
+  const int i = T.i0 + j;
+  const uint32_t drow = P.pr[phys((uint32_t)i)].y;  // device row = the caller's row + 1
+  const double x = log_ad_of(i, T.sweep, T.la, P);
+  fsclg_expect_site_t o;
+  o.site = i; o.degenerate = 1;
+  {  // the site's bin of x: n_bins equal-width bins of [LOG_AD_MIN, LOG_AD_MAX], x below the range in bin 0
+    const int sb = (int)(((x - LOG_AD_MIN) * (double)E.n_bins) / (LOG_AD_MAX - LOG_AD_MIN));
+    o.bin = (int16_t)(!(x >= LOG_AD_MIN) ? 0 : min(sb, E.n_bins - 1));
+  }
+  o.x = x; o.obs = term_dev<false>(i, T.sweep, T.la, 0, P);
+  o.m1_s = 0.0; o.m2_s = 0.0; o.m1_0 = 0.0; o.m2_0 = 0.0; o.lost_s = 0.0; o.lost_0 = 0.0;
+  if (drow >= 1u && drow <= (uint32_t)E.n_rows) {
+    const uint32_t cls = E.row_class[drow - 1];
+    const bool folded = (cls >> 31) != 0;
+    const ExpectDepth D = E.depth[cls & 0x7fffffffu];
+    const int n = D.n, m = n - 1, nh = n >> 1;
+    int iv = (int)__builtin_fma(x, P.inv_step, P.iv_off);  // sample_kernel's interval, clamped to 0 below LOG_AD_MIN
+    iv = max(0, min(iv, P.n_iv - 1));
+    iv += x >= P.thr[iv + 1] ? 1 : 0;
+    const double* __restrict__ rowu = E.coef_u + D.coef_off + (size_t)iv * (size_t)m * 4;
+    const double* __restrict__ rowf = E.coef_f + D.fold_off + (size_t)iv * (size_t)nh * 4;
+    const double* __restrict__ neut = E.neutral + D.unf_off;
+    const double* __restrict__ nul = folded ? E.null_f + D.nf_off : E.null_u + D.unf_off;
+    double S = 0.0, Q = 0.0, Su = 0.0, Qu = 0.0, a1 = 0.0, a2 = 0.0, b1 = 0.0, b2 = 0.0;
+    for (int f = 1 + lane; f <= m; f += 64) {
+      const double2 ca = *reinterpret_cast<const double2*>(rowu + (size_t)(f - 1) * 4);
+      const double2 cb = *reinterpret_cast<const double2*>(rowu + (size_t)(f - 1) * 4 + 2);
+      const double y = x * (ca.x * x * x + ca.y * x + cb.x) + cb.y;
+      const double p = expect_clean(exp(y));
+      const double q = expect_clean(neut[f - 1]);
+      double t;
+      if (folded) {
+        const int cc = min(f, n - f);
+        const double2 fa = *reinterpret_cast<const double2*>(rowf + (size_t)(cc - 1) * 4);
+        const double2 fb = *reinterpret_cast<const double2*>(rowf + (size_t)(cc - 1) * 4 + 2);
+        t = x * (fa.x * x * x + fa.y * x + fb.x) + fb.y - nul[cc - 1];
+      } else {
+        t = y - nul[f - 1];
+      }
+      S += p; Q += q;
+      if (p > 0.0 && q > 0.0 && fabs(t) <= 1.7976931348623157e308) {
+        Su += p; Qu += q;
+        a1 += p * t; a2 += p * t * t;
+        b1 += q * t; b2 += q * t * t;
+      }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      S += __shfl_xor(S, d, 64); Q += __shfl_xor(Q, d, 64);
+      Su += __shfl_xor(Su, d, 64); Qu += __shfl_xor(Qu, d, 64);
+      a1 += __shfl_xor(a1, d, 64); a2 += __shfl_xor(a2, d, 64);
+      b1 += __shfl_xor(b1, d, 64); b2 += __shfl_xor(b2, d, 64);
+    }
+    auto good = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };
+    if (good(S) && good(Q) && good(Su) && good(Qu)) {
+      o.degenerate = 0;
+      o.m1_s = a1 / Su; o.m2_s = a2 / Su; o.m1_0 = b1 / Qu; o.m2_0 = b2 / Qu;
+      o.lost_s = 1.0 - Su / S; o.lost_0 = 1.0 - Qu / Q;
+    }
+  }
+  if (lane == 0) E.rec[T.rec + (unsigned long long)j] = o;
+}
+
 // ------------------------------------------------------------ projected tail
 // A noncentral chi-square fit of every point's null record and its upper tail at the observed
 // value (fsclg_tail_submit).  One wave per point, TAIL_WAVES points per workgroup; the waves share
@@ -3836,10 +3988,10 @@ struct Slot {
 
 // what a batch holds between a submit and its wait
 enum BatchKind { BK_NONE, BK_SEARCH, BK_PROFILE, BK_CELLMAX, BK_CURVE, BK_SITES, BK_SAMPLE, BK_TAIL, BK_SURFACE,
-                 BK_BLOCKS, BK_COND, BK_COUNT };
+                 BK_BLOCKS, BK_COND, BK_EXPECT, BK_COUNT };
 
 // One call of any kind in flight (a submit / wait pair: search, profile, cell maxima, curves, site
-// terms, sample, tail fit, surface, block sums, conditional scan): its stream and events, the state
+// terms, sample, tail fit, surface, block sums, conditional scan, expected terms): its stream and events, the state
 // every kind shares (what it holds, on which slot, how many results, each kind's last kernel time),
 // a search's host-side dedup / ordering of its cells, and the buffers of each kind.  A kind adds its
 // buffers here and nothing else: the protocol is batch_reset / launch_bracket / batch_hold in its
@@ -3915,6 +4067,13 @@ struct Batch {
   Buf<uint32_t, PINNED> p_bkcnt;
   Buf<double, DEVICE> d_bkbs;
   size_t bk_cells = 0;              // the (position, block, alpha) cells of the submitted block sums
+  // fsclg_expect_submit: the walks' requests and headers are p_sreq and p_shdr (sites_kernel's pass 0); the
+  // tasks (read by expect_kernel), the site records (device memory) and the totals (written by the kernel)
+  Buf<ExpectTask, PINNED> p_xtasks;
+  Buf<fsclg_expect_site_t, DEVICE> d_xrec;
+  Buf<fsclg_expect_tot_t, PINNED> p_xtot;
+  int x_nbins = 0;                  // bins of the submitted call
+  size_t x_sites = 0;               // its (task, site) pairs, known once the headers are in (st_synced)
 };
 
 struct fsclg_ctx {
@@ -3937,6 +4096,15 @@ struct fsclg_ctx {
   int32_t* d_smp_chr = nullptr;
   bool smp_chr_valid = false;
   int smp_n_depths = 0, smp_max_m = 0, smp_n_iv = 0;
+  std::vector<int32_t> smp_depth_n;  // the sampler's depths (fsclg_expect_tables checks its own against them)
+  // fsclg_expect_tables: the folded rows, the neutral spectra, the null values, the depths, the rows' classes
+  double* d_exp_fcoef = nullptr;
+  double* d_exp_neutral = nullptr;
+  double* d_exp_null_u = nullptr;
+  double* d_exp_null_f = nullptr;
+  ExpectDepth* d_exp_depth = nullptr;
+  uint32_t* d_exp_class = nullptr;
+  int exp_n_depths = 0, exp_n_rows = 0;
   int n_rows = 0, n_iv = 0;
   double step = 0.0;
   // snps
@@ -4107,7 +4275,8 @@ int fsclg_close(fsclg_ctx* c) {
   void* ptrs[] = {c->d_logt, c->d_coef, c->d_null, c->d_thr, c->d_pr0,
                   c->d_chr_start, c->d_chr_n, c->d_la_coarse, c->d_la_refine, c->d_n_refine,
                   c->d_stats, c->d_dfail, c->d_dband, c->d_tpos, c->d_lx,
-                  c->d_smp_coef, c->d_smp_prefix, c->d_smp_depth, c->d_smp_chr};
+                  c->d_smp_coef, c->d_smp_prefix, c->d_smp_depth, c->d_smp_chr,
+                  c->d_exp_fcoef, c->d_exp_neutral, c->d_exp_null_u, c->d_exp_null_f, c->d_exp_depth, c->d_exp_class};
   for (void* p : ptrs) if (p) hipFree(p);
   for (Slot& S : c->slot) {
     hipEventDestroy(S.ready);
@@ -4234,6 +4403,7 @@ int fsclg_upload_tables(fsclg_ctx* c, const double* log_table, const double* coe
   if ((r = upload(&c->d_thr, thr.data(), thr.size(), c->ustream))) return r;
   c->n_rows = n_rows; c->n_iv = n_iv; c->step = log_ad_step;
   c->h_thr = thr;
+  c->exp_n_depths = 0;  // (fsclg_expect_tables names the rows of these tables)
   if ((r = update_dband(c))) return r;
   c->plan_dirty = true;
   for (Slot& S : c->slot) { S.win_valid = false; S.ctab_valid = false; }
@@ -5462,7 +5632,8 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
       "the batch holds cell maxima (fsclg_cellmax_wait)", "the batch holds curves (fsclg_curve_wait)",
       "the batch holds site terms (fsclg_sites_wait)", "the batch holds a sample (fsclg_sample_wait)",
       "the batch holds a tail fit (fsclg_tail_wait)", "the batch holds surfaces (fsclg_surface_wait)",
-      "the batch holds block sums (fsclg_blocks_wait)", "the batch holds a conditional scan (fsclg_cond_wait)"};
+      "the batch holds block sums (fsclg_blocks_wait)", "the batch holds a conditional scan (fsclg_cond_wait)",
+      "the batch holds expected terms (fsclg_expect_wait)"};
   if (B.holds != BK_SEARCH) return set_err(FSCLG_E_STATE, other[B.holds]);
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
@@ -6209,6 +6380,8 @@ int fsclg_sample_tables(fsclg_ctx* c, const double* coef_t, const double* neutra
   if ((r = upload(&c->d_smp_prefix, prefix.data(), prefix.size(), c->ustream))) return r;
   if ((r = upload(&c->d_smp_depth, dep.data(), dep.size(), c->ustream))) return r;
   c->smp_n_depths = n_depths; c->smp_max_m = max_m; c->smp_n_iv = n_iv;
+  c->smp_depth_n.assign(depth_n, depth_n + n_depths);
+  c->exp_n_depths = 0;  // (the expect tables go with the sampler's)
   return FSCLG_OK;
 }
 
@@ -6284,6 +6457,169 @@ int fsclg_sample_wait(fsclg_ctx* c, int batch, int32_t* freq_out, unsigned long 
 }
 
 double fsclg_sample_last_ms(fsclg_ctx* c, int batch) { return last_ms(c, batch, BK_SAMPLE); }
+
+// ------------------------------------------------------------ expected terms under the model (host side)
+int fsclg_expect_tables(fsclg_ctx* c, const double* fcoef, const double* neutral, const double* null_unf,
+                        const double* null_fold, const int32_t* depth_n, int n_depths, int n_iv, double log_ad_step,
+                        const uint32_t* row_class, int n_rows) {
+  if (!c || !fcoef || !neutral || !null_unf || !null_fold || !depth_n || !row_class || n_depths <= 0 || n_iv <= 0)
+    return set_err(FSCLG_E_ARG, "expect tables");
+  if (!c->d_thr || !c->d_coef) return set_err(FSCLG_E_STATE, "tables not uploaded");
+  if (!c->smp_n_depths || c->smp_n_iv != c->n_iv) return set_err(FSCLG_E_STATE, "sample tables not set for these tables");
+  if (n_iv != c->n_iv || log_ad_step != c->step) return set_err(FSCLG_E_ARG, "expect tables on another knot grid");
+  if (n_depths != c->smp_n_depths || n_rows != c->n_rows) return set_err(FSCLG_E_ARG, "expect tables: depths or rows of other tables");
+  if (any_pending(c)) return set_err(FSCLG_E_STATE, "search batches in flight");
+  std::vector<ExpectDepth> dep((size_t)n_depths);
+  size_t n_coef = 0, n_fold = 0, n_unf = 0, n_nf = 0;
+  for (int d = 0; d < n_depths; d++) {
+    if (depth_n[d] != c->smp_depth_n[d]) return set_err(FSCLG_E_ARG, "expect tables: a depth differs from the sample tables'");
+    const int m = depth_n[d] - 1, nh = depth_n[d] / 2;
+    dep[d] = ExpectDepth{depth_n[d], 0, (unsigned long long)n_coef, (unsigned long long)n_fold, (unsigned long long)n_unf,
+                         (unsigned long long)n_nf};
+    n_coef += (size_t)n_iv * (size_t)m * 4;
+    n_fold += (size_t)n_iv * (size_t)nh * 4;
+    n_unf += (size_t)m;
+    n_nf += (size_t)nh;
+  }
+  for (int r = 0; r < n_rows; r++)
+    if ((row_class[r] & 0x7fffffffu) >= (uint32_t)n_depths) return set_err(FSCLG_E_ARG, "expect tables: depth of a row");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  int r;
+  c->exp_n_depths = 0;
+  if ((r = upload(&c->d_exp_fcoef, fcoef, n_fold, c->ustream))) return r;
+  if ((r = upload(&c->d_exp_neutral, neutral, n_unf, c->ustream))) return r;
+  if ((r = upload(&c->d_exp_null_u, null_unf, n_unf, c->ustream))) return r;
+  if ((r = upload(&c->d_exp_null_f, null_fold, n_nf, c->ustream))) return r;
+  if ((r = upload(&c->d_exp_depth, dep.data(), dep.size(), c->ustream))) return r;
+  if ((r = upload(&c->d_exp_class, row_class, (size_t)n_rows, c->ustream))) return r;
+  c->exp_n_depths = n_depths; c->exp_n_rows = n_rows;
+  return FSCLG_OK;
+}
+
+int fsclg_expect_submit(fsclg_ctx* c, int batch, int slot, const fsclg_site_req_t* req, int n_req, const double* la,
+                        int n_la, int n_bins, int eval_range) {
+  if (!c || (!req && n_req) || n_req < 0 || eval_range < 0 || (!la && n_req)) return set_err(FSCLG_E_ARG, "requests");
+  if (n_la < 1 || n_la > EXPECT_MAX_LA) return set_err(FSCLG_E_ARG, "expect: n_la outside [1, 64]");
+  if (n_bins < 1 || n_bins > EXPECT_MAX_BINS) return set_err(FSCLG_E_ARG, "expect: n_bins outside [1, 64]");
+  if (batch < 0 || batch >= NBATCH || slot < 0 || slot >= NSLOT) return set_err(FSCLG_E_ARG, "batch/slot");
+  if ((long long)n_req * n_la > EXPECT_MAX_TASKS) return set_err(FSCLG_E_ARG, "expect: more than 65535 (request, alpha) tasks");
+  if (!c->d_pr0 || !c->d_coef) return set_err(FSCLG_E_STATE, "tables/snps not set");
+  if (!c->exp_n_depths || c->exp_n_rows != c->n_rows || !c->smp_n_depths)
+    return set_err(FSCLG_E_STATE, "expect tables not set for these tables");
+  Batch& B = c->batch[batch];
+  if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
+  for (int i = 0; i < n_req; i++) {
+    if (req[i].chr < 0 || req[i].chr >= c->n_chr) return set_err(FSCLG_E_ARG, "request chromosome");
+    if (req[i].pos > 0x7FFFFFFF - 64) return set_err(FSCLG_E_ARG, "request position overflow");
+    for (int k = 0; k < n_la; k++) {
+      const double v = la[(size_t)i * n_la + k];
+      if (!(v >= LOG_AD_MIN && v <= LOG_AD_MAX)) return set_err(FSCLG_E_ARG, "expect: a log alpha outside [-20, 4] or NaN");
+    }
+  }
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  batch_reset(B, BK_EXPECT, slot, eval_range);
+  const int nt = n_req * n_la;
+  B.n_res = nt; B.x_nbins = n_bins; B.x_sites = 0;
+  int r;
+  if (nt > 0) {
+    {  // one covering cell per request
+      std::vector<fsclg_cell_t> cover((size_t)n_req);
+      for (int i = 0; i < n_req; i++) cover[i] = fsclg_cell_t{req[i].chr, req[i].pos, req[i].pos, 0};
+      if ((r = cover_windows(c, B, slot, cover, eval_range))) return r;
+    }
+    if ((r = ensure_io(B, 1))) return r;  // (make_params' cells and points: unused by these kernels)
+    if ((r = B.p_sreq.ensure(nt))) return r;
+    if ((r = B.p_shdr.ensure(nt))) return r;
+    for (int i = 0; i < n_req; i++)
+      for (int k = 0; k < n_la; k++)
+        B.p_sreq[(size_t)i * n_la + k] = fsclg_site_req_t{req[i].chr, req[i].pos, la[(size_t)i * n_la + k]};
+    // the walks: sites_kernel's header pass, one workgroup per task
+    r = launch_bracket(c, B, nt, "launch sites_kernel", [&](const Params& P) {
+      hipLaunchKernelGGL(sites_kernel, dim3(nt), dim3(WG), 0, B.stream, P, 0, (const fsclg_site_req_t*)B.p_sreq,
+                         B.p_shdr, (const SiteTask*)nullptr, (double*)nullptr);
+      return FSCLG_OK;
+    });
+    if (r) return r;
+  }
+  return batch_hold(c, B, BK_EXPECT);
+}
+
+// the headers are in: their time, the records' offsets (a running sum in task order), the number of records
+static int expect_headers(fsclg_ctx* c, Batch& B) {
+  if (B.st_synced || B.n_res == 0) return FSCLG_OK;
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  B.st_synced = true;
+  int r;
+  if ((r = batch_time(c, B, 1, BK_EXPECT, true))) return r;
+  uint64_t off = 0;
+  for (int i = 0; i < B.n_res; i++) { B.p_shdr[i].off = off; off += (uint64_t)B.p_shdr[i].len; }
+  B.x_sites = (size_t)off;
+  return FSCLG_OK;
+}
+
+int fsclg_expect_count(fsclg_ctx* c, int batch, size_t* n_sites) {
+  if (!c || batch < 0 || batch >= NBATCH || !n_sites) return set_err(FSCLG_E_ARG, "batch");
+  Batch& B = c->batch[batch];
+  if (B.holds != BK_EXPECT) return set_err(FSCLG_E_STATE, "no expected terms submitted on the batch");
+  const int r = expect_headers(c, B);
+  if (r) { batch_release(c, B); return r; }  // the batch ends here
+  *n_sites = B.x_sites;
+  return FSCLG_OK;
+}
+
+static int expect_wait_impl(fsclg_ctx* c, Batch& B, fsclg_expect_tot_t* tot, fsclg_site_hdr_t* hdr,
+                            fsclg_expect_site_t* sites) {
+  const int nt = B.n_res, nb1 = B.x_nbins + 1;
+  int r;
+  if ((r = flags_err((const fsclg_site_hdr_t*)B.p_shdr, sizeof(fsclg_site_hdr_t), nt))) return r;
+  if ((r = B.p_xtasks.ensure(nt))) return r;
+  if ((r = B.p_xtot.ensure((size_t)nt * nb1))) return r;
+  if ((r = B.d_xrec.ensure(std::max(B.x_sites, (size_t)1), "hipMalloc expect records"))) return r;
+  int maxlen = 0;
+  for (int i = 0; i < nt; i++) {
+    const fsclg_site_hdr_t& h = B.p_shdr[i];
+    B.p_xtasks[i] = ExpectTask{h.len > 0 ? h.pt.nearest_snp - h.nl : 0, h.len, h.pt.sweep_pos, 0, h.pt.lalpha,
+                               (unsigned long long)h.off};
+    maxlen = std::max(maxlen, h.len);
+  }
+  ExpectParams E;
+  E.coef_u = c->d_smp_coef; E.coef_f = c->d_exp_fcoef; E.neutral = c->d_exp_neutral; E.null_u = c->d_exp_null_u;
+  E.null_f = c->d_exp_null_f; E.depth = c->d_exp_depth; E.row_class = c->d_exp_class; E.tasks = B.p_xtasks;
+  E.rec = B.d_xrec; E.tot = B.p_xtot; E.n_tasks = nt; E.n_bins = B.x_nbins; E.n_rows = c->exp_n_rows; E.pad = 0;
+  const Params P0 = make_params(c, B, B.slot, 0, 3, B.eval_range, 0);
+  r = launch_bracket(c, B, nt, "launch expect_kernel", [&](const Params& P) {
+    if (maxlen > 0)
+      hipLaunchKernelGGL(expect_kernel, dim3((unsigned)((maxlen + EXPECT_WAVES - 1) / EXPECT_WAVES), (unsigned)nt),
+                         dim3(64 * EXPECT_WAVES), 0, B.stream, P, E, 0);
+    hipLaunchKernelGGL(expect_kernel, dim3(1, (unsigned)nt), dim3(EXPECT_FOLD_WG), 0, B.stream, P, E, 1);
+    return FSCLG_OK;
+  }, &P0);
+  if (r) return r;
+  HIPCHK(hipEventSynchronize(B.ev1), "hipEventSynchronize");
+  if ((r = batch_time(c, B, maxlen > 0 ? 2 : 1, BK_EXPECT, true))) return r;
+  memcpy(tot, B.p_xtot, sizeof(fsclg_expect_tot_t) * (size_t)nt * nb1);
+  if (hdr) memcpy(hdr, B.p_shdr, sizeof(fsclg_site_hdr_t) * (size_t)nt);
+  if (sites && B.x_sites)
+    HIPCHK(hipMemcpy(sites, B.d_xrec, sizeof(fsclg_expect_site_t) * B.x_sites, hipMemcpyDeviceToHost), "copy expect records");
+  return FSCLG_OK;
+}
+
+int fsclg_expect_wait(fsclg_ctx* c, int batch, fsclg_expect_tot_t* tot, fsclg_site_hdr_t* hdr, fsclg_expect_site_t* sites,
+                      size_t sites_cap) {
+  if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
+  Batch& B = c->batch[batch];
+  if (B.holds != BK_EXPECT) return set_err(FSCLG_E_STATE, "no expected terms submitted on the batch");
+  if (!tot && B.n_res) return set_err(FSCLG_E_ARG, "tot");  // (the batch stays submitted)
+  int r = expect_headers(c, B);
+  if (r == FSCLG_OK && sites && sites_cap < B.x_sites)  // (the batch stays submitted)
+    return set_err(FSCLG_E_ARG, "sites_cap below the walks' sites");
+  if (r == FSCLG_OK && B.n_res > 0) r = expect_wait_impl(c, B, tot, hdr, sites);
+  batch_release(c, B);
+  return r;
+}
+
+double fsclg_expect_last_ms(fsclg_ctx* c, int batch) { return last_ms(c, batch, BK_EXPECT); }
 
 // ------------------------------------------------------------ projected tail (host side)
 int fsclg_tail_submit(fsclg_ctx* c, int batch, const float* samples, size_t n_samples, const unsigned long long* offsets,

@@ -137,6 +137,10 @@ int main(int argc, char **argv) {
   int jackknife_top = 3, jackknife_block = -1, jackknife_halfwidth = -1, jackknife_step = -1, jackknife_n = 33;
   double jackknife_lo = LOG_AD_MIN, jackknife_hi = LOG_AD_MAX;
   int tail_df = 2, tail_min_n = 20;
+  char *expect_fname = NULL, *expect_alphas = NULL, *expect_top_s = NULL, *expect_bins_s = NULL; /* (NULL: not given) */
+  strlist_t expect_sweep = {NULL, 0};
+  int expect_top = 3, expect_bins = 24, expect_n = -1;
+  double expect_lo = LOG_AD_MIN, expect_hi = LOG_AD_MAX;
   scan_t *s;
   double **fsp;
   opt_t opts[] = {
@@ -226,6 +230,15 @@ int main(int argc, char **argv) {
       {0, "jackknife-halfwidth", &jackknife_halfwidth, T_INT, "half-width in bp of the jackknife's positions (default: --surface-halfwidth)"},
       {0, "jackknife-step", &jackknife_step, T_INT, "spacing in bp of the jackknife's positions (default: --surface-step)"},
       {0, "jackknife-alphas", &jackknife_alphas, T_STR, "LO:HI:N, the jackknife's alpha grid (default: --surface-alphas)"},
+      {0, "expect-file", &expect_fname, T_STR, "write what the fitted model expects at the sweeps of greatest CLR -- the expectation and SD of "
+                                               "the CLR under the sweep and under neutrality, per bin of log(alpha d), along an alpha "
+                                               "list, and in all -- to this file"},
+      {0, "expect-top", &expect_top_s, T_STR, "--expect-file takes this many points of greatest CLR (default 3)"},
+      {0, "expect-sweep", &expect_sweep, T_LIST, "chr:pos:alpha of a sweep for --expect-file (may be given several times; replaces the "
+                                                 "--expect-top choice)"},
+      {0, "expect-alphas", &expect_alphas, T_STR, "LO:HI:N, the alpha list of --expect-file's curve rows (default: the --surface-alphas "
+                                                  "value); the sweep's own alpha is added"},
+      {0, "expect-bins", &expect_bins_s, T_STR, "equal-width bins of log(alpha d) over [-20, 4] in --expect-file (1 .. 64, default 24)"},
       {0, "tail-min-n", &tail_min_n, T_INT, "--tail-file fits a point with at least this many positive null CLRs (default 20)"},
       {0, NULL, NULL, 0, NULL}};
 
@@ -423,6 +436,37 @@ int main(int argc, char **argv) {
       stop = 1;
     }
   }
+  if (!expect_fname && (expect_sweep.n || expect_alphas || expect_top_s || expect_bins_s)) {
+    logmsg(MSG_ERROR, "Error: --expect-sweep, --expect-top, --expect-alphas and --expect-bins need --expect-file.\n");
+    stop = 1;
+  }
+  if (expect_fname && dont_scan && expect_sweep.n == 0) {
+    logmsg(MSG_ERROR, "Error: --expect-file with --no-scan needs explicit --expect-sweep sweeps.\n");
+    stop = 1;
+  }
+  if (expect_top_s && (!int_option(expect_top_s, &expect_top) || expect_top < 0)) { logmsg(MSG_ERROR, "Error: --expect-top must be >= 0.\n"); stop = 1; }
+  if (expect_bins_s && (!int_option(expect_bins_s, &expect_bins) || expect_bins < 1 || expect_bins > FSCL_AMD_EXPECT_MAX_BINS)) {
+    logmsg(MSG_ERROR, "Error: --expect-bins must be 1 .. 64.\n");
+    stop = 1;
+  }
+  if (expect_alphas) {
+    char tail_c = 0;
+    double probe[FSCL_AMD_SURFACE_MAX_LA];
+    if (sscanf(expect_alphas, "%lf:%lf:%d%c", &expect_lo, &expect_hi, &expect_n, &tail_c) != 3 ||
+        fscl_amd_surface_alphas(expect_lo, expect_hi, expect_n, NAN, probe) < 1) {
+      logmsg(MSG_ERROR, "Error: --expect-alphas must be LO:HI:N with -20 <= LO <= HI <= 4 (natural-log alpha), 1 <= N <= 63, "
+                        "and LO < HI unless N is 1 (not \"%s\").\n", expect_alphas);
+      stop = 1;
+    }
+  }
+  for (i = 0; i < expect_sweep.n; i++) { /* (the chromosome names are checked once the data is loaded, before the scan) */
+    const char *t = expect_sweep.v[i], *c2 = strrchr(t, ':');
+    const double a = c2 ? atof(c2 + 1) : 0.0;
+    if (!c2 || !(a > 0.0) || !(log(a) >= LOG_AD_MIN && log(a) <= LOG_AD_MAX)) {
+      logmsg(MSG_ERROR, "Error: --expect-sweep=%s: expected chr:pos:alpha, alpha positive with its natural log within [-20, 4].\n", t);
+      stop = 1;
+    }
+  }
   if (jackknife_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --jackknife-file needs the scan (not with --no-scan).\n"); stop = 1; }
   if (jackknife_top < 0) { logmsg(MSG_ERROR, "Error: --jackknife-top must be >= 0.\n"); stop = 1; }
   if (jackknife_block == -1) jackknife_block = large_grid_sp / 2 > 1 ? large_grid_sp / 2 : 1;
@@ -454,7 +498,8 @@ int main(int argc, char **argv) {
   fsp = background_fsp(s, force_neutral, bs_fname, include_invariant);
   if (output_bs_fname) output_background_fs(output_bs_fname, s, fsp);
   if (!cond_alphas) { cond_lo = surface_lo; cond_hi = surface_hi; cond_n = surface_n; }
-  need_tables = !dont_scan || simulate_fname || bootstrap_fname || cond_fname;
+  if (!expect_alphas) { expect_lo = surface_lo; expect_hi = surface_hi; expect_n = surface_n; }
+  need_tables = !dont_scan || simulate_fname || bootstrap_fname || cond_fname || expect_fname;
   if (need_tables) {
     sm_ptable_t *sm;
     const unsigned long long sim_seed = simulate_seed ? strtoull(simulate_seed, NULL, 0) : 0xFD821A6ull;
@@ -467,8 +512,19 @@ int main(int argc, char **argv) {
     if (cond_fname && fscl_amd_conditional_check(s, given_sw, given_sweep.n, cond_halfwidth, cond_step, cond_la, cond_n_la, cond_rounds,
                                                  cond_min_clr) != 0)
       logmsg(MSG_FATAL, "fscl: %s", fscl_amd_conditional_error());
+    /* the expect sweeps and every host-only refusal of --expect-file, on every rank, before any device work */
+    fscl_amd_sweep_t *expect_sw = parse_sweeps(s, &expect_sweep, "expect-sweep");
+    fsclg_site_req_t *expect_req = malloc(sizeof *expect_req * (size_t)(expect_sweep.n > 0 ? expect_sweep.n : 1));
+    double expect_la[FSCL_AMD_SURFACE_MAX_LA];
+    const int expect_n_la = expect_fname ? fscl_amd_surface_alphas(expect_lo, expect_hi, expect_n, NAN, expect_la) : 0;
     int n_boot = bootstrap_sweep.n;
     const char *ws = getenv("WORLD_SIZE"), *rk = getenv("RANK");
+    if (!expect_req) logmsg(MSG_FATAL, "fscl: out of memory (expect sweeps)");
+    for (i = 0; i < expect_sweep.n; i++) {
+      expect_req[i].chr = expect_sw[i].chr; expect_req[i].pos = expect_sw[i].pos; expect_req[i].lalpha = log(expect_sw[i].alpha);
+    }
+    if (expect_fname && fscl_amd_expect_check(s, expect_req, expect_sweep.n, expect_la, expect_n_la, expect_bins) != 0)
+      logmsg(MSG_FATAL, "fscl: %s", fscl_amd_expect_error());
     if (ws && rk && atoi(ws) > 1) {
       /* one process per GPU (e.g. under torch.distributed.run): GPU $LOCAL_RANK (or
          $FSCL_AMD_DEVICE), results exchanged through a shared-memory segment named by
@@ -599,6 +655,18 @@ int main(int argc, char **argv) {
              (unsigned long long)cd.n_rows, cd.n_terms, fscl_amd_conditional_last_ms(), cd.fold_s);
       fscl_amd_conditional_free(&cd);
     }
+    if (expect_fname && !(ws && rk && atoi(ws) > 1 && atoi(rk) != 0)) {
+      /* what the model expects at the sweeps, of the data as loaded (rank 0 alone); no rand() draw */
+      fscl_amd_expect_t ex;
+      const int r = expect_sweep.n ? fscl_amd_scan_expect(s, sm, fsp, eval_range, expect_req, expect_sweep.n, expect_la, expect_n_la,
+                                                          expect_bins, &ex)
+                                   : fscl_amd_scan_point_expect(s, sm, fsp, eval_range, expect_top, large_grid_sp, expect_la,
+                                                                expect_n_la, expect_bins, &ex);
+      if (r != 0) logmsg(MSG_FATAL, "fscl: expectation failed (code %d): %s", r, fscl_amd_expect_error());
+      if (fscl_amd_expect_output(expect_fname, s, &ex, prepend_label) != 0) logmsg(MSG_FATAL, "fscl: cannot write %s", expect_fname);
+      logmsg(MSG_STATUS, "Expectation: %d sweeps, %d walks, kernel %.3f ms\n", ex.n, ex.n_tasks, fscl_amd_expect_last_ms());
+      fscl_amd_expect_free(&ex);
+    }
     if (dont_scan) {
       /* nothing to test or to write */
     } else if (n_permute > 0 && grid_mode)
@@ -637,7 +705,7 @@ int main(int argc, char **argv) {
                          "scan %.3f s)\n", n_boot, bootstrap_reps, tm[0], tm[1], tm[2], tm[3], tm[4]);
       free(bt);
     }
-    free(sim_sw); free(boot_sw); free(given_sw);
+    free(sim_sw); free(boot_sw); free(given_sw); free(expect_sw); free(expect_req);
     if (verbosity >= MSG_DEBUG1) {
       fscl_amd_stats_t st;
       fscl_amd_get_stats(&st);

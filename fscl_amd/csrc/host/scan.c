@@ -164,6 +164,7 @@ static struct {
   fsclg_ctx *ctx;
   uint64_t hash;
   int n_depths;
+  unsigned long long gen; /* uploads so far (the expect tables go with one) */
 } SMP;
 
 static void dev_close_all(void) {
@@ -3531,21 +3532,10 @@ static int same_geometry(const scan_t *s) {
   return 1;
 }
 
-int fscl_amd_simulate(scan_t *s, sm_ptable_t *sm, const fscl_amd_sweep_t *sweeps, int n_sweeps,
-                      unsigned long long seed, int rep, int *freq_out, unsigned long long *n_degenerate) {
-  fsclg_sweep_t *sw;
-  int32_t *depth;
-  uint64_t h;
+/* the first device holds the sampler's tables of sm (kept per tables hash) */
+static int sampler_tables(const scan_t *s, const sm_ptable_t *sm) {
+  const uint64_t h = tables_hash(sm, s->n_depths);
   int i, r;
-  if (!s || !sm || !freq_out || n_sweeps < 0 || (n_sweeps && !sweeps)) return FSCLG_E_ARG;
-  for (i = 0; i < n_sweeps; i++)
-    if (sweeps[i].chr < 0 || sweeps[i].chr >= s->n_chromosomes || !(sweeps[i].alpha > 0.0) ||
-        sweeps[i].alpha > 1.7976931348623157e308)
-      return FSCLG_E_ARG;
-  if (n_degenerate) *n_degenerate = 0;
-  if (D.world > 1 && D.rank != 0) return FSCLG_OK; /* rank 0 alone evaluates, as the other diagnostics */
-  if (!same_geometry(s)) prepare(s, sm);
-  h = tables_hash(sm, s->n_depths);
   if (SMP.ctx != D.ctx[0] || SMP.hash != h || SMP.n_depths != s->n_depths) {
     double *coef_t, *neutral;
     int32_t *dn = fh_malloc(sizeof(int32_t) * (size_t)s->n_depths, "depths");
@@ -3558,8 +3548,25 @@ int fscl_amd_simulate(scan_t *s, sm_ptable_t *sm, const fscl_amd_sweep_t *sweeps
     r = fsclg_sample_tables(D.ctx[0], coef_t, neutral, dn, s->n_depths, n_iv, (LOG_AD_MAX - LOG_AD_MIN) / (n_iv + 1.));
     free(coef_t); free(neutral); free(dn);
     if (r != FSCLG_OK) return r;
-    SMP.ctx = D.ctx[0]; SMP.hash = h; SMP.n_depths = s->n_depths;
+    SMP.ctx = D.ctx[0]; SMP.hash = h; SMP.n_depths = s->n_depths; SMP.gen++;
   }
+  return FSCLG_OK;
+}
+
+int fscl_amd_simulate(scan_t *s, sm_ptable_t *sm, const fscl_amd_sweep_t *sweeps, int n_sweeps,
+                      unsigned long long seed, int rep, int *freq_out, unsigned long long *n_degenerate) {
+  fsclg_sweep_t *sw;
+  int32_t *depth;
+  int i, r;
+  if (!s || !sm || !freq_out || n_sweeps < 0 || (n_sweeps && !sweeps)) return FSCLG_E_ARG;
+  for (i = 0; i < n_sweeps; i++)
+    if (sweeps[i].chr < 0 || sweeps[i].chr >= s->n_chromosomes || !(sweeps[i].alpha > 0.0) ||
+        sweeps[i].alpha > 1.7976931348623157e308)
+      return FSCLG_E_ARG;
+  if (n_degenerate) *n_degenerate = 0;
+  if (D.world > 1 && D.rank != 0) return FSCLG_OK; /* rank 0 alone evaluates, as the other diagnostics */
+  if (!same_geometry(s)) prepare(s, sm);
+  if ((r = sampler_tables(s, sm)) != FSCLG_OK) return r;
   depth = fh_malloc(sizeof(int32_t) * (size_t)(s->n_snps ? s->n_snps : 1), "site depths");
   sw = fh_malloc(sizeof(fsclg_sweep_t) * (size_t)(n_sweeps ? n_sweeps : 1), "sweeps");
   for (i = 0; i < s->n_snps; i++) depth[i] = s->snps[i].depth_p;
@@ -3626,6 +3633,162 @@ int fscl_amd_bootstrap(scan_t *s, sm_ptable_t *sm, double **fsp, const fscl_amd_
   }
   free(freq);
   g_boot_s[0] = fh_now() - t_all;
+  return r;
+}
+
+/* ------------------------------------------------------ expected terms under the model (--expect-file)
+   fscl_amd_scan_expect evaluates every (request, alpha) as one task of fsclg_expect_submit on the
+   first device, on the data as loaded (slot 0).  The expect tables are kept per upload of the scan
+   (prepare's key), of the sampler's tables and of the background spectra.  The host-only pieces
+   are in expect.c. */
+static double g_expect_ms;
+static struct {
+  fsclg_ctx *ctx;
+  uint64_t key, fsp_hash;
+  unsigned long long smp_gen;
+} EXP;
+double fscl_amd_expect_last_ms(void) { return g_expect_ms; }
+
+static int expect_tables(const scan_t *s, const sm_ptable_t *sm, double **fsp) {
+  double *fcoef, *neutral, *nu, *nf;
+  int32_t *dn;
+  uint32_t *cls;
+  uint64_t fh = 1469598103934665603ull;
+  int d, r, n_iv;
+  if ((r = sampler_tables(s, sm)) != FSCLG_OK) return r;
+  for (d = 0; d < s->n_depths; d++) fh = hash_words(fsp[d], sizeof(double) * (size_t)(s->sample_depths[d] + 1), fh);
+  if (EXP.ctx == D.ctx[0] && EXP.key == D.key && EXP.smp_gen == SMP.gen && EXP.fsp_hash == fh) return FSCLG_OK;
+  dn = fh_malloc(sizeof(int32_t) * (size_t)s->n_depths, "depths");
+  fscl_amd_expect_tables_build(sm, fsp, s->n_depths, &fcoef, &neutral, &nu, &nf, dn, &n_iv);
+  /* the class of every device row: the depth of the sites that carry it, bit 31 for a folded row */
+  cls = fh_calloc((size_t)D.rm.n_dev_rows, sizeof(uint32_t), "row classes");
+  for (d = 0; d < D.rm.n_depths; d++) {
+    const int n = D.rm.depth_n[d];
+    for (r = 0; r <= n + n / 2 + 1; r++) {
+      const int dr = D.rm.dev_row[D.rm.row_base[d] + r];
+      if (dr >= 0) cls[dr] = (uint32_t)d | (r > n ? 0x80000000u : 0u);
+    }
+  }
+  EXP.ctx = NULL;
+  r = fsclg_expect_tables(D.ctx[0], fcoef, neutral, nu, nf, dn, s->n_depths, n_iv, (LOG_AD_MAX - LOG_AD_MIN) / (n_iv + 1.), cls,
+                          D.rm.n_dev_rows);
+  free(fcoef); free(neutral); free(nu); free(nf); free(dn); free(cls);
+  if (r != FSCLG_OK) return r;
+  EXP.ctx = D.ctx[0]; EXP.key = D.key; EXP.smp_gen = SMP.gen; EXP.fsp_hash = fh;
+  return FSCLG_OK;
+}
+
+/* the test handle of fsclg_expect_submit / fsclg_expect_count / fsclg_expect_wait on the first device, for
+   any batch: on the uploaded rows (slot 0).  *sites_out is malloc'd (n_sites records) when not NULL */
+int fscl_amd_expect_runs(scan_t *s, sm_ptable_t *sm, double **fsp, const fsclg_site_req_t *req, int n_req, const double *la,
+                         int n_la, int n_bins, int eval_range, int batch, fsclg_expect_tot_t *tot, fsclg_site_hdr_t *hdr,
+                         fsclg_expect_site_t **sites_out, size_t *n_sites) {
+  size_t ns = 0;
+  fsclg_expect_site_t *sites = NULL;
+  int r;
+  if (!s || !sm || !fsp || n_req < 0) return FSCLG_E_ARG;
+  if (sites_out) *sites_out = NULL;
+  if (n_sites) *n_sites = 0;
+  prepare(s, sm);
+  set_original_rows();
+  if ((r = expect_tables(s, sm, fsp)) != FSCLG_OK) return r;
+  if ((r = fsclg_expect_submit(D.ctx[0], batch, 0, req, n_req, la, n_la, n_bins, eval_range)) != FSCLG_OK) return r;
+  if ((r = fsclg_expect_count(D.ctx[0], batch, &ns)) != FSCLG_OK) return r;
+  if (sites_out) sites = fh_malloc(sizeof *sites * (ns ? ns : 1), "expect site records");
+  r = fsclg_expect_wait(D.ctx[0], batch, tot, hdr, sites, ns);
+  g_expect_ms = fsclg_expect_last_ms(D.ctx[0], batch);
+  if (r != FSCLG_OK) { free(sites); return r; }
+  if (sites_out) *sites_out = sites;
+  if (n_sites) *n_sites = ns;
+  return FSCLG_OK;
+}
+
+int fscl_amd_scan_expect(scan_t *s, sm_ptable_t *sm, double **fsp, int eval_range, const fsclg_site_req_t *req, int n,
+                         const double *la, int n_la, int n_bins, fscl_amd_expect_t *out) {
+  fsclg_site_req_t *fr;
+  double *fl;
+  int i, k, r, nt = 0;
+  if (!out) return FSCLG_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (fscl_amd_expect_check(s, req, n, la, n_la, n_bins) != 0) return FSCLG_E_ARG; /* (before any device work) */
+  if (!sm || !fsp || eval_range < 0) return FSCLG_E_ARG;
+  if (D.world > 1 && D.rank != 0) return FSCLG_OK; /* rank 0 alone evaluates, as the sampler */
+  /* every request's own list: the shared one with the request's alpha inserted in order */
+  out->n = n; out->n_bins = n_bins;
+  out->req = fh_malloc(sizeof *out->req * (size_t)(n ? n : 1), "expect requests");
+  out->first = fh_malloc(sizeof(int) * (size_t)(n + 1), "expect requests");
+  out->own = fh_malloc(sizeof(int) * (size_t)(n ? n : 1), "expect requests");
+  out->la = fh_malloc(sizeof(double) * (size_t)(n ? n : 1) * (size_t)(n_la + 1), "expect alphas");
+  for (i = 0; i < n; i++) {
+    int placed = 0;
+    out->req[i] = req[i];
+    out->first[i] = nt;
+    for (k = 0; k < n_la; k++) {
+      if (!placed && req[i].lalpha <= la[k]) {
+        out->own[i] = nt - out->first[i];
+        if (req[i].lalpha < la[k]) out->la[nt++] = req[i].lalpha;
+        placed = 1;
+      }
+      out->la[nt++] = la[k];
+    }
+    if (!placed) { out->own[i] = nt - out->first[i]; out->la[nt++] = req[i].lalpha; }
+  }
+  out->first[n] = nt;
+  out->n_tasks = nt;
+  out->hdr = fh_malloc(sizeof *out->hdr * (size_t)(nt ? nt : 1), "expect headers");
+  out->tot = fh_malloc(sizeof *out->tot * (size_t)(nt ? nt : 1) * (size_t)(n_bins + 1), "expect totals");
+  fr = fh_malloc(sizeof *fr * (size_t)(nt ? nt : 1), "expect tasks");
+  fl = out->la;
+  for (i = 0; i < n; i++)
+    for (k = out->first[i]; k < out->first[i + 1]; k++) { fr[k].chr = req[i].chr; fr[k].pos = req[i].pos; fr[k].lalpha = fl[k]; }
+  prepare(s, sm);
+  set_original_rows();
+  g_expect_ms = 0.;
+  r = expect_tables(s, sm, fsp);
+  if (r == FSCLG_OK) r = fsclg_expect_submit(D.ctx[0], 0, 0, fr, nt, fl, 1, n_bins, eval_range);
+  if (r == FSCLG_OK) {
+    r = fsclg_expect_wait(D.ctx[0], 0, out->tot, out->hdr, NULL, 0);
+    g_expect_ms = fsclg_expect_last_ms(D.ctx[0], 0);
+  }
+  out->kernel_ms = g_expect_ms;
+  free(fr);
+  if (r != FSCLG_OK) fscl_amd_expect_free(out);
+  return r;
+}
+
+int fscl_amd_scan_point_expect(scan_t *s, sm_ptable_t *sm, double **fsp, int eval_range, int top, int spacing, const double *la,
+                               int n_la, int n_bins, fscl_amd_expect_t *out) {
+  fsclg_site_req_t *req;
+  int *point;
+  char *used;
+  int n = 0, i, k, r;
+  if (!out) return FSCLG_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (!s || !sm || (!s->scan_pts && s->n_scan_pts) || s->n_scan_pts < 0 || top < 0 || spacing < 0) return FSCLG_E_ARG;
+  req = fh_calloc(top ? top : 1, sizeof *req, "expect requests");
+  point = fh_calloc(top ? top : 1, sizeof *point, "expect requests");
+  used = fh_calloc(s->n_scan_pts ? s->n_scan_pts : 1, 1, "expect requests");
+  while (n < top) { /* descending CLR (a NaN never), none within `spacing` of one already taken: --surface-top's rule */
+    int best = -1;
+    for (i = 0; i < s->n_scan_pts; i++)
+      if (!used[i] && s->scan_pts[i].clr == s->scan_pts[i].clr && (best < 0 || s->scan_pts[i].clr > s->scan_pts[best].clr))
+        best = i;
+    if (best < 0) break;
+    used[best] = 1;
+    for (k = 0; k < n; k++) {
+      long long d = (long long)s->scan_pts[best].sweep_pos - req[k].pos;
+      if (req[k].chr == s->scan_pts[best].chr && (d < 0 ? -d : d) <= spacing) break;
+    }
+    if (k < n) continue;
+    if (!(s->scan_pts[best].lalpha >= LOG_AD_MIN && s->scan_pts[best].lalpha <= LOG_AD_MAX)) continue;
+    req[n].chr = s->scan_pts[best].chr; req[n].pos = s->scan_pts[best].sweep_pos; req[n].lalpha = s->scan_pts[best].lalpha;
+    point[n++] = best;
+  }
+  free(used);
+  r = fscl_amd_scan_expect(s, sm, fsp, eval_range, req, n, la, n_la, n_bins, out);
+  free(req);
+  if (r == FSCLG_OK && out->hdr) out->point = point;
+  else free(point);
   return r;
 }
 

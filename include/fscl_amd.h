@@ -709,6 +709,73 @@ void fscl_amd_bootstrap_output(const char *fname, const scan_t *scan_obj, const 
 void fscl_amd_sample_tables_build(const sm_ptable_t *sm_p, int n_depths, double **coef_t, double **neutral,
                                   int32_t *depth_n, int *n_iv);
 
+/* ---- expected CLR and term moments of a sweep under the model (--expect-file) ----------
+   What the fitted model itself predicts at a sweep (chr, pos, alpha): for every site of the walk
+   fscl_amd_scan_sites returns for it, the first two moments of the site's term over the model
+   spectrum -- under the sweep (p_f = exp(spline_f(x))) and under neutrality (q_f = the tables'
+   fsp[f]) -- with the class f = 1 .. n-1 observed as c = f, or min(f, n - f) on a folded site, and its
+   term t_f = spline_c(x) - null_logl(depth, c), what snp_likelihood returns for the site observed in
+   that class.  The definitions -- usable classes, renormalisation, lost mass, degenerate sites, the
+   bins of x = logt(|d|) + log alpha over [-20, 4], the fixed order of every sum -- are fsclg_expect_submit's
+   (include/fsclg.h).  null_logl comes from tables built with compute_snp_null_model's expressions from
+   fsp, the background spectra the null model was computed from (fscl_amd_expect_tables_build, host
+   only; all four malloc'd: the folded rows [depth][interval][c][c0..c3], the tables' neutral
+   probabilities, the null values of the unfolded classes f = 1 .. n-1 and of the folded classes c = 1 ..
+   n/2).
+   fscl_amd_scan_expect: request i is evaluated at its own list -- la[0 .. n_la), ascending, with
+   req[i].lalpha inserted in order unless it is one of them -- as the tasks first[i] .. first[i + 1),
+   own[i] the index of its own alpha within them; hdr[task] is the walk's header (as fscl_amd_scan_sites';
+   off counts the sites of the tasks before), tot[task * (n_bins + 1) + b] its totals of bin b, entry
+   n_bins of all its sites.  The totals are sums of log-likelihood terms; the file doubles them (the
+   CLR scale).  Runs on the first device on the data as loaded; with several ranks rank 0 alone
+   evaluates (the others return FSCLG_OK with hdr NULL).  Refused with FSCLG_E_ARG before any device
+   work, fscl_amd_expect_error() naming the option (fscl_amd_expect_check, host only: 0 or -1): n_bins
+   outside 1 .. 64, n_la outside 1 .. 64 or a list not ascending within [-20, 4], an unknown chromosome, a
+   log alpha outside [-20, 4], a result above $FSCL_AMD_EXPECT_CAP bytes (default 2^30).
+   fscl_amd_scan_point_expect: the `top` scan points of greatest CLR at their fitted alpha, skipping
+   a point within `spacing` bp of one already chosen (--surface-top's rule); point[i] is the scan point
+   of request i.
+   fscl_amd_expect_output (fname NULL: stdout; host only; 0, or -1 if the file cannot be written), per
+   request, all likelihood columns on the CLR scale (2 x the sum, SD = 2 sqrt(sum var)):
+     [label TAB] chromosome pos alpha bin x_lo x_hi n_sites obs E_sweep SD_sweep z_sweep E_null SD_null z_null
+     [label TAB] chromosome pos alpha curve alpha_k n_sites E_sweep SD_sweep E_null SD_null dprime
+     [label TAB] chromosome pos alpha summary n_sites n_degenerate obs E_sweep SD_sweep z_sweep E_null SD_null
+       z_null max_lost_sweep max_lost_null
+   tab separated; the bins of the request's own alpha that hold sites, then one curve row per alpha of
+   its list, then the summary.  z = (obs - E) / SD, dprime = (E_sweep - E_null) / sqrt((SD_sweep^2 +
+   SD_null^2) / 2), NA where the divisor is 0.  The SDs assume independent sites.
+   fscl_amd_expect_runs: the test handle of fsclg_expect_submit / _count / _wait on the first device
+   and slot 0, for any batch; *sites_out (may be NULL) is malloc'd. */
+#define FSCL_AMD_EXPECT_MAX_LA 64
+#define FSCL_AMD_EXPECT_MAX_BINS 64
+typedef struct {
+  int n, n_tasks, n_bins;
+  fsclg_site_req_t *req;     /* [n] */
+  int *first;                /* [n + 1] */
+  int *own;                  /* [n] */
+  double *la;                /* [n_tasks] */
+  fsclg_site_hdr_t *hdr;     /* [n_tasks]; NULL: not evaluated on this rank */
+  fsclg_expect_tot_t *tot;   /* [n_tasks][n_bins + 1] */
+  int *point;                /* [n] scan point of each request (fscl_amd_scan_point_expect), else NULL */
+  double kernel_ms;
+} fscl_amd_expect_t;
+int fscl_amd_scan_expect(scan_t *scan_obj, sm_ptable_t *sm_p, double **fsp, int eval_range, const fsclg_site_req_t *req, int n,
+                         const double *la, int n_la, int n_bins, fscl_amd_expect_t *out);
+int fscl_amd_scan_point_expect(scan_t *scan_obj, sm_ptable_t *sm_p, double **fsp, int eval_range, int top, int spacing,
+                               const double *la, int n_la, int n_bins, fscl_amd_expect_t *out);
+int fscl_amd_expect_runs(scan_t *scan_obj, sm_ptable_t *sm_p, double **fsp, const fsclg_site_req_t *req, int n_req,
+                         const double *la, int n_la, int n_bins, int eval_range, int batch, fsclg_expect_tot_t *tot,
+                         fsclg_site_hdr_t *hdr, fsclg_expect_site_t **sites_out, size_t *n_sites);
+int fscl_amd_expect_check(const scan_t *scan_obj, const fsclg_site_req_t *req, int n, const double *la, int n_la, int n_bins);
+const char *fscl_amd_expect_error(void);
+size_t fscl_amd_expect_cap(void);
+int fscl_amd_expect_bin(double x, int n_bins);
+void fscl_amd_expect_tables_build(const sm_ptable_t *sm_p, double **fsp, int n_depths, double **fcoef, double **neutral,
+                                  double **null_unf, double **null_fold, int32_t *depth_n, int *n_iv);
+int fscl_amd_expect_output(const char *fname, const scan_t *scan_obj, const fscl_amd_expect_t *r, const char *prepend_label);
+void fscl_amd_expect_free(fscl_amd_expect_t *r);
+double fscl_amd_expect_last_ms(void);
+
 /* ---- conditional sweep scan given fixed sweeps (--conditional-file) ------------------
    The composite likelihood of one more sweep at a candidate position, given sweeps held fixed, as
    a likelihood ratio against the model with the given sweeps alone -- the fit of what

@@ -484,6 +484,74 @@ int fsclg_tail_submit(fsclg_ctx *c, int batch, const float *samples, size_t n_sa
 int fsclg_tail_wait(fsclg_ctx *c, int batch, fsclg_tail_t *out);
 double fsclg_tail_last_ms(fsclg_ctx *c, int batch);
 
+/* Expected terms of a walk under the model: what the fitted spectrum itself predicts at a sweep.
+   A request is a walk of fsclg_sites_submit (chr, pos; its lalpha field is not read); request r is evaluated at each of the
+   n_la log alphas la[r * n_la ..], giving the tasks (r, k) in that order.  The sites of task (r, k)
+   are exactly the sites whose terms fsclg_sites_submit returns for (chr, pos, la[r * n_la + k]) on
+   the slot's rows -- the same nearest SNP, window limits and cut at log(alpha d) > LOG_AD_MAX -- in
+   ascending site index [nearest - nl, nearest + nr]; an empty walk has no sites.
+   fsclg_expect_tables uploads what the sampler's tables lack (fsclg_sample_tables first, whose
+   unfolded coefficients are reused; FSCLG_E_STATE before it, FSCLG_E_ARG for other depths or another
+   knot grid): fcoef, the folded rows [depth][interval][c][c0..c3], c = 1 .. n/2 (depth d starts after
+   the 4 * n_iv * (depth_n[e] / 2) doubles of the depths e < d); neutral, fsp[1 .. n-1] per depth;
+   null_unf, null_logl of an unfolded site of class f = 1 .. n-1 per depth; null_fold, null_logl of a
+   folded site of class c = 1 .. n/2 per depth; row_class[n_rows of fsclg_upload_tables], per device
+   row the depth index of the sites that carry it, bit 31 set for a folded row.  The device takes no log.
+   For site i of depth n at x = logt(|d|) + lalpha (fsclg_sample_submit's logt and interval, with the
+   clamp to interval 0), over the derived counts f = 1 .. n-1:
+     p_f = exp(spline_f(x)), q_f = fsp[f]; a value that is not finite or not positive counts as 0;
+     S = sum p_f, Q = sum q_f;
+     the observed class of f is c = f, on a folded site c = min(f, n - f);
+     t_f = spline_c(x) - null_unf[c], on a folded site fspline_c(x) - null_fold[c]: what
+       snp_likelihood returns for the site observed in that class;
+     f is usable iff p_f > 0, q_f > 0 and t_f is finite; Su, Qu are S, Q over the usable f;
+     m1_s = sum (p_f / Su) t_f, m2_s = sum (p_f / Su) t_f^2; m1_0, m2_0 the same with q_f / Qu;
+     lost_s = 1 - Su / S, lost_0 = 1 - Qu / Q.
+   A site with no usable class, or with S, Q, Su or Qu not positive and finite, is degenerate: its
+   moments and losses are stored as 0 and it adds nothing to the sums below but obs and the counts.
+   Order of the class sums: lane l of the site's wave adds its classes f = 1 + l, 65 + l, 129 + l, ...
+   in ascending f from +0.0 (the unnormalised sums sum p t, sum p t^2, ...), then the 64 lane sums are
+   combined by an xor butterfly with lane distances 32, 16, 8, 4, 2, 1 in that order, and the
+   quotients are taken last.  obs is the site's observed term, the value fsclg_sites_wait stores.
+   tot[task * (n_bins + 1) + b], b < n_bins, covers the task's sites whose x falls into bin b of
+   n_bins equal-width bins of [LOG_AD_MIN, LOG_AD_MAX]: b = (int)((x - LOG_AD_MIN) * n_bins / 24)
+   clamped to [0, n_bins - 1] (x below the range goes to bin 0); entry b = n_bins covers all of the
+   task's sites.  Each sum is a sequential fold over the sites in ascending site index from +0.0,
+   var = max(m2 - m1^2, 0) per site; max_lost_* is the greatest loss of a site that is not degenerate
+   (0 without one).  No atomic is on the result path: the same input gives the same bytes on every
+   batch and slot, alone or among other requests.
+   Asynchronous like fsclg_sites_submit / fsclg_sites_wait (any batch and slot; the window null sums
+   are summed here).  The submit launches the walks' headers; fsclg_expect_count blocks for them and
+   gives the number of (task, site) pairs; fsclg_expect_wait launches expect_kernel (phase 0: one wave
+   per pair, the site's moments into device memory; phase 1: one workgroup per task folds them) and
+   stores tot (n_req * n_la * (n_bins + 1) entries), hdr if not NULL (n_req * n_la headers as
+   fsclg_sites_wait's, off the index of the task's first site record) and sites if not NULL (the
+   site records, task after task; sites_cap below their number: FSCLG_E_ARG, the batch stays
+   submitted).  Errors as fsclg_sites_submit's, and FSCLG_E_ARG for n_la outside [1, 64], n_bins
+   outside [1, 64], a lalpha outside [LOG_AD_MIN, LOG_AD_MAX], more than 65535 tasks;
+   FSCLG_E_STATE when the expect tables are not set for the uploaded tables.
+   fsclg_expect_last_ms: the summed time (HIP events) of the batch's header launch and expect_kernel
+   launches. */
+typedef struct {
+  int32_t site;              /* global site index */
+  int16_t degenerate, bin;   /* 1: degenerate; the site's bin of x among the call's n_bins */
+  double x, obs, m1_s, m2_s, m1_0, m2_0, lost_s, lost_0;
+} fsclg_expect_site_t;
+typedef struct {
+  uint32_t n_sites, n_degenerate;
+  double obs, e_s, v_s, e_0, v_0;  /* sums of obs, m1_s, var_s, m1_0, var_0 (log-likelihood scale) */
+  double max_lost_s, max_lost_0;
+} fsclg_expect_tot_t;
+int fsclg_expect_tables(fsclg_ctx *c, const double *fcoef, const double *neutral, const double *null_unf,
+                        const double *null_fold, const int32_t *depth_n, int n_depths, int n_iv, double log_ad_step,
+                        const uint32_t *row_class, int n_rows);
+int fsclg_expect_submit(fsclg_ctx *c, int batch, int slot, const fsclg_site_req_t *req, int n_req,
+                        const double *la /* [n_req][n_la] */, int n_la, int n_bins, int eval_range);
+int fsclg_expect_count(fsclg_ctx *c, int batch, size_t *n_sites);
+int fsclg_expect_wait(fsclg_ctx *c, int batch, fsclg_expect_tot_t *tot, fsclg_site_hdr_t *hdr, fsclg_expect_site_t *sites,
+                      size_t sites_cap);
+double fsclg_expect_last_ms(fsclg_ctx *c, int batch);
+
 /* the exact interval thresholds the kernel uses in place of spline_interpolate's
    division (sm-spline.c:52): thr[j] = least double x with
    (int)((x - LOG_AD_MIN) / log_ad_step) >= j, for j = 1..n_iv (thr has n_iv+1 slots) */

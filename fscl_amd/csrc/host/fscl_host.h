@@ -44,6 +44,11 @@ int fh_plan_build(fh_plan_t *P, const fh_perm_geom_t *G, double nbp, double widt
 void fh_plan_free(fh_plan_t *P);
 void fh_plan_apply_u32(uint32_t *rows, int n, const fsclg_swap_t *ent, const int32_t *grp, int n_grp);
 
+/* the permutation test's trial rule (perm.c; scan-chromosome.c:488-502): one result applied to
+   one scan point; draw(ctx) supplies the prune draw, called only when one is due */
+typedef int (*fh_draw_fn)(void *ctx);
+void fh_trial_apply(scan_pt_t *p, double clr, double lalpha, int start_pos, int save, fh_draw_fn draw, void *ctx);
+
 /* log_fact table shared by lchoose (sm-spline.c:18-39) */
 double fh_log_fact(int n);
 void fh_log_fact_reserve(int n);

@@ -13,6 +13,7 @@
    turn (about 15 levels for 5 000 blocks at C5).  The result is the sequential one, element for
    element (tests/test_host.py: against the oracle's orc_block_permute). */
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -211,6 +212,23 @@ void fh_plan_apply_u32(uint32_t *rows, int n, const fsclg_swap_t *ent, const int
       }
     }
   free(tmp);
+}
+
+/* one trial's result (clr, lalpha; its cell starts at start_pos) applied to its scan point:
+   scan-chromosome.c:488-502, the product's only copy.  The prune draw (31 bits, as rand()) is asked
+   of the caller only when this hit takes permute_p to >= 20, so at most once: the stream, the
+   counter-based draw and the pipeline's order guard stay with the drivers (scan.c).  At most `save`
+   null CLRs are kept */
+void fh_trial_apply(scan_pt_t *p, double clr, double lalpha, int start_pos, int save, fh_draw_fn draw, void *ctx) {
+  if (clr >= p->clr) {
+    p->permute_p++;
+    if (p->permute_p >= 20 && p->permute_p / (double)p->permute_n >= draw(ctx) / (2147483647 + 1.0))
+      p->permute_finished = 1; /* Q7: ratio uses the pre-increment count */
+  }
+  if (p->permute_n < save) p->permute_clr[p->permute_n] = (float)clr;
+  p->permute_n++;
+  if (clr < 0 || clr > 1000000 || isnan(clr))
+    fprintf(stderr, "%d\t%d\t%g\t%1.3e\n", p->chr, start_pos, clr, exp(lalpha));
 }
 
 /* test hook (tests/test_host.py): one trial's permutation of rows[0..n) (in place) through the

@@ -14,6 +14,7 @@
 #define _GNU_SOURCE
 #include <errno.h>
 #include <float.h>
+#include <limits.h>
 #include <math.h>
 #include <pthread.h>
 #include <sched.h>
@@ -52,6 +53,14 @@ void fscl_amd_srand(unsigned seed) {
 static fh_rand_t *perm_rng(void) {
   if (!g_rng_seeded) fscl_amd_srand(PERM_SEED);
   return &g_rng;
+}
+
+/* an integer environment switch clamped to [lo, hi]; dflt when unset (an empty or non-numeric
+   value reads as 0, then clamped) */
+static int env_int(const char *name, int dflt, int lo, int hi) {
+  const char *e = getenv(name);
+  const int v = e ? atoi(e) : dflt;
+  return !e ? dflt : v < lo ? lo : v > hi ? hi : v;
 }
 
 /* what the SIGINT dump writes (scan-chromosome.c:553-560 reads fscl.c's globals
@@ -1333,6 +1342,14 @@ typedef struct {
    0 = not yet measured */
 static double *g_pcost;
 
+/* a point's cell in a permutation trial */
+static void trial_cell(const scan_pt_t *q, int large_grid_sp, fsclg_cell_t *cl) {
+  cl->chr = q->chr;
+  cl->start_pos = q->sweep_pos - (q->sweep_pos % large_grid_sp); /* Q5: G-aligned, unclipped */
+  cl->end_pos = cl->start_pos + large_grid_sp;
+  cl->pad = 0;
+}
+
 static void tb_reserve(trial_batch_t *b, int n) {
   if (n <= b->cap) return;
   b->cap = n;
@@ -1436,25 +1453,21 @@ static void tb_wait(trial_batch_t *b, pqueue_t *pq) { tb_wait_flags(b, pq, NULL)
    may draw rand() (scan-chromosome.c:488-502) */
 static unsigned long long g_draws;  /* rand() draws of the pruning pass so far */
 
+typedef struct { int trial, draw; fh_rand_t *g; } pq_draw_t;
+static int pq_draw(void *ctx) {
+  const pq_draw_t *d = ctx;
+  if (d->trial != d->draw) logmsg(MSG_FATAL, "fscl_amd: permutation pipeline: out-of-order rand draw");
+  g_draws++;
+  return fh_rand(d->g);
+}
+
 static void pq_flush(scan_t *s, pqueue_t *pq, int i, int upto, int draw, fh_rand_t *g, int save) {
   pqueue_t *q = pq + i;
-  scan_pt_t *p = s->scan_pts + i;
   while (q->n > 0) {
     pres_t *e = q->e + q->head;
+    pq_draw_t d = {e->trial, draw, g};
     if (!e->have || e->trial > upto) break;
-    if (e->clr >= p->clr) {
-      p->permute_p++;
-      if (p->permute_p >= 20) {
-        if (e->trial != draw) logmsg(MSG_FATAL, "fscl_amd: permutation pipeline: out-of-order rand draw");
-        g_draws++;
-        if (p->permute_p / (double)p->permute_n >= fh_rand(g) / (2147483647 + 1.0))
-          p->permute_finished = 1; /* Q7: ratio uses the pre-increment count */
-      }
-    }
-    if (p->permute_n < save) p->permute_clr[p->permute_n] = (float)e->clr;
-    p->permute_n++;
-    if (e->clr < 0 || e->clr > 1000000 || isnan(e->clr))
-      fprintf(stderr, "%d\t%d\t%g\t%1.3e\n", p->chr, e->start_pos, e->clr, exp(e->lalpha));
+    fh_trial_apply(s->scan_pts + i, e->clr, e->lalpha, e->start_pos, save, pq_draw, &d);
     q->head = (q->head + 1) % PQ;
     q->n--;
   }
@@ -1529,45 +1542,64 @@ static int plan_mode_setup(double nbp, double width_mb, const fh_rand_t *g) {
   return 1;
 }
 
-static void permute_pipelined(scan_t *s, int n_perm, double permute_nbp, int eval_range, int bp_resl,
-                              int large_grid_sp, double scan_width_mb, fh_rand_t *g, int save) {
-  const char *env = getenv("FSCL_AMD_DEPTH");
-  const int K = env ? (atoi(env) < 2 ? 2 : (atoi(env) > FSCLG_N_SLOTS ? FSCLG_N_SLOTS : atoi(env))) : 4;
+/* what permute_pipelined's loop carries between trials */
+typedef struct {
+  scan_t *s;
+  int n_perm, eval_range, bp_resl, large_grid_sp, save;
+  double nbp, width_mb;
+  fh_rand_t *g;
+  int K, S;                             /* trials in flight; row slots (and bulk batches) */
+  int n_pre, no_merge;
+  trial_batch_t A, Bt[FSCLG_N_SLOTS];   /* the blocking batch; each row slot's bulk batch */
+  double *nul[FSCLG_N_SLOTS];           /* each row slot's whole-chromosome null sums */
+  pqueue_t *pq;
+  int *act, n_act;
+  int pre_bi[FSCLG_N_SLOTS];  /* the candidate buffer spare slot S + i was prepared from (owner PB_PRE), or -1 */
+  int posted;                 /* candidates for the next trial were posted */
+  unsigned long long draw_mark;
+  int trial, done;            /* the current trial; the last one applied */
+  FILE *tt;                   /* FSCL_AMD_TRIAL_TRACE (development aid) */
+} pipe_t;
+
+/* a trial's permutation: the rows (or plan) and null sums, and where they are */
+typedef struct {
+  void *rows;
+  double *nul;
+  int from_spec;  /* the null sums come with it */
+  int rows_here;  /* plan mode: this trial's rows were built on the host into D.stage[slot] */
+  int use_pre;    /* it was pre-staged in spare slot use_pre (>= S), to be swapped in */
+} trial_perm_t;
+
+static void pipe_setup(pipe_t *P, scan_t *s, int n_perm, double permute_nbp, int eval_range, int bp_resl,
+                       int large_grid_sp, double scan_width_mb, fh_rand_t *g, int save) {
+  /* the bulk batches' cells get up to FSCL_AMD_BULK_SPLIT workgroups each when they are few (the
+     pruned tail), so that a bulk batch is done before its slot comes round again */
+  const int bulk_split = env_int("FSCL_AMD_BULK_SPLIT", 4, 1, INT_MAX);
+  const int n = s->n_scan_pts ? s->n_scan_pts : 1;
+  int i, k, l;
+  memset(P, 0, sizeof *P);
+  P->s = s; P->n_perm = n_perm; P->nbp = permute_nbp; P->eval_range = eval_range; P->bp_resl = bp_resl;
+  P->large_grid_sp = large_grid_sp; P->width_mb = scan_width_mb; P->g = g; P->save = save;
+  P->K = env_int("FSCL_AMD_DEPTH", 4, 2, FSCLG_N_SLOTS);
   /* row slots (and bulk batches): S >= K trials' rows on the devices (FSCL_AMD_SLOTS, at most FSCLG_N_SLOTS).
      The blocking class keeps the margin K; a bulk batch is waited only when its slot comes round, S
      trials later, and a point that may draw before its bulk results are in drains them first. */
-  const char *senv = getenv("FSCL_AMD_SLOTS");
-  const int S = senv ? (atoi(senv) < K ? K : (atoi(senv) > FSCLG_N_SLOTS ? FSCLG_N_SLOTS : atoi(senv))) : K;
-  /* the bulk batches' cells get up to FSCL_AMD_BULK_SPLIT workgroups each when they are few (the
-     pruned tail), so that a bulk batch is done before its slot comes round again */
-  const char *bsenv = getenv("FSCL_AMD_BULK_SPLIT");
-  const int bulk_split = bsenv ? (atoi(bsenv) < 1 ? 1 : atoi(bsenv)) : 4;
-  const int no_merge = getenv("FSCL_AMD_NO_MERGE") != NULL;  /* read once: every rank must decide alike */
-  int *act, n_act = s->n_scan_pts, i, k, trial = -1, done = -1;
-  pqueue_t *pq;
-  double *nul[FSCLG_N_SLOTS];
-  trial_batch_t A, Bt[FSCLG_N_SLOTS];
-  memset(&A, 0, sizeof A);
-  memset(Bt, 0, sizeof Bt);
-  A.batch = 0; /* high-priority stream */
-  for (k = 0; k < S; k++) {
-    int l;
-    Bt[k].batch = 2 + k;
-    nul[k] = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
-    for (l = 0; l < D.n_dev; l++) dev_check(fsclg_set_batch_split(D.ctx[l], Bt[k].batch, bulk_split), "batch split");
+  P->S = env_int("FSCL_AMD_SLOTS", P->K, P->K, FSCLG_N_SLOTS);
+  P->no_merge = getenv("FSCL_AMD_NO_MERGE") != NULL;  /* read once: every rank must decide alike */
+  P->n_act = s->n_scan_pts; P->trial = P->done = -1;
+  P->A.batch = 0; /* high-priority stream */
+  for (k = 0; k < P->S; k++) {
+    P->Bt[k].batch = 2 + k;
+    P->nul[k] = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
+    for (l = 0; l < D.n_dev; l++) dev_check(fsclg_set_batch_split(D.ctx[l], P->Bt[k].batch, bulk_split), "batch split");
   }
-  act = fh_malloc(sizeof(int) * (n_act ? n_act : 1), "active points");
-  pq = fh_calloc(n_act ? n_act : 1, sizeof(pqueue_t), "result queues");
-  if (D.world * D.n_dev > 1) g_pcost = fh_calloc(n_act ? n_act : 1, sizeof(double), "point costs");
-  tb_reserve(&A, n_act ? n_act : 1);
-  for (k = 0; k < S; k++) tb_reserve(&Bt[k], n_act ? n_act : 1);
-  for (i = 0; i < n_act; i++) act[i] = i;
-  FILE *tt = getenv("FSCL_AMD_TRIAL_TRACE") ? fopen(getenv("FSCL_AMD_TRIAL_TRACE"), "w") : NULL;  /* development aid */
-  double tr[8];
-  unsigned long long draw_mark = 0;
-  int posted = 0, from_spec, bi;
-  unsigned sig = 0;
-  double *pnul;
+  P->act = fh_malloc(sizeof(int) * n, "active points");
+  P->pq = fh_calloc(n, sizeof(pqueue_t), "result queues");
+  if (D.world * D.n_dev > 1) g_pcost = fh_calloc(n, sizeof(double), "point costs");
+  tb_reserve(&P->A, n);
+  for (k = 0; k < P->S; k++) tb_reserve(&P->Bt[k], n);
+  for (i = 0; i < P->n_act; i++) P->act[i] = i;
+  P->tt = getenv("FSCL_AMD_TRIAL_TRACE") ? fopen(getenv("FSCL_AMD_TRIAL_TRACE"), "w") : NULL;
   PL.on = perm_leader_wanted();
   PL.sizing = perm_leader_sizing();
   if (PL.sizing) {
@@ -1581,12 +1613,12 @@ static void permute_pipelined(scan_t *s, int n_perm, double permute_nbp, int eva
   /* the switches every rank's batches and collectives follow must agree (an environment variable
      set on one rank only would otherwise diverge the exchanges) */
   ranks_agree("FSCL_AMD_DEPTH / FSCL_AMD_SLOTS / FSCL_AMD_NO_MERGE / FSCL_AMD_PERM_LEADER / FSCL_AMD_PLAN*",
-              (uint64_t)K | (uint64_t)S << 4 | (uint64_t)no_merge << 8 | (uint64_t)PL.on << 9 | (uint64_t)PM.on << 10 |
-              (uint64_t)(PM.on ? PM.ecap : 0) << 11 | (uint64_t)(PM.on ? PM.gcap : 0) << 40);
+              (uint64_t)P->K | (uint64_t)P->S << 4 | (uint64_t)P->no_merge << 8 | (uint64_t)PL.on << 9 |
+              (uint64_t)PM.on << 10 | (uint64_t)(PM.on ? PM.ecap : 0) << 11 | (uint64_t)(PM.on ? PM.gcap : 0) << 40);
   spec_start();
   D.st.spec_threads = SP.n_th;
-  if (PL.on) pool_setup(s->n_snps, S);
-  else pb_reserve(s->n_snps, S);
+  if (PL.on) pool_setup(s->n_snps, P->S);
+  else pb_reserve(s->n_snps, P->S);
   D.st.perm_leader = PL.on;
   SP.snps = s->snps; SP.n = s->n_snps; SP.nbp = permute_nbp; SP.width_mb = scan_width_mb;
   /* pre-staging (plan mode, one process of one rank): while trial t's blocking batch runs, each of
@@ -1595,283 +1627,326 @@ static void permute_pipelined(scan_t *s, int n_perm, double permute_nbp, int eva
      trial's upload chain (plan kernels, window sums) is off its critical path.  Not with several
      ranks (the leader's candidates are not the other ranks').  FSCL_AMD_PRESTAGE=n: the n
      likeliest, in spare slots S .. S + n - 1 (0: off) */
-  const char *pse = getenv("FSCL_AMD_PRESTAGE");
-  int n_pre = pse ? atoi(pse) : 2;  /* 2: C5 one chromosome 15.1 s against 15.4 s with 1, 15.3 s with 3 */
-  if (n_pre > FSCLG_N_SLOTS - S) n_pre = FSCLG_N_SLOTS - S;
-  if (!(PM.on && D.world == 1 && !PL.on && SP.n_th > 0)) n_pre = 0;
-  if (n_pre < 0) n_pre = 0;
-  const int pre_on = n_pre > 0;
-  int pre_bi[FSCLG_N_SLOTS];  /* the candidate buffer spare slot S + i was prepared from (owner PB_PRE), or -1 */
-  for (k = 0; k < FSCLG_N_SLOTS; k++) pre_bi[k] = -1;
-  for (;;) {
-    const int slot = (trial + 1) % S;
-    trial_batch_t *B = &Bt[slot];
-    double tp = fh_now();
-    void *prow;
-    int rows_here = 0;  /* plan mode: this trial's rows were built on the host into D.stage[slot] */
-    int use_pre = 0;    /* this trial's permutation was pre-staged in spare slot use_pre (>= S), swapped in */
-    tr[0] = tp;
-    /* the slot's previous trial: its bulk results (no draws among them) */
-    if (B->submitted) {
-      tb_wait(B, pq);
-      for (k = 0; k < B->n; k++) pq_flush(s, pq, B->pt[k], done, -1, g, save);
-    }
-    D.st.search_s += fh_now() - tp;
-    tp = fh_now();
-    tr[1] = tp;
-    slot_release(slot);
-    if (PL.on && D.rank != 0) {
-      /* the leader's permutation of this trial: its rows, its null sums, and the rand() state
-         after it (the prune draws that follow are this rank's own, the same as the leader's) */
-      size_t ro, no;
-      unsigned long long nj;
-      fh_rand_t g0 = *g;
-      if (fh_pool_take(PL.pool, &ro, &no, g, &nj) != 0) logmsg(MSG_FATAL, "fscl_amd: permutation pool: no leader");
-      prow = fh_pool_data(PL.pool) + ro;
-      pnul = (double *)(fh_pool_data(PL.pool) + no);
-      from_spec = 1;  /* the null sums come with it */
-      if (PM.on && !((plan_hdr_t *)prow)->ok) {  /* a plan that did not fit: the rows, from this rank's own stream */
-        unsigned long long nj2 = 0;
-        block_permute(D.stage[slot], D.rowp, s->n_snps, permute_nbp, scan_width_mb, &g0, &nj2, NULL, 0);
-        if (memcmp(&g0, g, sizeof g0) != 0 || nj2 != nj) logmsg(MSG_FATAL, "fscl_amd: permutation pool: stream mismatch");
-        rows_here = 1;
-        D.st.plan_fallback++;
-      }
-      D.st.negj += nj;
-    } else {
-      const unsigned long long negj0 = D.st.negj;
-      /* this trial's permutation: the candidate for the previous trial's draw count, else built here */
-      bi = posted ? spec_take((int)(g_draws - draw_mark), g) : -1;
-      from_spec = bi >= 0;
-      for (k = 0; k < n_pre; k++) {
-        if (pre_bi[k] < 0) continue;
-        if (bi == pre_bi[k]) use_pre = S + k;  /* this spare slot holds the trial */
-        else {  /* not taken: free its buffer once the spare's upload has read it */
-          int l;
-          for (l = 0; l < D.n_dev; l++) dev_check(fsclg_slot_wait(D.ctx[l], S + k), "slot wait");
-          if (SP.pb[pre_bi[k]].owner == PB_PRE) SP.pb[pre_bi[k]].owner = PB_FREE;
-        }
-        pre_bi[k] = -1;
-      }
-      if (bi < 0) {
-        bi = pb_get();
-        if (PM.on) {
-          const fh_rand_t g0 = *g;
-          unsigned long long nj = 0;
-          if (plan_into(SP.pb[bi].buf, SP.plan + SPEC_MAX, permute_nbp, scan_width_mb, g, &nj, NULL, 0) == 0)
-            D.st.negj += nj;
-          else {  /* the plan did not fit its buffer: this trial's rows on the host (hdr.ok = 0 tells the ranks) */
-            *g = g0;
-            block_permute(D.stage[slot], D.rowp, s->n_snps, permute_nbp, scan_width_mb, g, &D.st.negj, NULL, 0);
-            rows_here = 1;
-            D.st.plan_fallback++;
-          }
-        } else
-          block_permute(SP.pb[bi].buf, D.rowp, s->n_snps, permute_nbp, scan_width_mb, g, &D.st.negj, NULL, 0);
-      }
-      SP.pb[bi].owner = slot;
-      prow = SP.pb[bi].buf;
-      pnul = SP.pb[bi].nul;
-      if (PL.on) {  /* the leader: complete and publish it */
-        if (!from_spec) {
-          if (PM.on) memset(pnul, 0, sizeof(double) * (D.n_chr ? D.n_chr : 1));
-          else chr_null_sums(prow, pnul);
-        }
-        from_spec = 1;
-        if (fh_pool_publish(PL.pool, (size_t)((char *)prow - fh_pool_data(PL.pool)),
-                            (size_t)((char *)pnul - fh_pool_data(PL.pool)), g, D.st.negj - negj0) != 0)
-          logmsg(MSG_FATAL, "fscl_amd: permutation pool: a rank stopped taking permutations");
-      }
-    }
-    D.st.host_perm_s += fh_now() - tp;
-    trial++;
-    for (i = k = 0; i < n_act; i++)
-      if (!s->scan_pts[act[i]].permute_finished) act[k++] = act[i];
-    n_act = k;
-    cr_logmsg(MSG_STATUS, "Scanning snp block permutations... %7d (%d scan pts remaining)        ", trial, n_act);
-    if (n_act == 0 || trial > n_perm) break;
-    tp = fh_now();
-    tr[2] = tp;
-    if (!from_spec && !PM.on) chr_null_sums(prow, pnul);  /* a candidate carries its own; plan mode reads none */
-    if (!from_spec && PM.on) memset(pnul, 0, sizeof(double) * (D.n_chr ? D.n_chr : 1));
-    D.st.host_null_s += fh_now() - tp;
-    memcpy(nul[slot], pnul, sizeof(double) * (D.n_chr ? D.n_chr : 1));
-    tp = fh_now();
-    if (rows_here) slot_upload_buf(slot, D.stage[slot], nul[slot]);
-    else if (use_pre) {
-      int l;
-      for (l = 0; l < D.n_dev; l++) dev_check(fsclg_slot_swap(D.ctx[l], slot, use_pre), "slot swap");
-      D.st.prestage_hits++;
-    } else {
-      if (PL.on && !PL.registered) {  /* the pool is not page-locked here: through the slot's own staging */
-        memcpy(D.stage[slot], prow, PM.on ? PM.bytes : (size_t)D.rb * (size_t)s->n_snps);
-        prow = D.stage[slot];
-      }
-      if (PM.on) slot_upload_plan(slot, prow, nul[slot]);
-      else slot_upload_buf(slot, prow, nul[slot]);
-    }
-    D.st.host_upload_s += fh_now() - tp;
-    tp = fh_now();
-    A.n = B->n = 0;
-    A.trial = B->trial = trial;
-    for (i = 0; i < n_act; i++) {
-      const int a = act[i];
-      const scan_pt_t *q = s->scan_pts + a;
-      trial_batch_t *b = q->permute_p + pq[a].n >= 20 - K ? &A : B;
-      fsclg_cell_t *cl = b->cells + b->n;
-      pres_t *e = pq[a].e + (pq[a].head + pq[a].n) % PQ;
-      if (pq[a].n == PQ) logmsg(MSG_FATAL, "fscl_amd: permutation pipeline queue overflow");
-      cl->chr = q->chr;
-      cl->start_pos = q->sweep_pos - (q->sweep_pos % large_grid_sp); /* Q5: G-aligned, unclipped */
-      cl->end_pos = cl->start_pos + large_grid_sp;
-      cl->pad = 0;
-      b->pt[b->n++] = a;
-      e->trial = trial; e->have = 0;
-      pq[a].n++;
-    }
-    /* a small bulk batch joins the blocking batch when the blocking batch's cells keep their full
-       split (8 members within 256 workgroups, half the launch budget, HISTORY.md §11.11): the
-       early-prune tail's few bulk cells -- the most significant points, which never reach the
-       blocking class -- would otherwise run one workgroup per cell and hold up the host K trials
-       later.  Merged in ascending point order (the blocking batch's draws go in that order; the
-       merged points cannot draw).  The decision depends only on the counts: the same on every
-       rank.  FSCL_AMD_NO_MERGE=1: never. */
-    if (B->n > 0 && A.n + B->n <= 32 * D.world * D.n_dev && !no_merge &&
-        merged_max_share(s, &A, B, eval_range) <= 32) {
-      int ia = A.n - 1, ib = B->n - 1, o = A.n + B->n - 1;
-      while (ib >= 0) {  /* merge from the back, in place in A (its capacity holds every active point) */
-        if (ia >= 0 && A.pt[ia] > B->pt[ib]) { A.pt[o] = A.pt[ia]; A.cells[o] = A.cells[ia]; ia--; }
-        else { A.pt[o] = B->pt[ib]; A.cells[o] = B->cells[ib]; ib--; }
-        o--;
-      }
-      D.st.n_merged += (unsigned long long)B->n;
-      A.n += B->n;
-      B->n = 0;
-    }
-    D.st.n_crit += (unsigned long long)A.n;
-    /* both batches always go through submit / wait (an empty share is a no-op), so that
-       every rank takes part in the same exchanges */
-    tr[3] = fh_now();
-    tb_plan(&A, eval_range);
-    tb_plan(B, eval_range);
-    trial_windows(slot, &A, B, eval_range);
-    tb_submit(&A, slot, eval_range, bp_resl);
-    tb_submit(B, slot, eval_range, bp_resl);
-    /* while the GPUs work: the next trial's permutation for this trial's likely draw counts */
-    posted = SP.n_th > 0 && !(PL.on && D.rank != 0);  /* with the leader's permutations only the leader speculates */
-    if (posted) {
-      int dl[SPEC_MAX];
-      spec_post(g, dl, spec_candidates(s, pq, &A, spec_ncand(), dl));
-    }
-    draw_mark = g_draws;
-    for (k = 0; pre_on && posted && A.n > 0 && k < n_pre; k++) {
-      /* the k-th likeliest candidate, if a worker finishes it before the blocking batch is done */
-      int st0 = 0, b0 = -1, done = 0;
-      for (;;) {
-        int l;
-        pthread_mutex_lock(&SP.mu);
-        if (SP.n_job > k) { st0 = SP.state[k]; b0 = SP.bi[k]; } else st0 = 3;
-        if (st0 == 2) SP.pb[b0].owner = PB_PRE;  /* spec_take's cancelling leaves it alone */
-        pthread_mutex_unlock(&SP.mu);
-        if (st0 >= 2) break;
-        for (done = 1, l = 0; l < D.n_dev && done; l++) done = fsclg_search_done(D.ctx[l], A.batch) > 0;
-        if (done) break;
-        sched_yield();
-      }
-      if (st0 != 2) break;
-      slot_upload_plan(S + k, SP.pb[b0].buf, SP.pb[b0].nul);
-      trial_windows(S + k, &A, B, eval_range);
-      pre_bi[k] = b0;
-      D.st.prestaged++;
-    }
-    {
-      int drain = 0, m = 0;
-      for (k = 0; k < A.n; k++) m += s->scan_pts[A.pt[k]].permute_p + pq[A.pt[k]].n >= 20;
-      tr[4] = fh_now();
-      /* the blocking batch's exchange (made every trial, even for no cells) carries each rank's
-         SIGINT flag: every rank gets the OR, so all dump at the same trial (no extra collective) */
-      sig = g_sigint ? 1u : 0u;
-      tb_wait_flags(&A, pq, &sig);
-      if (D.world <= 1 || D.sim) sig = g_sigint ? 1u : 0u;
-      tr[5] = fh_now();
-      /* a point that may draw in this trial needs every earlier result applied first */
-      for (k = 0; k < A.n && !drain; k++) {
-        const int a = A.pt[k];
-        if (s->scan_pts[a].permute_p + pq[a].n >= 20)
-          for (i = 0; i < pq[a].n; i++)
-            if (!pq[a].e[(pq[a].head + i) % PQ].have) drain = 1;
-      }
-      if (drain) { /* never expected: wait the bulk batches in trial order */
-        D.st.n_drain++;
-        for (;;) {
-          trial_batch_t *old = NULL;
-          for (k = 0; k < S; k++)
-            if (Bt[k].submitted && Bt[k].trial < trial && (!old || Bt[k].trial < old->trial)) old = &Bt[k];
-          if (!old) break;
-          tb_wait(old, pq);
-          for (k = 0; k < old->n; k++) pq_flush(s, pq, old->pt[k], trial - 1, -1, g, save);
-        }
-      }
-      for (k = 0; k < A.n; k++) pq_flush(s, pq, A.pt[k], trial, trial, g, save); /* ascending point order */
-      tr[6] = m; tr[7] = (double)(g_draws - draw_mark);
-    }
-    done = trial;
-    D.st.search_s += fh_now() - tp;
-    D.st.trials++;
-    if (tt) /* trial, active, blocking cells, bulk cells; us: bulk wait, permute, null sums + upload + build,
-               submit, blocking wait, flush; points that could draw, draws */
-      fprintf(tt, "%d %d %d %d %.0f %.0f %.0f %.0f %.0f %.0f %.0f %.0f\n", trial, n_act, A.n, B->n,
-              (tr[1] - tr[0]) * 1e6, (tr[2] - tr[1]) * 1e6, (tr[3] - tr[2]) * 1e6, (tr[4] - tr[3]) * 1e6,
-              (tr[5] - tr[4]) * 1e6, (fh_now() - tr[5]) * 1e6, tr[6], tr[7]);
-    if (sig) {
-      /* the dump shows every trial up to this one: the bulk results still in flight first
-         (no draws among them) */
-      for (;;) {
-        trial_batch_t *old = NULL;
-        for (k = 0; k < S; k++)
-          if (Bt[k].submitted && (!old || Bt[k].trial < old->trial)) old = &Bt[k];
-        if (!old) break;
-        tb_wait(old, pq);
-        for (k = 0; k < old->n; k++) pq_flush(s, pq, old->pt[k], trial, -1, g, save);
-      }
-      sigint_dump(s, n_perm);
-    }
+  P->n_pre = env_int("FSCL_AMD_PRESTAGE", 2, INT_MIN, INT_MAX);  /* 2: C5 one chromosome 15.1 s against 15.4 s with 1, 15.3 s with 3 */
+  if (P->n_pre > FSCLG_N_SLOTS - P->S) P->n_pre = FSCLG_N_SLOTS - P->S;
+  if (!(PM.on && D.world == 1 && !PL.on && SP.n_th > 0)) P->n_pre = 0;
+  if (P->n_pre < 0) P->n_pre = 0;
+  for (k = 0; k < FSCLG_N_SLOTS; k++) P->pre_bi[k] = -1;
+}
+
+static void pipe_teardown(pipe_t *P) {
+  int i, k, l;
+  for (i = 0; i < P->s->n_scan_pts; i++)
+    if (P->pq[i].n) logmsg(MSG_FATAL, "fscl_amd: permutation pipeline: unapplied results");
+  for (k = 0; k < P->n_pre; k++) {  /* the spare slots' last uploads have read their buffers (a trial that did
+                                       not come, or one taken just before the last trial ended the loop) */
+    for (l = 0; l < D.n_dev; l++) dev_check(fsclg_slot_wait(D.ctx[l], P->S + k), "slot wait");
+    if (P->pre_bi[k] >= 0 && SP.pb[P->pre_bi[k]].owner == PB_PRE) SP.pb[P->pre_bi[k]].owner = PB_FREE;
   }
-  /* the bulk batches still in flight, oldest first */
-  for (;;) {
-    trial_batch_t *old = NULL;
-    double tp = fh_now();
-    for (k = 0; k < S; k++)
-      if (Bt[k].submitted && (!old || Bt[k].trial < old->trial)) old = &Bt[k];
-    if (!old) break;
-    tb_wait(old, pq);
-    for (k = 0; k < old->n; k++) pq_flush(s, pq, old->pt[k], done, -1, g, save);
-    D.st.search_s += fh_now() - tp;
-  }
-  for (i = 0; i < s->n_scan_pts; i++)
-    if (pq[i].n) logmsg(MSG_FATAL, "fscl_amd: permutation pipeline: unapplied results");
-  for (k = 0; k < n_pre; k++) {  /* the spare slots' last uploads have read their buffers (a trial that did
-                                    not come, or one taken just before the last trial ended the loop) */
-    int l;
-    for (l = 0; l < D.n_dev; l++) dev_check(fsclg_slot_wait(D.ctx[l], S + k), "slot wait");
-    if (pre_bi[k] >= 0 && SP.pb[pre_bi[k]].owner == PB_PRE) SP.pb[pre_bi[k]].owner = PB_FREE;
-  }
-  for (k = 0; k < S; k++) slot_release(k);  /* every upload has read its buffer */
+  for (k = 0; k < P->S; k++) slot_release(k);  /* every upload has read its buffer */
   spec_quiesce();
   PL.on = 0;
   PL.sizing = 0;
   PM.on = 0;
   g_null_nt = 0;
-  if (tt) fclose(tt);
-  tb_free(&A);
-  for (k = 0; k < S; k++) {
-    int l;
-    for (l = 0; l < D.n_dev; l++) dev_check(fsclg_set_batch_split(D.ctx[l], Bt[k].batch, 1), "batch split");
-    tb_free(&Bt[k]);
-    free(nul[k]);
+  if (P->tt) fclose(P->tt);
+  tb_free(&P->A);
+  for (k = 0; k < P->S; k++) {
+    for (l = 0; l < D.n_dev; l++) dev_check(fsclg_set_batch_split(D.ctx[l], P->Bt[k].batch, 1), "batch split");
+    tb_free(&P->Bt[k]);
+    free(P->nul[k]);
   }
-  free(act); free(pq);
+  free(P->act); free(P->pq);
   free(g_pcost); g_pcost = NULL;
+}
+
+/* the oldest bulk batch still in flight of a trial before `before_trial`, or NULL */
+static trial_batch_t *oldest_bulk(pipe_t *P, int before_trial) {
+  trial_batch_t *old = NULL;
+  int k;
+  for (k = 0; k < P->S; k++)
+    if (P->Bt[k].submitted && P->Bt[k].trial < before_trial && (!old || P->Bt[k].trial < old->trial)) old = &P->Bt[k];
+  return old;
+}
+
+/* wait a bulk batch in flight and apply its points' results up to trial `upto` (no draws among them) */
+static void wait_flush_bulk(pipe_t *P, trial_batch_t *b, int upto) {
+  int k;
+  if (!b->submitted) return;
+  tb_wait(b, P->pq);
+  for (k = 0; k < b->n; k++) pq_flush(P->s, P->pq, b->pt[k], upto, -1, P->g, P->save);
+}
+
+/* the next trial's permutation, for row slot `slot`: a follower takes the leader's from the pool;
+   otherwise the candidate for the previous trial's draw count, else it is built here; a plan that
+   does not fit falls back to rows built on the host */
+static trial_perm_t trial_permutation(pipe_t *P, int slot) {
+  const scan_t *s = P->s;
+  fh_rand_t *g = P->g;
+  trial_perm_t t = {NULL, NULL, 0, 0, 0};
+  int k;
+  if (PL.on && D.rank != 0) {
+    /* the leader's permutation of this trial: its rows, its null sums, and the rand() state
+       after it (the prune draws that follow are this rank's own, the same as the leader's) */
+    size_t ro, no;
+    unsigned long long nj;
+    fh_rand_t g0 = *g;
+    if (fh_pool_take(PL.pool, &ro, &no, g, &nj) != 0) logmsg(MSG_FATAL, "fscl_amd: permutation pool: no leader");
+    t.rows = fh_pool_data(PL.pool) + ro;
+    t.nul = (double *)(fh_pool_data(PL.pool) + no);
+    t.from_spec = 1;
+    if (PM.on && !((plan_hdr_t *)t.rows)->ok) {  /* a plan that did not fit: the rows, from this rank's own stream */
+      unsigned long long nj2 = 0;
+      block_permute(D.stage[slot], D.rowp, s->n_snps, P->nbp, P->width_mb, &g0, &nj2, NULL, 0);
+      if (memcmp(&g0, g, sizeof g0) != 0 || nj2 != nj) logmsg(MSG_FATAL, "fscl_amd: permutation pool: stream mismatch");
+      t.rows_here = 1;
+      D.st.plan_fallback++;
+    }
+    D.st.negj += nj;
+  } else {
+    const unsigned long long negj0 = D.st.negj;
+    int bi = P->posted ? spec_take((int)(g_draws - P->draw_mark), g) : -1;
+    t.from_spec = bi >= 0;
+    for (k = 0; k < P->n_pre; k++) {
+      if (P->pre_bi[k] < 0) continue;
+      if (bi == P->pre_bi[k]) t.use_pre = P->S + k;  /* this spare slot holds the trial */
+      else {  /* not taken: free its buffer once the spare's upload has read it */
+        int l;
+        for (l = 0; l < D.n_dev; l++) dev_check(fsclg_slot_wait(D.ctx[l], P->S + k), "slot wait");
+        if (SP.pb[P->pre_bi[k]].owner == PB_PRE) SP.pb[P->pre_bi[k]].owner = PB_FREE;
+      }
+      P->pre_bi[k] = -1;
+    }
+    if (bi < 0) {
+      bi = pb_get();
+      if (PM.on) {
+        const fh_rand_t g0 = *g;
+        unsigned long long nj = 0;
+        if (plan_into(SP.pb[bi].buf, SP.plan + SPEC_MAX, P->nbp, P->width_mb, g, &nj, NULL, 0) == 0)
+          D.st.negj += nj;
+        else {  /* the plan did not fit its buffer: this trial's rows on the host (hdr.ok = 0 tells the ranks) */
+          *g = g0;
+          block_permute(D.stage[slot], D.rowp, s->n_snps, P->nbp, P->width_mb, g, &D.st.negj, NULL, 0);
+          t.rows_here = 1;
+          D.st.plan_fallback++;
+        }
+      } else
+        block_permute(SP.pb[bi].buf, D.rowp, s->n_snps, P->nbp, P->width_mb, g, &D.st.negj, NULL, 0);
+    }
+    SP.pb[bi].owner = slot;
+    t.rows = SP.pb[bi].buf;
+    t.nul = SP.pb[bi].nul;
+    if (PL.on) {  /* the leader: complete and publish it */
+      if (!t.from_spec) {
+        if (PM.on) memset(t.nul, 0, sizeof(double) * (D.n_chr ? D.n_chr : 1));
+        else chr_null_sums(t.rows, t.nul);
+      }
+      t.from_spec = 1;
+      if (fh_pool_publish(PL.pool, (size_t)((char *)t.rows - fh_pool_data(PL.pool)),
+                          (size_t)((char *)t.nul - fh_pool_data(PL.pool)), g, D.st.negj - negj0) != 0)
+        logmsg(MSG_FATAL, "fscl_amd: permutation pool: a rank stopped taking permutations");
+    }
+  }
+  return t;
+}
+
+/* the trial's null sums completed, and its permutation on the devices in row slot `slot`: host
+   rows, a swapped-in spare slot, a plan, or the rows (a pool that is not page-locked: through the
+   slot's own staging) */
+static void trial_upload(pipe_t *P, int slot, trial_perm_t *t) {
+  double tp = fh_now();
+  int l;
+  if (!t->from_spec && !PM.on) chr_null_sums(t->rows, t->nul);  /* a candidate carries its own; plan mode reads none */
+  if (!t->from_spec && PM.on) memset(t->nul, 0, sizeof(double) * (D.n_chr ? D.n_chr : 1));
+  D.st.host_null_s += fh_now() - tp;
+  memcpy(P->nul[slot], t->nul, sizeof(double) * (D.n_chr ? D.n_chr : 1));
+  tp = fh_now();
+  if (t->rows_here) slot_upload_buf(slot, D.stage[slot], P->nul[slot]);
+  else if (t->use_pre) {
+    for (l = 0; l < D.n_dev; l++) dev_check(fsclg_slot_swap(D.ctx[l], slot, t->use_pre), "slot swap");
+    D.st.prestage_hits++;
+  } else {
+    if (PL.on && !PL.registered) {
+      memcpy(D.stage[slot], t->rows, PM.on ? PM.bytes : (size_t)D.rb * (size_t)P->s->n_snps);
+      t->rows = D.stage[slot];
+    }
+    if (PM.on) slot_upload_plan(slot, t->rows, P->nul[slot]);
+    else slot_upload_buf(slot, t->rows, P->nul[slot]);
+  }
+  D.st.host_upload_s += fh_now() - tp;
+}
+
+/* the trial's two batches: near-critical points into the blocking batch A, the rest into the
+   slot's bulk batch B; each point's queue gets the trial's entry */
+static void trial_batches(pipe_t *P, trial_batch_t *B) {
+  const scan_t *s = P->s;
+  trial_batch_t *A = &P->A;
+  pqueue_t *pq = P->pq;
+  int i;
+  A->n = B->n = 0;
+  A->trial = B->trial = P->trial;
+  for (i = 0; i < P->n_act; i++) {
+    const int a = P->act[i];
+    const scan_pt_t *q = s->scan_pts + a;
+    trial_batch_t *b = q->permute_p + pq[a].n >= 20 - P->K ? A : B;
+    pres_t *e = pq[a].e + (pq[a].head + pq[a].n) % PQ;
+    if (pq[a].n == PQ) logmsg(MSG_FATAL, "fscl_amd: permutation pipeline queue overflow");
+    trial_cell(q, P->large_grid_sp, b->cells + b->n);
+    b->pt[b->n++] = a;
+    e->trial = P->trial; e->have = 0;
+    pq[a].n++;
+  }
+  /* a small bulk batch joins the blocking batch when the blocking batch's cells keep their full
+     split (8 members within 256 workgroups, half the launch budget, HISTORY.md §11.11): the
+     early-prune tail's few bulk cells -- the most significant points, which never reach the
+     blocking class -- would otherwise run one workgroup per cell and hold up the host K trials
+     later.  Merged in ascending point order (the blocking batch's draws go in that order; the
+     merged points cannot draw).  The decision depends only on the counts: the same on every
+     rank.  FSCL_AMD_NO_MERGE=1: never. */
+  if (B->n > 0 && A->n + B->n <= 32 * D.world * D.n_dev && !P->no_merge &&
+      merged_max_share(s, A, B, P->eval_range) <= 32) {
+    int ia = A->n - 1, ib = B->n - 1, o = A->n + B->n - 1;
+    while (ib >= 0) {  /* merge from the back, in place in A (its capacity holds every active point) */
+      if (ia >= 0 && A->pt[ia] > B->pt[ib]) { A->pt[o] = A->pt[ia]; A->cells[o] = A->cells[ia]; ia--; }
+      else { A->pt[o] = B->pt[ib]; A->cells[o] = B->cells[ib]; ib--; }
+      o--;
+    }
+    D.st.n_merged += (unsigned long long)B->n;
+    A->n += B->n;
+    B->n = 0;
+  }
+  D.st.n_crit += (unsigned long long)A->n;
+}
+
+/* while the blocking batch runs: each of the n_pre likeliest candidates for the next trial that a
+   worker finishes before the batch is done goes to a spare slot, with its window sums */
+static void prestage_candidates(pipe_t *P, trial_batch_t *B) {
+  int k;
+  for (k = 0; P->n_pre > 0 && P->posted && P->A.n > 0 && k < P->n_pre; k++) {
+    /* the k-th likeliest candidate, if a worker finishes it before the blocking batch is done */
+    int st0 = 0, b0 = -1, done = 0;
+    for (;;) {
+      int l;
+      pthread_mutex_lock(&SP.mu);
+      if (SP.n_job > k) { st0 = SP.state[k]; b0 = SP.bi[k]; } else st0 = 3;
+      if (st0 == 2) SP.pb[b0].owner = PB_PRE;  /* spec_take's cancelling leaves it alone */
+      pthread_mutex_unlock(&SP.mu);
+      if (st0 >= 2) break;
+      for (done = 1, l = 0; l < D.n_dev && done; l++) done = fsclg_search_done(D.ctx[l], P->A.batch) > 0;
+      if (done) break;
+      sched_yield();
+    }
+    if (st0 != 2) break;
+    slot_upload_plan(P->S + k, SP.pb[b0].buf, SP.pb[b0].nul);
+    trial_windows(P->S + k, &P->A, B, P->eval_range);
+    P->pre_bi[k] = b0;
+    D.st.prestaged++;
+  }
+}
+
+/* wait the blocking batch and apply it, its draws in ascending point order; returns the ranks'
+   agreed SIGINT flag.  tr[4..7]: the trace's stamps and counts */
+static unsigned trial_apply(pipe_t *P, double *tr) {
+  const scan_t *s = P->s;
+  const trial_batch_t *A = &P->A;
+  const pqueue_t *pq = P->pq;
+  trial_batch_t *old;
+  unsigned sig;
+  int drain = 0, m = 0, i, k;
+  for (k = 0; k < A->n; k++) m += s->scan_pts[A->pt[k]].permute_p + pq[A->pt[k]].n >= 20;
+  tr[4] = fh_now();
+  /* the blocking batch's exchange (made every trial, even for no cells) carries each rank's
+     SIGINT flag: every rank gets the OR, so all dump at the same trial (no extra collective) */
+  sig = g_sigint ? 1u : 0u;
+  tb_wait_flags(&P->A, P->pq, &sig);
+  if (D.world <= 1 || D.sim) sig = g_sigint ? 1u : 0u;
+  tr[5] = fh_now();
+  /* a point that may draw in this trial needs every earlier result applied first */
+  for (k = 0; k < A->n && !drain; k++) {
+    const int a = A->pt[k];
+    if (s->scan_pts[a].permute_p + pq[a].n >= 20)
+      for (i = 0; i < pq[a].n; i++)
+        if (!pq[a].e[(pq[a].head + i) % PQ].have) drain = 1;
+  }
+  if (drain) { /* never expected: wait the bulk batches in trial order */
+    D.st.n_drain++;
+    while ((old = oldest_bulk(P, P->trial))) wait_flush_bulk(P, old, P->trial - 1);
+  }
+  for (k = 0; k < A->n; k++) pq_flush(P->s, P->pq, A->pt[k], P->trial, P->trial, P->g, P->save);
+  tr[6] = m; tr[7] = (double)(g_draws - P->draw_mark);
+  return sig;
+}
+
+/* the schedule in the comment above PQ, one trial a turn */
+static void permute_pipelined(scan_t *s, int n_perm, double permute_nbp, int eval_range, int bp_resl,
+                              int large_grid_sp, double scan_width_mb, fh_rand_t *g, int save) {
+  pipe_t P;
+  trial_batch_t *old;
+  double tr[8], tp;
+  int i, k;
+  pipe_setup(&P, s, n_perm, permute_nbp, eval_range, bp_resl, large_grid_sp, scan_width_mb, g, save);
+  for (;;) {
+    const int slot = (P.trial + 1) % P.S;
+    trial_batch_t *B = &P.Bt[slot];
+    trial_perm_t pm;
+    unsigned sig;
+    tp = fh_now();
+    tr[0] = tp;
+    wait_flush_bulk(&P, B, P.done);  /* the slot's previous trial: its bulk results */
+    D.st.search_s += fh_now() - tp;
+    tp = fh_now();
+    tr[1] = tp;
+    slot_release(slot);
+    pm = trial_permutation(&P, slot);
+    D.st.host_perm_s += fh_now() - tp;
+    P.trial++;
+    for (i = k = 0; i < P.n_act; i++)
+      if (!s->scan_pts[P.act[i]].permute_finished) P.act[k++] = P.act[i];
+    P.n_act = k;
+    cr_logmsg(MSG_STATUS, "Scanning snp block permutations... %7d (%d scan pts remaining)        ", P.trial, P.n_act);
+    if (P.n_act == 0 || P.trial > n_perm) break;
+    tr[2] = fh_now();
+    trial_upload(&P, slot, &pm);
+    tp = fh_now();
+    trial_batches(&P, B);
+    /* both batches always go through submit / wait (an empty share is a no-op), so that
+       every rank takes part in the same exchanges */
+    tr[3] = fh_now();
+    tb_plan(&P.A, eval_range);
+    tb_plan(B, eval_range);
+    trial_windows(slot, &P.A, B, eval_range);
+    tb_submit(&P.A, slot, eval_range, bp_resl);
+    tb_submit(B, slot, eval_range, bp_resl);
+    /* while the GPUs work: the next trial's permutation for this trial's likely draw counts */
+    P.posted = SP.n_th > 0 && !(PL.on && D.rank != 0);  /* with the leader's permutations only the leader speculates */
+    if (P.posted) {
+      int dl[SPEC_MAX];
+      spec_post(g, dl, spec_candidates(s, P.pq, &P.A, spec_ncand(), dl));
+    }
+    P.draw_mark = g_draws;
+    prestage_candidates(&P, B);
+    sig = trial_apply(&P, tr);
+    P.done = P.trial;
+    D.st.search_s += fh_now() - tp;
+    D.st.trials++;
+    if (P.tt) /* trial, active, blocking cells, bulk cells; us: bulk wait, permute, null sums + upload + build,
+                 submit, blocking wait, flush; points that could draw, draws */
+      fprintf(P.tt, "%d %d %d %d %.0f %.0f %.0f %.0f %.0f %.0f %.0f %.0f\n", P.trial, P.n_act, P.A.n, B->n,
+              (tr[1] - tr[0]) * 1e6, (tr[2] - tr[1]) * 1e6, (tr[3] - tr[2]) * 1e6, (tr[4] - tr[3]) * 1e6,
+              (tr[5] - tr[4]) * 1e6, (fh_now() - tr[5]) * 1e6, tr[6], tr[7]);
+    if (sig) {
+      /* the dump shows every trial up to this one: the bulk results still in flight first
+         (no draws among them) */
+      while ((old = oldest_bulk(&P, INT_MAX))) wait_flush_bulk(&P, old, P.trial);
+      sigint_dump(s, n_perm);
+    }
+  }
+  /* the bulk batches still in flight, oldest first */
+  for (tp = fh_now(); (old = oldest_bulk(&P, INT_MAX)); tp = fh_now()) {
+    wait_flush_bulk(&P, old, P.done);
+    D.st.search_s += fh_now() - tp;
+  }
+  pipe_teardown(&P);
 }
 
 /* ------------------------------------------------ throughput mode (non-parity)
@@ -1913,6 +1988,12 @@ static uint64_t mix64(uint64_t z) { /* splitmix64's output function */
 static unsigned tp_trial_seed(uint64_t seed, long t) { return (unsigned)(mix64(seed ^ mix64((uint64_t)t + 1)) >> 32); }
 static int tp_prune_rand(uint64_t seed, long t, int i) { /* 31 bits, as rand() */
   return (int)(mix64(mix64(seed ^ 0x632BE59BD9B4E019ull) ^ ((uint64_t)(uint32_t)t << 32 | (uint32_t)i)) >> 33);
+}
+
+typedef struct { long t; int i; } tp_draw_t;  /* point i's prune draw in trial t */
+static int tp_draw(void *ctx) {
+  const tp_draw_t *d = ctx;
+  return tp_prune_rand(g_pseed, d->t, d->i);
 }
 
 static struct {
@@ -2024,10 +2105,8 @@ static void permute_throughput(scan_t *s, int n_perm, double permute_nbp, int ev
                                int large_grid_sp, double scan_width_mb, int save) {
   /* rounds in flight: about 8 trials in all (at least 2 rounds), so that a pruned point's
      evaluations past its prune stay few; FSCL_AMD_DEPTH overrides */
-  const char *env = getenv("FSCL_AMD_DEPTH");
   const int nd = D.n_dev, Q = D.world * nd;
-  const int K = env ? (atoi(env) < 1 ? 1 : (atoi(env) > FSCLG_N_SLOTS ? FSCLG_N_SLOTS : atoi(env)))
-                    : (Q >= 4 ? 2 : FSCLG_N_SLOTS / Q);
+  const int K = env_int("FSCL_AMD_DEPTH", Q >= 4 ? 2 : FSCLG_N_SLOTS / Q, 1, FSCLG_N_SLOTS);
   const long R = ((long)n_perm + Q) / Q; /* rounds holding trials 0 .. n_perm */
   tp_round_t rd[FSCLG_N_SLOTS];
   long r_sub = 0, r_done = 0;
@@ -2067,12 +2146,8 @@ static void permute_throughput(scan_t *s, int n_perm, double permute_nbp, int ev
       }
       for (i = 0; i < s->n_scan_pts; i++) {
         const scan_pt_t *q = s->scan_pts + i;
-        fsclg_cell_t *cl = b->cells + b->n;
         if (q->permute_finished) continue;
-        cl->chr = q->chr;
-        cl->start_pos = q->sweep_pos - (q->sweep_pos % large_grid_sp); /* Q5: G-aligned, unclipped */
-        cl->end_pos = cl->start_pos + large_grid_sp;
-        cl->pad = 0;
+        trial_cell(q, large_grid_sp, b->cells + b->n);
         b->pt[b->n++] = i;
       }
       if (b->n == 0) { stop_sub = 1; continue; }
@@ -2118,18 +2193,10 @@ static void permute_throughput(scan_t *s, int n_perm, double permute_nbp, int ev
         if (t > n_perm) break;
         for (i = 0; i < b->n; i++) {
           scan_pt_t *p = s->scan_pts + b->pt[i];
-          const double clr = o[i].clr;
+          tp_draw_t d = {t, b->pt[i]};
           if (p->permute_finished) continue; /* pruned in an earlier trial: later results dropped */
           any = 1;
-          if (clr >= p->clr) {
-            p->permute_p++;
-            if (p->permute_p >= 20 && p->permute_p / (double)p->permute_n >= tp_prune_rand(g_pseed, t, b->pt[i]) / (2147483647 + 1.0))
-              p->permute_finished = 1; /* Q7: ratio uses the pre-increment count */
-          }
-          if (p->permute_n < save) p->permute_clr[p->permute_n] = (float)clr;
-          p->permute_n++;
-          if (clr < 0 || clr > 1000000 || isnan(clr))
-            fprintf(stderr, "%d\t%d\t%g\t%1.3e\n", p->chr, b->cells[i].start_pos, clr, exp(o[i].lalpha));
+          fh_trial_apply(p, o[i].clr, o[i].lalpha, b->cells[i].start_pos, save, tp_draw, &d);
         }
         D.st.trials += any;
       }
@@ -2144,35 +2211,19 @@ static void permute_throughput(scan_t *s, int n_perm, double permute_nbp, int ev
   for (k = 0; k < FSCLG_N_SLOTS; k++) { free(rd[k].pt); free(rd[k].cells); free(rd[k].out); }
 }
 
-/* scan-chromosome.c:582-652 (with --n-threads=1 pruning semantics) */
-void scan_permute(scan_t *s, sm_ptable_t *sm, int n_perm, double permute_nbp, double alpha_factor, int n_threads,
-                  int eval_range, int bp_resl, int large_grid_sp, double scan_width_mb) {
-  fh_rand_t *g = perm_rng();
-  void *prow;
-  int *act, n_act = s->n_scan_pts, i, k, trial = -1;
-  const int save = CLR_NULL_DIST_SAVE; /* scan-chromosome.c:496 */
-  fsclg_cell_t *cells;
-  fsclg_point_t *out;
-  double *nul, t0 = fh_now();
+/* entry of a permutation test, after the caller's own refusals and prepare(): the SIGINT window
+   and handler, the chromosomes whose whole-chromosome null sums a trial reads, the permutation
+   geometry, and (g != NULL: the parity stream) the single thread's usleep() draw */
+static void permute_begin(int eval_range, double scan_width_mb, fh_rand_t *g) {
+  const char *e = getenv("FSCL_AMD_SIGINT_WINDOW_MS");
   struct sigaction sa;
-  (void)alpha_factor; (void)n_threads; /* -a is inert in the reference too (scan-chromosome.c:584) */
-  prepare(s, sm);
-  {
-    const char *e = getenv("FSCL_AMD_SIGINT_WINDOW_MS");
-    g_sigint_window = e ? atof(e) / 1e3 : 10.;
-  }
+  int i;
+  g_sigint_window = e ? atof(e) / 1e3 : 10.;
   memset(&sa, 0, sizeof sa);
   sa.sa_handler = on_sigint;
   sigemptyset(&sa.sa_mask);
   gettimeofday(&g_last_dump, NULL);
   sigaction(SIGINT, &sa, NULL);
-  for (i = 0; i < s->n_scan_pts; i++) /* points a caller built without scan_chromosome */
-    if (!s->scan_pts[i].permute_clr) s->scan_pts[i].permute_clr = fh_malloc(sizeof(float) * save, "permute_clr");
-  {
-    const char *e = getenv("FSCL_AMD_PERMUTE"); /* throughput[:seed] overrides the mode set by the API */
-    if (e && !strncmp(e, "throughput", 10)) fscl_amd_set_permute_mode(FSCL_AMD_PERMUTE_THROUGHPUT,
-                                                                       e[10] == ':' ? strtoull(e + 11, NULL, 0) : g_pseed);
-  }
   /* a trial's whole-chromosome null sums are read only where the window is the whole chromosome
      (scan-chromosome.c:75-94): the other chromosomes' sums are not computed */
   D.chr_list = fh_malloc(sizeof(int) * (D.n_chr ? D.n_chr : 1), "chromosomes");
@@ -2180,24 +2231,38 @@ void scan_permute(scan_t *s, sm_ptable_t *sm, int n_perm, double permute_nbp, do
   for (i = 0; i < D.n_chr; i++)
     if ((long long)D.chr_n[i] <= 2ll * eval_range + 1) D.chr_list[D.n_chr_list++] = i;
   perm_geom(scan_width_mb);
-  if (g_pmode == FSCL_AMD_PERMUTE_THROUGHPUT) { /* the rand() stream is not used */
-    permute_throughput(s, n_perm, permute_nbp, eval_range, bp_resl, large_grid_sp, scan_width_mb, save);
-    goto done;
-  }
-  (void)fh_rand(g); /* scan-chromosome.c:440: the single thread's usleep() draw */
-  if (!getenv("FSCL_AMD_LOCKSTEP")) {
-    permute_pipelined(s, n_perm, permute_nbp, eval_range, bp_resl, large_grid_sp, scan_width_mb, g, save);
-    goto done;
-  }
-  /* lockstep: permute -> rows to the devices -> every active cell -> prune */
-  act = fh_malloc(sizeof(int) * (n_act ? n_act : 1), "active points");
-  cells = fh_malloc(sizeof(fsclg_cell_t) * (n_act ? n_act : 1), "cells");
-  out = fh_malloc(sizeof(fsclg_point_t) * (n_act ? n_act : 1), "points");
-  nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
-  for (i = 0; i < s->n_scan_pts; i++) act[i] = i;
+  if (g) (void)fh_rand(g); /* scan-chromosome.c:440 */
+}
+
+/* exit of a permutation test begun at time t0 */
+static void permute_end(double t0) {
+  cr_logmsg(MSG_STATUS, "Scanning snp block permutations... finished.\n");
+  signal(SIGINT, SIG_DFL);
+  free(D.chr_list);
+  D.chr_list = NULL;
+  D.n_chr_list = 0;
+  set_original_rows();
+  D.st.permute_s += fh_now() - t0;
+}
+
+static int stream_draw(void *g) { return fh_rand(g); }
+
+static void eval_cell_maxima(int slot, const fsclg_cell_t *cells, int n, int g, int eval_range, fsclg_point_t *out);
+
+/* lockstep trials: permute -> rows and null sums to slot 0 of every device -> every active cell ->
+   count and prune (scan-chromosome.c:441-502).  all == NULL: a point's trial cell, searched
+   (eval_cells); else the grid test: cell all[point], its maximum over the small_grid_sp grid */
+static void permute_lockstep(scan_t *s, int n_perm, double permute_nbp, int eval_range, int bp_resl, int large_grid_sp,
+                             double scan_width_mb, fh_rand_t *g, int save, const fsclg_cell_t *all, int small_grid_sp) {
+  int n_act = s->n_scan_pts, i, k, trial = -1;
+  int *act = fh_malloc(sizeof(int) * (n_act ? n_act : 1), "active points");
+  fsclg_cell_t *cells = fh_malloc(sizeof(fsclg_cell_t) * (n_act ? n_act : 1), "cells");
+  fsclg_point_t *out = fh_malloc(sizeof(fsclg_point_t) * (n_act ? n_act : 1), "points");
+  double *nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
+  for (i = 0; i < n_act; i++) act[i] = i;
   for (;;) {
     double tp = fh_now();
-    prow = slot_stage(0);
+    void *prow = slot_stage(0);
     block_permute(prow, D.rowp, s->n_snps, permute_nbp, scan_width_mb, g, &D.st.negj, NULL, 0);
     D.st.host_perm_s += fh_now() - tp;
     trial++;
@@ -2213,42 +2278,48 @@ void scan_permute(scan_t *s, sm_ptable_t *sm, int n_perm, double permute_nbp, do
     slot_upload(0, nul);
     D.st.host_upload_s += fh_now() - tp;
     for (i = 0; i < n_act; i++) {
-      const scan_pt_t *q = s->scan_pts + act[i];
-      cells[i].chr = q->chr;
-      cells[i].start_pos = q->sweep_pos - (q->sweep_pos % large_grid_sp); /* Q5: G-aligned, unclipped */
-      cells[i].end_pos = cells[i].start_pos + large_grid_sp;
-      cells[i].pad = 0;
+      if (all) cells[i] = all[act[i]];
+      else trial_cell(s->scan_pts + act[i], large_grid_sp, cells + i);
     }
     tp = fh_now();
-    eval_cells(cells, n_act, eval_range, bp_resl, out);
+    if (all) eval_cell_maxima(0, cells, n_act, small_grid_sp, eval_range, out);
+    else eval_cells(cells, n_act, eval_range, bp_resl, out);
     D.st.search_s += fh_now() - tp;
     tp = fh_now();
     D.st.trials++;
-    for (i = 0; i < n_act; i++) { /* scan-chromosome.c:488-502, ascending point order */
-      scan_pt_t *q = s->scan_pts + act[i];
-      const double clr = out[i].clr;
-      if (clr >= q->clr) {
-        q->permute_p++;
-        if (q->permute_p >= 20 && q->permute_p / (double)q->permute_n >= fh_rand(g) / (2147483647 + 1.0))
-          q->permute_finished = 1; /* Q7: ratio uses the pre-increment count */
-      }
-      if (q->permute_n < save) q->permute_clr[q->permute_n] = (float)clr;
-      q->permute_n++;
-      if (clr < 0 || clr > 1000000 || isnan(clr))
-        fprintf(stderr, "%d\t%d\t%g\t%1.3e\n", q->chr, cells[i].start_pos, clr, exp(out[i].lalpha));
-    }
+    for (i = 0; i < n_act; i++) /* ascending point order */
+      fh_trial_apply(s->scan_pts + act[i], out[i].clr, out[i].lalpha, cells[i].start_pos, save, stream_draw, g);
     D.st.prune_s += fh_now() - tp;
     if (sigint_agreed()) sigint_dump(s, n_perm);
   }
   free(act); free(cells); free(out); free(nul);
-done:
-  cr_logmsg(MSG_STATUS, "Scanning snp block permutations... finished.\n");
-  signal(SIGINT, SIG_DFL);
-  free(D.chr_list);
-  D.chr_list = NULL;
-  D.n_chr_list = 0;
-  set_original_rows();
-  D.st.permute_s += fh_now() - t0;
+}
+
+/* scan-chromosome.c:582-652 (with --n-threads=1 pruning semantics) */
+void scan_permute(scan_t *s, sm_ptable_t *sm, int n_perm, double permute_nbp, double alpha_factor, int n_threads,
+                  int eval_range, int bp_resl, int large_grid_sp, double scan_width_mb) {
+  fh_rand_t *g = perm_rng();
+  const int save = CLR_NULL_DIST_SAVE; /* scan-chromosome.c:496 */
+  const char *e = getenv("FSCL_AMD_PERMUTE"); /* throughput[:seed] overrides the mode set by the API */
+  const double t0 = fh_now();
+  int i;
+  (void)alpha_factor; (void)n_threads; /* -a is inert in the reference too (scan-chromosome.c:584) */
+  prepare(s, sm);
+  for (i = 0; i < s->n_scan_pts; i++) /* points a caller built without scan_chromosome */
+    if (!s->scan_pts[i].permute_clr) s->scan_pts[i].permute_clr = fh_malloc(sizeof(float) * save, "permute_clr");
+  if (e && !strncmp(e, "throughput", 10))
+    fscl_amd_set_permute_mode(FSCL_AMD_PERMUTE_THROUGHPUT, e[10] == ':' ? strtoull(e + 11, NULL, 0) : g_pseed);
+  if (g_pmode == FSCL_AMD_PERMUTE_THROUGHPUT) { /* the rand() stream is not used */
+    permute_begin(eval_range, scan_width_mb, NULL);
+    permute_throughput(s, n_perm, permute_nbp, eval_range, bp_resl, large_grid_sp, scan_width_mb, save);
+  } else {
+    permute_begin(eval_range, scan_width_mb, g);
+    if (!getenv("FSCL_AMD_LOCKSTEP"))
+      permute_pipelined(s, n_perm, permute_nbp, eval_range, bp_resl, large_grid_sp, scan_width_mb, g, save);
+    else
+      permute_lockstep(s, n_perm, permute_nbp, eval_range, bp_resl, large_grid_sp, scan_width_mb, g, save, NULL, 0);
+  }
+  permute_end(t0);
 }
 
 /* --------------------------------------------------- search_maxalpha drop-in
@@ -3926,14 +3997,10 @@ void fscl_amd_scan_chromosome_grid(scan_t *s, sm_ptable_t *sm, int eval_range, i
 void fscl_amd_scan_permute_grid(scan_t *s, sm_ptable_t *sm, int n_perm, double permute_nbp, int eval_range,
                                 int small_grid_sp, int large_grid_sp, double scan_width_mb) {
   fh_rand_t *g = perm_rng();
-  void *prow;
-  int *act, n_act, n_cells = 0, i, k, trial = -1;
-  const int save = CLR_NULL_DIST_SAVE;
-  fsclg_cell_t *all, *cells;
-  fsclg_point_t *out;
-  double *nul, t0 = fh_now();
-  struct sigaction sa;
   const char *e = getenv("FSCL_AMD_PERMUTE");
+  const double t0 = fh_now();
+  fsclg_cell_t *all;
+  int n_cells = 0;
   if (D.world > 1)
     logmsg(MSG_FATAL, "fscl_amd: the grid permutation test runs in one process (not with %d ranks)", D.world);
   if (g_pmode == FSCL_AMD_PERMUTE_THROUGHPUT || (e && !strncmp(e, "throughput", 10)))
@@ -3945,74 +4012,11 @@ void fscl_amd_scan_permute_grid(scan_t *s, sm_ptable_t *sm, int n_perm, double p
                       "same spacings (-g %d -G %d)", small_grid_sp, large_grid_sp);
   all = scan_cells(s, large_grid_sp, &n_cells);
   if (n_cells != s->n_scan_pts) logmsg(MSG_FATAL, "fscl_amd: grid permutation test: %d cells, %d points", n_cells, s->n_scan_pts);
-  n_act = s->n_scan_pts;
-  {
-    const char *w = getenv("FSCL_AMD_SIGINT_WINDOW_MS");
-    g_sigint_window = w ? atof(w) / 1e3 : 10.;
-  }
-  memset(&sa, 0, sizeof sa);
-  sa.sa_handler = on_sigint;
-  sigemptyset(&sa.sa_mask);
-  gettimeofday(&g_last_dump, NULL);
-  sigaction(SIGINT, &sa, NULL);
-  D.chr_list = fh_malloc(sizeof(int) * (D.n_chr ? D.n_chr : 1), "chromosomes");
-  D.n_chr_list = 0;
-  for (i = 0; i < D.n_chr; i++)
-    if ((long long)D.chr_n[i] <= 2ll * eval_range + 1) D.chr_list[D.n_chr_list++] = i;
-  perm_geom(scan_width_mb);
-  (void)fh_rand(g); /* scan-chromosome.c:440: the single thread's usleep() draw */
-  act = fh_malloc(sizeof(int) * (n_act ? n_act : 1), "active points");
-  cells = fh_malloc(sizeof(fsclg_cell_t) * (n_act ? n_act : 1), "cells");
-  out = fh_malloc(sizeof(fsclg_point_t) * (n_act ? n_act : 1), "points");
-  nul = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
-  for (i = 0; i < s->n_scan_pts; i++) act[i] = i;
-  for (;;) {
-    double tp = fh_now();
-    prow = slot_stage(0);
-    block_permute(prow, D.rowp, s->n_snps, permute_nbp, scan_width_mb, g, &D.st.negj, NULL, 0);
-    D.st.host_perm_s += fh_now() - tp;
-    trial++;
-    for (i = k = 0; i < n_act; i++)
-      if (!s->scan_pts[act[i]].permute_finished) act[k++] = act[i];
-    n_act = k;
-    cr_logmsg(MSG_STATUS, "Scanning snp block permutations... %7d (%d scan pts remaining)        ", trial, n_act);
-    if (n_act == 0 || trial > n_perm) break;
-    tp = fh_now();
-    chr_null_sums(prow, nul);
-    D.st.host_null_s += fh_now() - tp;
-    tp = fh_now();
-    slot_upload(0, nul);
-    D.st.host_upload_s += fh_now() - tp;
-    for (i = 0; i < n_act; i++) cells[i] = all[act[i]];
-    tp = fh_now();
-    eval_cell_maxima(0, cells, n_act, small_grid_sp, eval_range, out);
-    D.st.search_s += fh_now() - tp;
-    tp = fh_now();
-    D.st.trials++;
-    for (i = 0; i < n_act; i++) { /* scan-chromosome.c:488-502, ascending point order */
-      scan_pt_t *q = s->scan_pts + act[i];
-      const double clr = out[i].clr;
-      if (clr >= q->clr) {
-        q->permute_p++;
-        if (q->permute_p >= 20 && q->permute_p / (double)q->permute_n >= fh_rand(g) / (2147483647 + 1.0))
-          q->permute_finished = 1; /* Q7: ratio uses the pre-increment count */
-      }
-      if (q->permute_n < save) q->permute_clr[q->permute_n] = (float)clr;
-      q->permute_n++;
-      if (clr < 0 || clr > 1000000 || isnan(clr))
-        fprintf(stderr, "%d\t%d\t%g\t%1.3e\n", q->chr, cells[i].start_pos, clr, exp(out[i].lalpha));
-    }
-    D.st.prune_s += fh_now() - tp;
-    if (sigint_agreed()) sigint_dump(s, n_perm);
-  }
-  free(act); free(cells); free(out); free(nul); free(all);
-  cr_logmsg(MSG_STATUS, "Scanning snp block permutations... finished.\n");
-  signal(SIGINT, SIG_DFL);
-  free(D.chr_list);
-  D.chr_list = NULL;
-  D.n_chr_list = 0;
-  set_original_rows();
-  D.st.permute_s += fh_now() - t0;
+  permute_begin(eval_range, scan_width_mb, g);
+  permute_lockstep(s, n_perm, permute_nbp, eval_range, 0, large_grid_sp, scan_width_mb, g, CLR_NULL_DIST_SAVE, all,
+                   small_grid_sp);
+  free(all);
+  permute_end(t0);
 }
 
 /* ---------------------------------------------------------------- output */

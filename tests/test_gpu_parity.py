@@ -456,9 +456,11 @@ def test_pipelined_trials_match_lockstep_and_oracle(built, tmp, monkeypatch):
     monkeypatch.delenv("FSCL_AMD_LOCKSTEP")
     # other pipeline shapes: more row slots than the blocking margin (a bulk batch waited only
     # when its slot comes round, S trials later; a point that may draw first drains them), bulk
-    # batches split over several workgroups per cell, and both with a margin of 2
+    # batches split over several workgroups per cell, and both with a margin of 2; the pruned
+    # tail's bulk batch never merged into the blocking one; no spare slot left for pre-staging
     for env in ({"FSCL_AMD_SLOTS": "8"}, {"FSCL_AMD_BULK_SPLIT": "4"}, {"FSCL_AMD_BULK_SPLIT": "1"},
-                {"FSCL_AMD_DEPTH": "2", "FSCL_AMD_SLOTS": "8", "FSCL_AMD_BULK_SPLIT": "8"}):
+                {"FSCL_AMD_DEPTH": "2", "FSCL_AMD_SLOTS": "8", "FSCL_AMD_BULK_SPLIT": "8"},
+                {"FSCL_AMD_NO_MERGE": "1"}, {"FSCL_AMD_PRESTAGE": "0", "FSCL_AMD_SLOTS": "8"}):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         scan = fscl_amd.run(snp, tmp / "s.txt", **_kw(opts))

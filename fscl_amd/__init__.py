@@ -38,6 +38,9 @@ __all__ = [
     "simulate", "simulate_scan", "simulate_output", "simulate_last_ms", "scan_free", "bootstrap", "bootstrap_output",
     "bootstrap_times", "parse_sweep", "nearest_sweep", "SWEEP_DTYPE", "BOOT_DTYPE",
     "tail_fit", "tail_runs", "tail_output", "tail_last_ms", "tail_summary", "tail_records", "TAIL_DTYPE", "TAIL_FLAGS",
+    "familywise", "familywise_runs", "familywise_combine", "familywise_output", "familywise_null_output",
+    "familywise_last_ms", "familywise_order", "familywise_threshold", "familywise_chunk", "FamilywiseT",
+    "MAXT_WG", "MAXT_TILE", "MAXT_MAX_GROUPS",
 ]
 
 ROOT = Path(__file__).resolve().parent
@@ -130,6 +133,14 @@ class TailT(C.Structure):  # fscl_amd_tail_t
                 ("kernel_ms", C.c_double), ("wall_s", C.c_double)]
 
 
+class FamilywiseT(C.Structure):  # fscl_amd_familywise_t
+    _fields_ = [("n", C.c_int), ("n_groups", C.c_int), ("trials", C.c_int), ("seed", C.c_ulonglong),
+                ("order", C.POINTER(C.c_int32)), ("c_single", C.POINTER(C.c_int32)), ("c_chr", C.POINTER(C.c_int32)),
+                ("c_step", C.POINTER(C.c_int32)), ("gmax", C.POINTER(C.c_double)), ("garg", C.POINTER(C.c_int32)),
+                ("chr_max", C.POINTER(C.c_double)), ("chr_arg", C.POINTER(C.c_int32)), ("matrix", C.POINTER(C.c_double)),
+                ("kernel_ms", C.c_double), ("wall_s", C.c_double)]
+
+
 class SurfacesT(C.Structure):  # fscl_amd_surfaces_t
     _fields_ = [("n", C.c_int), ("hdr", C.c_void_p), ("pts", C.c_void_p), ("sm", C.c_void_p), ("n_pos", C.c_size_t),
                 ("n_cells", C.c_size_t), ("n_terms", C.c_ulonglong)]
@@ -204,6 +215,11 @@ EXPORTS = [
     "fscl_amd_scan_expect", "fscl_amd_scan_point_expect", "fscl_amd_expect_runs", "fscl_amd_expect_check",
     "fscl_amd_expect_error", "fscl_amd_expect_cap", "fscl_amd_expect_bin", "fscl_amd_expect_tables_build",
     "fscl_amd_expect_output", "fscl_amd_expect_free", "fscl_amd_expect_last_ms",
+    "fsclg_maxt_submit", "fsclg_maxt_wait", "fsclg_maxt_last_ms",
+    "fscl_amd_familywise", "fscl_amd_familywise_runs", "fscl_amd_familywise_last_ms", "fscl_amd_familywise_error",
+    "fscl_amd_familywise_cap", "fscl_amd_familywise_check", "fscl_amd_familywise_free", "fscl_amd_familywise_order",
+    "fscl_amd_familywise_chunk", "fscl_amd_familywise_combine", "fscl_amd_familywise_threshold",
+    "fscl_amd_familywise_output", "fscl_amd_familywise_null_output",
 ]
 
 
@@ -346,6 +362,23 @@ def _load() -> C.CDLL:
         "fscl_amd_expect_output": (C.c_int, [C.c_char_p, P(ScanT), P(ExpectT), C.c_char_p]),
         "fscl_amd_expect_free": (None, [P(ExpectT)]),
         "fscl_amd_expect_last_ms": (C.c_double, []),
+        "fscl_amd_familywise": (C.c_int, [P(ScanT), P(SmPtableT), C.c_int, C.c_ulonglong, C.c_double, C.c_int, C.c_int, C.c_int,
+                                          C.c_double, C.c_int, P(FamilywiseT)]),
+        "fscl_amd_familywise_runs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
+        "fscl_amd_familywise_last_ms": (C.c_double, []),
+        "fscl_amd_familywise_error": (C.c_char_p, []),
+        "fscl_amd_familywise_cap": (C.c_size_t, []),
+        "fscl_amd_familywise_check": (C.c_int, [P(ScanT), C.c_int, C.c_int]),
+        "fscl_amd_familywise_free": (None, [P(FamilywiseT)]),
+        "fscl_amd_familywise_order": (None, [C.c_void_p, C.c_int, C.c_void_p]),
+        "fscl_amd_familywise_chunk": (C.c_int, [C.c_int, C.c_int, C.c_size_t]),
+        "fscl_amd_familywise_combine": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+        "fscl_amd_familywise_threshold": (C.c_int, [C.c_void_p, C.c_int, C.c_double, P(C.c_double)]),
+        "fscl_amd_familywise_output": (C.c_int, [C.c_char_p, P(ScanT), P(FamilywiseT), C.c_char_p]),
+        "fscl_amd_familywise_null_output": (C.c_int, [C.c_char_p, P(ScanT), P(FamilywiseT), C.c_char_p]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -1590,6 +1623,140 @@ def tail_last_ms() -> float:
     return float(get_lib().fscl_amd_tail_last_ms())
 
 
+# family-wise adjusted p-values from unpruned permutation maxima (include/fscl_amd.h; maxt_kernel, include/fsclg.h)
+MAXT_WG = 256            # FSCLG_MAXT_WG: threads of a trial's workgroup
+MAXT_TILE = 1024         # FSCLG_MAXT_TILE: ranks of one tile of the suffix-maximum scan
+MAXT_MAX_GROUPS = 4096   # FSCLG_MAXT_MAX_GROUPS
+
+
+def _familywise_check(r: int, what: str) -> None:
+    if r != 0:
+        msg = (get_lib().fscl_amd_familywise_error() or b"").decode()
+        raise (ValueError if r == -1 else RuntimeError)(f"{what} failed (code {r}): {msg}")
+
+
+def familywise_order(obs) -> np.ndarray:
+    """The points by observed CLR descending, ties by index ascending, a NaN last (int32).  Host only."""
+    x = np.ascontiguousarray(obs, dtype=np.float64)
+    out = np.zeros(len(x), dtype=np.int32)
+    if len(x):
+        get_lib().fscl_amd_familywise_order(x.ctypes.data, len(x), out.ctypes.data)
+    return out
+
+
+def familywise_chunk(n: int, trials: int, cap_bytes: int | None = None) -> int:
+    """The trials of one chunk: the most whose trials * n doubles fit in cap_bytes ($FSCL_AMD_FWER_CAP, default
+    2^28), at most ``trials``; 0 when one trial does not fit.  Host only."""
+    L = get_lib()
+    return int(L.fscl_amd_familywise_chunk(int(n), int(trials), int(L.fscl_amd_familywise_cap() if cap_bytes is None else cap_bytes)))
+
+
+def familywise_runs(clr, obs, group, n_groups: int | None = None, order=None) -> dict:
+    """maxt_kernel on caller arrays (fsclg_maxt_submit, in chunks under $FSCL_AMD_FWER_CAP, counts added): ``clr`` is
+    [n_trials][m], ``obs`` [m], ``group`` [m] in [0, n_groups); ``order`` defaults to familywise_order(obs).  Needs
+    no scan.  A dict of gmax, garg [n_trials], chr_max, chr_arg [n_trials][n_groups], c_single, c_chr, c_step [m]."""
+    T = np.ascontiguousarray(clr, dtype=np.float64)
+    x = np.ascontiguousarray(obs, dtype=np.float64)
+    g = np.ascontiguousarray(group, dtype=np.int32)
+    if T.ndim != 2 or T.shape[1] != len(x) or len(g) != len(x):
+        raise ValueError("clr must be [n_trials][m], with one obs and one group per point")
+    o = familywise_order(x) if order is None else np.ascontiguousarray(order, dtype=np.int32)
+    if len(o) != len(x):
+        raise ValueError("one rank per point")
+    nt, m = T.shape
+    G = int((g.max() + 1 if len(g) else 0) if n_groups is None else n_groups)
+    res = {"order": o, "gmax": np.zeros(nt), "garg": np.zeros(nt, np.int32), "chr_max": np.zeros((nt, G)),
+           "chr_arg": np.zeros((nt, G), np.int32), "c_single": np.zeros(m, np.int32), "c_chr": np.zeros(m, np.int32),
+           "c_step": np.zeros(m, np.int32), "trials": nt}
+    ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    _familywise_check(get_lib().fscl_amd_familywise_runs(ptr(T), nt, m, ptr(x), ptr(o), ptr(g), G, ptr(res["gmax"]), ptr(res["garg"]),
+                                                         ptr(res["chr_max"]), ptr(res["chr_arg"]), ptr(res["c_single"]),
+                                                         ptr(res["c_chr"]), ptr(res["c_step"])), "fscl_amd_familywise_runs")
+    return res
+
+
+def familywise(scan, tables, trials: int = 1000, seed: int = 0xFD821A6, permute_nbp: float = 0.1, eval_range: int = 81920,
+               bp_resl: int = 128, large_grid_sp: int = 100000, scan_width_mb: float = 1.0, matrix: bool = False) -> dict:
+    """The unpruned pass after scan_chromosome (include/fscl_amd.h): trial t is the throughput mode's trial t under
+    ``seed``, every scan point evaluated in every trial.  A dict of order, the counts c_single, c_chr, c_step [n], the
+    maxima gmax, garg [trials], chr_max, chr_arg [trials][chromosomes], trials, seed, kernel_ms, wall_s and, with
+    ``matrix``, familywise_matrix: T itself, [trials][n] doubles."""
+    f = FamilywiseT()
+    _familywise_check(get_lib().fscl_amd_familywise(scan, tables, int(trials), int(seed), float(permute_nbp), int(eval_range),
+                                                    int(bp_resl), int(large_grid_sp), float(scan_width_mb), int(bool(matrix)),
+                                                    C.byref(f)), "fscl_amd_familywise")
+    take = lambda p, shape, dt: (np.ctypeslib.as_array(p, shape=shape).astype(dt, copy=True)  # noqa: E731
+                                 if int(np.prod(shape)) else np.zeros(shape, dt))
+    n, G, M = f.n, f.n_groups, f.trials
+    res = {"order": take(f.order, (n,), np.int32), "c_single": take(f.c_single, (n,), np.int32),
+           "c_chr": take(f.c_chr, (n,), np.int32), "c_step": take(f.c_step, (n,), np.int32),
+           "gmax": take(f.gmax, (M,), np.float64), "garg": take(f.garg, (M,), np.int32),
+           "chr_max": take(f.chr_max, (M, G), np.float64), "chr_arg": take(f.chr_arg, (M, G), np.int32),
+           "trials": M, "seed": int(f.seed), "kernel_ms": f.kernel_ms, "wall_s": f.wall_s}
+    if matrix:
+        res["familywise_matrix"] = take(f.matrix, (M, n), np.float64)
+    get_lib().fscl_amd_familywise_free(C.byref(f))
+    return res
+
+
+def familywise_combine(c_single, c_chr, c_step, order, trials: int) -> dict:
+    """rank (from 1), p_single, p_chr and the step-down p_step of every point, from the counts.  Host only."""
+    cs, cc, ct = (np.ascontiguousarray(a, dtype=np.int32) for a in (c_single, c_chr, c_step))
+    o = np.ascontiguousarray(order, dtype=np.int32)
+    n = len(o)
+    if not (len(cs) == len(cc) == len(ct) == n) or int(trials) < 1 or sorted(o.tolist()) != list(range(n)):
+        raise ValueError("one count of each kind per point, order a permutation, trials >= 1")
+    res = {"rank": np.zeros(n, np.int32), "p_single": np.zeros(n), "p_chr": np.zeros(n), "p_step": np.zeros(n)}
+    if n:
+        get_lib().fscl_amd_familywise_combine(cs.ctypes.data, cc.ctypes.data, ct.ctypes.data, o.ctypes.data, n, int(trials),
+                                              res["rank"].ctypes.data, res["p_single"].ctypes.data, res["p_chr"].ctypes.data,
+                                              res["p_step"].ctypes.data)
+    return res
+
+
+def familywise_threshold(maxima, level: float):
+    """(k, threshold): k = floor(level (M + 1)) and the k-th largest of the M maxima; (0, None) when k = 0.  Host only."""
+    x = np.ascontiguousarray(maxima, dtype=np.float64)
+    thr = C.c_double()
+    k = int(get_lib().fscl_amd_familywise_threshold(x.ctypes.data if len(x) else None, len(x), float(level), C.byref(thr)))
+    return k, (thr.value if k > 0 else None)
+
+
+def _familywise_struct(scan, result: dict):
+    n, G = scan.contents.n_scan_pts, scan.contents.n_chromosomes
+    M = int(result["trials"])
+    a = {k: np.ascontiguousarray(result[k], dtype=np.int32) for k in ("order", "c_single", "c_chr", "c_step", "garg", "chr_arg")}
+    a.update({k: np.ascontiguousarray(result[k], dtype=np.float64) for k in ("gmax", "chr_max")})
+    if M < 1 or any(len(a[k]) != n for k in ("order", "c_single", "c_chr", "c_step")) or len(a["gmax"]) != M or \
+            len(a["garg"]) != M or a["chr_max"].size != M * G or a["chr_arg"].size != M * G:
+        raise ValueError("one count per scan point, one maximum per trial, one per trial and chromosome")
+    f = FamilywiseT()
+    f.n, f.n_groups, f.trials, f.seed = n, G, M, int(result.get("seed", 0))
+    p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    for k in ("order", "c_single", "c_chr", "c_step", "garg", "chr_arg"):
+        setattr(f, k, a[k].ctypes.data_as(p32))
+    f.gmax, f.chr_max = a["gmax"].ctypes.data_as(p64), a["chr_max"].ctypes.data_as(p64)
+    return f, a
+
+
+def familywise_output(path, scan, result: dict, label=None) -> None:
+    """The --familywise-file format (include/fscl_amd.h): a row per scan point, then the summary rows.  Host only."""
+    f, keep = _familywise_struct(scan, result)
+    if get_lib().fscl_amd_familywise_output(_b(path), scan, C.byref(f), _b(label)) != 0:
+        raise OSError(f"cannot write {path}")
+
+
+def familywise_null_output(path, scan, result: dict, label=None) -> None:
+    """The --familywise-null-file format: a row per trial.  Host only."""
+    f, keep = _familywise_struct(scan, result)
+    if get_lib().fscl_amd_familywise_null_output(_b(path), scan, C.byref(f), _b(label)) != 0:
+        raise OSError(f"cannot write {path}")
+
+
+def familywise_last_ms() -> float:
+    return float(get_lib().fscl_amd_familywise_last_ms())
+
+
 def get_stats() -> dict:
     st = Stats()
     get_lib().fscl_amd_get_stats(C.byref(st))
@@ -1682,7 +1849,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         jackknife_file=None, jackknife_top=3, jackknife_block=None, jackknife_halfwidth=None, jackknife_step=None,
         jackknife_alphas=None, conditional_file=None, given_sweeps=(), conditional_halfwidth=0, conditional_step=None,
         conditional_alphas=None, conditional_rounds=1, conditional_min_clr=0.0,
-        expect_file=None, expect_top=3, expect_sweeps=(), expect_alphas=None, expect_bins=24):
+        expect_file=None, expect_top=3, expect_sweeps=(), expect_alphas=None, expect_bins=24,
+        familywise_file=None, familywise_trials=None, familywise_seed=None, familywise_null_file=None):
     """The fscl main() pipeline (fscl.c:316-337) in-process; returns the scan_t
     pointer (points(scan) reads the results).  permute_mode "throughput": the
     counter-based permutation test (set_permute_mode).  scan_mode "grid": the CLI's
@@ -1738,6 +1906,16 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
             raise ValueError("tail_file needs the permutation test (n_permute > 0)")
         if int(tail_min_n) < 1:
             raise ValueError("tail_min_n must be >= 1")
+    if familywise_file is None and (familywise_trials is not None or familywise_seed is not None or
+                                    familywise_null_file is not None):
+        raise ValueError("familywise_trials, familywise_seed and familywise_null_file need familywise_file")
+    if familywise_file is not None:
+        familywise_trials = 1000 if familywise_trials is None else int(familywise_trials)
+        familywise_seed = 0xFD821A6 if familywise_seed is None else int(familywise_seed)
+        if familywise_trials < 1:
+            raise ValueError("familywise_trials must be at least 1")
+        if scan_mode == "grid":
+            raise ValueError("familywise_file evaluates the bisection scan's cells (not with scan_mode grid)")
     get_lib().configure_logmsg(int(verbosity))
     set_permute_mode(permute_mode, permute_seed)
     init_log_table()
@@ -1800,6 +1978,12 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         scan_output(output, scan, max_only, n_permute, label)
     if tail_file is not None:  # the CLI's --tail-file: after the permutation test and the output
         tail_output(tail_file, scan, tail_fit(scan, tail_df, tail_min_n), tail_df, label)
+    if familywise_file is not None:  # the CLI's --familywise-file: unpruned trials of its own, after the output
+        fw = familywise(scan, tab, familywise_trials, familywise_seed, permute_nbp, eval_range, bp_resl, large_grid_sp,
+                        scan_width_mb)
+        familywise_output(familywise_file, scan, fw, label)
+        if familywise_null_file is not None:
+            familywise_null_output(familywise_null_file, scan, fw, label)
     if bootstrap_file is not None:  # the CLI's --bootstrap-file, last
         win = int(large_grid_sp if bootstrap_window is None else bootstrap_window)
         if not boot_sw:  # the scan points of greatest CLR, none within the window of one already chosen

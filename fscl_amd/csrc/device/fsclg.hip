@@ -3399,6 +3399,145 @@ tail_kernel(TailParams P) {
   if (lane == 0) P.out[pt] = R;
 }
 
+// ------------------------------------------------------------ family-wise maxima (maxT)
+// The per-trial maxima and the per-point exceedance counts of a chunk of unpruned permutation trials
+// (fsclg_maxt_submit).  One workgroup per trial.  Maxima: every thread folds its strided points into a
+// running (group, maximum) pair and files it with one LDS 64-bit integer maximum when the group changes
+// (points come sorted by chromosome, so that is rare); doubles are compared as order-preserving integer
+// keys.  First argmax: a second pass files the least index whose value equals the maximum.  Counts: the
+// step-down suffix maxima u(j) = max T[order[k]], k >= j, by a tiled scan from the last rank to the
+// first -- MAXT_PER consecutive ranks per thread, a shuffle scan across the wave's threads, the waves'
+// totals through LDS (two buffers: one barrier per tile), the running maximum of the later tiles -- and
+// where a rank's point is visited its three comparisons add 1 to its counts in device memory.
+// A value enters a maximum as v + 0.0 (so a maximum of zeros is +0.0) and a NaN never does; everything
+// is comparisons and integer adds, so the result does not depend on any order of execution.
+constexpr int MAXT_WG = FSCLG_MAXT_WG, MAXT_TILE = FSCLG_MAXT_TILE, MAXT_PER = MAXT_TILE / MAXT_WG, MAXT_NW = MAXT_WG / 64;
+static_assert(MAXT_WG % 64 == 0 && MAXT_PER * MAXT_WG == MAXT_TILE, "a tile is a whole number of ranks per thread");
+struct MaxtParams {
+  const double* clr;      // [n_trials][m]
+  const double* obs;      // [m]
+  const int32_t* order;   // [m] a permutation of the points
+  const int32_t* group;   // [m] in [0, n_groups)
+  double* gmax;           // [n_trials]
+  int32_t* garg;
+  double* grp_max;        // [n_trials][n_groups]
+  int32_t* grp_arg;
+  int32_t* c_single;      // [m] each, zeroed before the launch
+  int32_t* c_chr;
+  int32_t* c_step;
+  int m, n_groups;
+};
+
+__device__ __forceinline__ unsigned long long maxt_key(double v) {
+  const long long b = __double_as_longlong(v);
+  return b < 0 ? ~(unsigned long long)b : (unsigned long long)b | 0x8000000000000000ull;
+}
+__device__ __forceinline__ double maxt_unkey(unsigned long long k) {
+  return __longlong_as_double((long long)(k >> 63 ? k & 0x7fffffffffffffffull : ~k));
+}
+
+__global__ void __launch_bounds__(MAXT_WG)
+maxt_kernel(MaxtParams P) {
+  extern __shared__ unsigned long long maxt_lds[];  // n_groups keys, then n_groups first indices
+  __shared__ unsigned long long s_gen;
+  __shared__ int s_garg;
+  __shared__ double s_wave[2][MAXT_NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m = P.m, G = P.n_groups;
+  const size_t t = blockIdx.x;
+  const double* __restrict__ T = P.clr + t * (size_t)m;
+  const double ninf = -INFINITY;
+  const unsigned long long kneg = maxt_key(ninf);
+  unsigned long long* s_key = maxt_lds;
+  int* s_arg = reinterpret_cast<int*>(maxt_lds + G);
+  for (int g = tid; g < G; g += MAXT_WG) { s_key[g] = kneg; s_arg[g] = INT_MAX; }
+  if (tid == 0) { s_gen = kneg; s_garg = INT_MAX; }
+  __syncthreads();
+  {  // the maxima
+    double best = ninf, cur = ninf;
+    int cur_g = -1;
+    for (int i = tid; i < m; i += MAXT_WG) {
+      const double raw = T[i];
+      if (raw != raw) continue;
+      const double v = raw + 0.0;
+      const int g = P.group[i];
+      if (g != cur_g) {
+        if (cur_g >= 0) atomicMax(&s_key[cur_g], maxt_key(cur));
+        cur_g = g; cur = v;
+      } else cur = fmax(cur, v);
+      best = fmax(best, v);
+    }
+    if (cur_g >= 0) atomicMax(&s_key[cur_g], maxt_key(cur));
+    best = tail_wave_max(best);
+    if (lane == 0) atomicMax(&s_gen, maxt_key(best));
+  }
+  __syncthreads();
+  const double gen = maxt_unkey(s_gen);
+  {  // their first indices (a NaN equals nothing)
+    int first = INT_MAX;
+    for (int i = tid; i < m; i += MAXT_WG) {
+      const double v = T[i] + 0.0;
+      const int g = P.group[i];
+      if (v == maxt_unkey(s_key[g]) && i < reinterpret_cast<volatile int*>(s_arg)[g]) atomicMin(&s_arg[g], i);
+      if (v == gen && i < first) first = i;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+    if (lane == 0 && first != INT_MAX) atomicMin(&s_garg, first);
+  }
+  __syncthreads();
+  for (int g = tid; g < G; g += MAXT_WG) {
+    const int a = s_arg[g];
+    P.grp_max[t * (size_t)G + g] = maxt_unkey(s_key[g]);
+    P.grp_arg[t * (size_t)G + g] = a == INT_MAX ? -1 : a;
+  }
+  if (tid == 0) { P.gmax[t] = gen; P.garg[t] = s_garg == INT_MAX ? -1 : s_garg; }
+  // the suffix maxima in rank order, last tile first, and the counts
+  double carry = ninf;
+  const int n_tiles = (m + MAXT_TILE - 1) / MAXT_TILE;
+  for (int tile = n_tiles - 1, it = 0; tile >= 0; tile--, it++) {
+    const int j0 = tile * MAXT_TILE + tid * MAXT_PER;
+    double v[MAXT_PER];
+    int idx[MAXT_PER];
+#pragma unroll
+    for (int k = 0; k < MAXT_PER; k++) {
+      idx[k] = j0 + k < m ? P.order[j0 + k] : -1;
+      const double raw = idx[k] >= 0 ? T[idx[k]] : ninf;
+      v[k] = raw != raw ? ninf : raw + 0.0;
+    }
+#pragma unroll
+    for (int k = MAXT_PER - 2; k >= 0; k--) v[k] = fmax(v[k], v[k + 1]);
+    double s = v[0];  // the maximum over this thread's ranks and the later threads' of the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const double x = __shfl_down(s, o, 64);
+      if (lane + o < 64) s = fmax(s, x);
+    }
+    double ex = __shfl_down(s, 1, 64);  // the later threads' alone
+    if (lane == 63) ex = ninf;
+    if (lane == 0) s_wave[it & 1][wave] = s;
+    __syncthreads();
+    double all = carry;
+    ex = fmax(ex, carry);
+#pragma unroll
+    for (int w = 0; w < MAXT_NW; w++) {
+      const double x = s_wave[it & 1][w];
+      all = fmax(all, x);
+      if (w > wave) ex = fmax(ex, x);
+    }
+    carry = all;
+#pragma unroll
+    for (int k = 0; k < MAXT_PER; k++) {
+      const int i = idx[k];
+      if (i < 0) continue;
+      const double o = P.obs[i];
+      if (fmax(v[k], ex) >= o) atomicAdd(&P.c_step[i], 1);
+      if (gen >= o) atomicAdd(&P.c_single[i], 1);
+      if (maxt_unkey(s_key[P.group[i]]) >= o) atomicAdd(&P.c_chr[i], 1);
+    }
+  }
+}
+
 // ------------------------------------------------------------ window null sums
 // init_scan_result's window sum (scan-chromosome.c:92-94) for every window start of the
 // chromosomes longer than the window: acc = 0.0; acc += null_logl[i] for i = ws..ws+W-1,
@@ -3988,10 +4127,10 @@ struct Slot {
 
 // what a batch holds between a submit and its wait
 enum BatchKind { BK_NONE, BK_SEARCH, BK_PROFILE, BK_CELLMAX, BK_CURVE, BK_SITES, BK_SAMPLE, BK_TAIL, BK_SURFACE,
-                 BK_BLOCKS, BK_COND, BK_EXPECT, BK_COUNT };
+                 BK_BLOCKS, BK_COND, BK_EXPECT, BK_MAXT, BK_COUNT };
 
 // One call of any kind in flight (a submit / wait pair: search, profile, cell maxima, curves, site
-// terms, sample, tail fit, surface, block sums, conditional scan, expected terms): its stream and events, the state
+// terms, sample, tail fit, surface, block sums, conditional scan, expected terms, family-wise maxima): its stream and events, the state
 // every kind shares (what it holds, on which slot, how many results, each kind's last kernel time),
 // a search's host-side dedup / ordering of its cells, and the buffers of each kind.  A kind adds its
 // buffers here and nothing else: the protocol is batch_reset / launch_bracket / batch_hold in its
@@ -4074,6 +4213,15 @@ struct Batch {
   Buf<fsclg_expect_tot_t, PINNED> p_xtot;
   int x_nbins = 0;                  // bins of the submitted call
   size_t x_sites = 0;               // its (task, site) pairs, known once the headers are in (st_synced)
+  // fsclg_maxt_submit: the chunk, the observed values, the rank order and the groups (staging, copied to
+  // their device arrays on the batch's stream); the maxima (the genome's [n_trials], then the groups'
+  // [n_trials][n_groups]), their first indices, and the three counts [3][m] (device memory, copied back
+  // to their staging after the kernel)
+  Buf<double, PINNED> p_mclr, p_mobs, p_mmax;
+  Buf<int32_t, PINNED> p_mord, p_mgrp, p_marg, p_mcnt;
+  Buf<double, DEVICE> d_mclr, d_mobs, d_mmax;
+  Buf<int32_t, DEVICE> d_mord, d_mgrp, d_marg, d_mcnt;
+  int mx_trials = 0, mx_m = 0, mx_groups = 0;  // of the submitted call
 };
 
 struct fsclg_ctx {
@@ -5633,7 +5781,7 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
       "the batch holds site terms (fsclg_sites_wait)", "the batch holds a sample (fsclg_sample_wait)",
       "the batch holds a tail fit (fsclg_tail_wait)", "the batch holds surfaces (fsclg_surface_wait)",
       "the batch holds block sums (fsclg_blocks_wait)", "the batch holds a conditional scan (fsclg_cond_wait)",
-      "the batch holds expected terms (fsclg_expect_wait)"};
+      "the batch holds expected terms (fsclg_expect_wait)", "the batch holds family-wise maxima (fsclg_maxt_wait)"};
   if (B.holds != BK_SEARCH) return set_err(FSCLG_E_STATE, other[B.holds]);
   if (!out && B.n_cells) return set_err(FSCLG_E_ARG, "out");
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
@@ -6679,6 +6827,107 @@ int fsclg_tail_wait(fsclg_ctx* c, int batch, fsclg_tail_t* out) {
 }
 
 double fsclg_tail_last_ms(fsclg_ctx* c, int batch) { return last_ms(c, batch, BK_TAIL); }
+
+// ------------------------------------------------------------ family-wise maxima (host side)
+int fsclg_maxt_submit(fsclg_ctx* c, int batch, const double* clr, int n_trials, int m, const double* obs,
+                      const int32_t* order, const int32_t* group, int n_groups) {
+  if (!c || n_trials < 0 || m < 0 || n_groups < 0 || (m && (!obs || !order || !group)) || (n_trials && m && !clr))
+    return set_err(FSCLG_E_ARG, "maxt");
+  if (n_groups > FSCLG_MAXT_MAX_GROUPS) return set_err(FSCLG_E_ARG, "maxt: more than FSCLG_MAXT_MAX_GROUPS groups");
+  if (batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
+  if ((size_t)n_trials * (size_t)(n_groups + 1) > (size_t)0x7fffffff)
+    return set_err(FSCLG_E_ARG, "maxt: more than 2^31 - 1 maxima in one call");
+  Batch& B = c->batch[batch];
+  if (B.holds) return set_err(FSCLG_E_STATE, "batch not waited for");
+  {
+    std::vector<unsigned char> seen((size_t)m, 0);
+    for (int i = 0; i < m; i++) {
+      if (group[i] < 0 || group[i] >= n_groups) return set_err(FSCLG_E_ARG, "maxt: a point's group lies outside [0, n_groups)");
+      if (order[i] < 0 || order[i] >= m || seen[order[i]]) return set_err(FSCLG_E_ARG, "maxt: order is not a permutation of the points");
+      seen[order[i]] = 1;
+    }
+  }
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  const size_t nm = (size_t)n_trials * (size_t)m, nx = (size_t)n_trials * (size_t)(n_groups + 1), sm = (size_t)m;
+  int r;
+  if ((r = B.p_mclr.ensure(nm))) return r;
+  if ((r = B.p_mobs.ensure(sm))) return r;
+  if ((r = B.p_mord.ensure(sm))) return r;
+  if ((r = B.p_mgrp.ensure(sm))) return r;
+  if ((r = B.p_mmax.ensure(nx))) return r;
+  if ((r = B.p_marg.ensure(nx))) return r;
+  if ((r = B.p_mcnt.ensure(3 * sm))) return r;
+  if ((r = B.d_mclr.ensure(std::max(nm, (size_t)1), "hipMalloc maxt chunk"))) return r;  // (never NULL)
+  if ((r = B.d_mobs.ensure(std::max(sm, (size_t)1), "hipMalloc maxt observed"))) return r;
+  if ((r = B.d_mord.ensure(std::max(sm, (size_t)1), "hipMalloc maxt order"))) return r;
+  if ((r = B.d_mgrp.ensure(std::max(sm, (size_t)1), "hipMalloc maxt groups"))) return r;
+  if ((r = B.d_mmax.ensure(std::max(nx, (size_t)1), "hipMalloc maxt maxima"))) return r;
+  if ((r = B.d_marg.ensure(std::max(nx, (size_t)1), "hipMalloc maxt maxima"))) return r;
+  if ((r = B.d_mcnt.ensure(std::max(3 * sm, (size_t)1), "hipMalloc maxt counts"))) return r;
+  if (nm) {
+    memcpy(B.p_mclr, clr, sizeof(double) * nm);
+    HIPCHK(hipMemcpyAsync(B.d_mclr, B.p_mclr, sizeof(double) * nm, hipMemcpyHostToDevice, B.stream), "hipMemcpyAsync maxt chunk");
+  }
+  if (m) {
+    memcpy(B.p_mobs, obs, sizeof(double) * sm);
+    memcpy(B.p_mord, order, sizeof(int32_t) * sm);
+    memcpy(B.p_mgrp, group, sizeof(int32_t) * sm);
+    HIPCHK(hipMemcpyAsync(B.d_mobs, B.p_mobs, sizeof(double) * sm, hipMemcpyHostToDevice, B.stream), "hipMemcpyAsync maxt observed");
+    HIPCHK(hipMemcpyAsync(B.d_mord, B.p_mord, sizeof(int32_t) * sm, hipMemcpyHostToDevice, B.stream), "hipMemcpyAsync maxt order");
+    HIPCHK(hipMemcpyAsync(B.d_mgrp, B.p_mgrp, sizeof(int32_t) * sm, hipMemcpyHostToDevice, B.stream), "hipMemcpyAsync maxt groups");
+    HIPCHK(hipMemsetAsync(B.d_mcnt, 0, sizeof(int32_t) * 3 * sm, B.stream), "hipMemsetAsync maxt counts");
+  }
+  MaxtParams P;
+  P.clr = B.d_mclr; P.obs = B.d_mobs; P.order = B.d_mord; P.group = B.d_mgrp;
+  P.gmax = B.d_mmax; P.grp_max = B.d_mmax.p + n_trials; P.garg = B.d_marg; P.grp_arg = B.d_marg.p + n_trials;
+  P.c_single = B.d_mcnt; P.c_chr = B.d_mcnt.p + sm; P.c_step = B.d_mcnt.p + 2 * sm;
+  P.m = m; P.n_groups = n_groups;
+  batch_reset(B, BK_MAXT, -1);
+  B.n_res = n_trials; B.mx_trials = n_trials; B.mx_m = m; B.mx_groups = n_groups;
+  HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
+  if (n_trials) {
+    hipLaunchKernelGGL(maxt_kernel, dim3((unsigned)n_trials), dim3(MAXT_WG), (sizeof(unsigned long long) + sizeof(int)) * (size_t)n_groups,
+                       B.stream, P);
+    HIPCHK(hipGetLastError(), "launch maxt_kernel");
+  }
+  HIPCHK(hipEventRecord(B.ev1, B.stream), "hipEventRecord");
+  if (nx) {
+    HIPCHK(hipMemcpyAsync(B.p_mmax, B.d_mmax, sizeof(double) * nx, hipMemcpyDeviceToHost, B.stream), "hipMemcpyAsync maxt maxima");
+    HIPCHK(hipMemcpyAsync(B.p_marg, B.d_marg, sizeof(int32_t) * nx, hipMemcpyDeviceToHost, B.stream), "hipMemcpyAsync maxt maxima");
+  }
+  if (m) HIPCHK(hipMemcpyAsync(B.p_mcnt, B.d_mcnt, sizeof(int32_t) * 3 * sm, hipMemcpyDeviceToHost, B.stream), "hipMemcpyAsync maxt counts");
+  HIPCHK(hipEventRecord(B.ev2, B.stream), "hipEventRecord");
+  return batch_hold(c, B, BK_MAXT);
+}
+
+int fsclg_maxt_wait(fsclg_ctx* c, int batch, double* gmax, int32_t* garg, double* grp_max, int32_t* grp_arg, int32_t* c_single,
+                    int32_t* c_chr, int32_t* c_step) {
+  if (!c || batch < 0 || batch >= NBATCH) return set_err(FSCLG_E_ARG, "batch");
+  Batch& B = c->batch[batch];
+  if (B.holds != BK_MAXT) return set_err(FSCLG_E_STATE, "no family-wise maxima submitted on the batch");
+  const size_t nt = (size_t)B.mx_trials, sm = (size_t)B.mx_m, ng = (size_t)B.mx_groups;
+  if ((nt && (!gmax || !garg)) || (nt * ng && (!grp_max || !grp_arg)) || (sm && (!c_single || !c_chr || !c_step)))
+    return set_err(FSCLG_E_ARG, "out");  // (the batch stays submitted)
+  int r;
+  if ((r = batch_finish(c, B, BK_MAXT, true))) return r;  // (the events are recorded around no launch too)
+  HIPCHK(hipEventSynchronize(B.ev2), "hipEventSynchronize");
+  if (nt) {
+    memcpy(gmax, B.p_mmax, sizeof(double) * nt);
+    memcpy(garg, B.p_marg, sizeof(int32_t) * nt);
+  }
+  if (nt * ng) {
+    memcpy(grp_max, B.p_mmax.p + nt, sizeof(double) * nt * ng);
+    memcpy(grp_arg, B.p_marg.p + nt, sizeof(int32_t) * nt * ng);
+  }
+  if (sm) {
+    memcpy(c_single, B.p_mcnt, sizeof(int32_t) * sm);
+    memcpy(c_chr, B.p_mcnt.p + sm, sizeof(int32_t) * sm);
+    memcpy(c_step, B.p_mcnt.p + 2 * sm, sizeof(int32_t) * sm);
+  }
+  return FSCLG_OK;
+}
+
+double fsclg_maxt_last_ms(fsclg_ctx* c, int batch) { return last_ms(c, batch, BK_MAXT); }
 
 int fsclg_interval_thresholds(double log_ad_step, int n_iv, double* thr) {
   if (!thr || n_iv <= 0 || !(log_ad_step > 0)) return set_err(FSCLG_E_ARG, "thresholds");

@@ -12,6 +12,7 @@ void *fh_malloc(size_t n, const char *where);
 void *fh_calloc(size_t n, size_t m, const char *where);
 void *fh_realloc(void *p, size_t n, const char *where);
 double fh_now(void);
+void fh_familywise_set_error(const char *msg); /* familywise.c: what fscl_amd_familywise_error returns */
 
 /* glibc random_r TYPE_3 stream (the reference draws glibc rand(), seeded by
    srand(0xFD821A6) at fscl.c:135); own state so ranks and speculation can

@@ -137,6 +137,8 @@ int main(int argc, char **argv) {
   int jackknife_top = 3, jackknife_block = -1, jackknife_halfwidth = -1, jackknife_step = -1, jackknife_n = 33;
   double jackknife_lo = LOG_AD_MIN, jackknife_hi = LOG_AD_MAX;
   int tail_df = 2, tail_min_n = 20;
+  char *fw_fname = NULL, *fw_trials_s = NULL, *fw_seed_s = NULL, *fw_null_fname = NULL; /* (NULL: not given) */
+  int fw_trials = 1000;
   char *expect_fname = NULL, *expect_alphas = NULL, *expect_top_s = NULL, *expect_bins_s = NULL; /* (NULL: not given) */
   strlist_t expect_sweep = {NULL, 0};
   int expect_top = 3, expect_bins = 24, expect_n = -1;
@@ -240,6 +242,13 @@ int main(int argc, char **argv) {
                                                   "value); the sweep's own alpha is added"},
       {0, "expect-bins", &expect_bins_s, T_STR, "equal-width bins of log(alpha d) over [-20, 4] in --expect-file (1 .. 64, default 24)"},
       {0, "tail-min-n", &tail_min_n, T_INT, "--tail-file fits a point with at least this many positive null CLRs (default 20)"},
+      {0, "familywise-file", &fw_fname, T_STR, "after the permutation test and the output, write every scan point's family-wise adjusted "
+                                               "p-values (Westfall-Young maxT over unpruned permutation trials: single-step, per "
+                                               "chromosome and step-down) and the genome-wide CLR thresholds to this file"},
+      {0, "familywise-trials", &fw_trials_s, T_STR, "unpruned trials of --familywise-file, each a full scan (default 1000; at least 1)"},
+      {0, "familywise-seed", &fw_seed_s, T_STR, "seed of the --familywise-file permutations, those of the throughput mode under this "
+                                                "seed (default 0xFD821A6)"},
+      {0, "familywise-null-file", &fw_null_fname, T_STR, "write every --familywise-file trial's genome and chromosome maxima to this file"},
       {0, NULL, NULL, 0, NULL}};
 
   spline_pts = N_SPLINE_KNOTS;
@@ -380,6 +389,27 @@ int main(int argc, char **argv) {
     stop = 1;
   }
   if (tail_fname && tail_min_n < 1) { logmsg(MSG_ERROR, "Error: --tail-min-n must be >= 1.\n"); stop = 1; }
+  if (!fw_fname && (fw_trials_s || fw_seed_s || fw_null_fname)) {
+    logmsg(MSG_ERROR, "Error: --familywise-trials, --familywise-seed and --familywise-null-file need --familywise-file.\n");
+    stop = 1;
+  }
+  if (fw_trials_s) {
+    char *end;
+    const long v = strtol(fw_trials_s, &end, 10);
+    if (end == fw_trials_s || *end || v < 1 || v > 100000000) {
+      logmsg(MSG_ERROR, "Error: --familywise-trials must be an integer >= 1 (not \"%s\").\n", fw_trials_s);
+      stop = 1;
+    } else fw_trials = (int)v;
+  }
+  if (fw_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --familywise-file needs the scan (not with --no-scan).\n"); stop = 1; }
+  if (fw_fname && grid_mode) {
+    logmsg(MSG_ERROR, "Error: --familywise-file evaluates the bisection scan's cells (not with --scan-mode=grid).\n");
+    stop = 1;
+  }
+  if (fw_fname && getenv("WORLD_SIZE") && getenv("RANK") && atoi(getenv("WORLD_SIZE")) > 1) {
+    logmsg(MSG_ERROR, "Error: --familywise-file runs in one process (not with WORLD_SIZE=%s ranks).\n", getenv("WORLD_SIZE"));
+    stop = 1;
+  }
   if (surface_fname && dont_scan) { logmsg(MSG_ERROR, "Error: --surface-file needs the scan (not with --no-scan).\n"); stop = 1; }
   if (surface_top < 0) { logmsg(MSG_ERROR, "Error: --surface-top must be >= 0.\n"); stop = 1; }
   if (surface_halfwidth < 0) surface_halfwidth = surface_halfwidth == -1 ? large_grid_sp : -2;
@@ -525,6 +555,9 @@ int main(int argc, char **argv) {
     }
     if (expect_fname && fscl_amd_expect_check(s, expect_req, expect_sweep.n, expect_la, expect_n_la, expect_bins) != 0)
       logmsg(MSG_FATAL, "fscl: %s", fscl_amd_expect_error());
+    /* every host-only refusal of --familywise-file, before any device work */
+    if (fw_fname && fscl_amd_familywise_check(s, large_grid_sp, fw_trials) != 0)
+      logmsg(MSG_FATAL, "fscl: --familywise-file: %s", fscl_amd_familywise_error());
     if (ws && rk && atoi(ws) > 1) {
       /* one process per GPU (e.g. under torch.distributed.run): GPU $LOCAL_RANK (or
          $FSCL_AMD_DEVICE), results exchanged through a shared-memory segment named by
@@ -687,6 +720,21 @@ int main(int argc, char **argv) {
                          "with permute_p >= 5: median log10(p_tail / p_empirical) = %.3f\n", tail_df, tl.n_fit, tl.n_central,
              tl.n_nofit, tl.kernel_ms, tl.wall_s, tl.n_calibration, tl.calibration);
       fscl_amd_tail_free(&tl);
+    }
+    if (fw_fname) {
+      /* the family-wise adjusted p-values, from unpruned trials of their own; no rand() draw, no record touched */
+      fscl_amd_familywise_t fw;
+      const unsigned long long fw_seed = fw_seed_s ? strtoull(fw_seed_s, NULL, 0) : 0xFD821A6ull;
+      const int r = fscl_amd_familywise(s, sm, fw_trials, fw_seed, permute_nbp, eval_range, bp_resl, large_grid_sp, scan_width_mb,
+                                        0, &fw);
+      if (r != 0) logmsg(MSG_FATAL, "fscl: family-wise maxima failed (code %d): %s", r, fscl_amd_familywise_error());
+      if (fscl_amd_familywise_output(fw_fname, s, &fw, prepend_label) != 0) logmsg(MSG_FATAL, "fscl: cannot write %s", fw_fname);
+      if (fw_null_fname && fscl_amd_familywise_null_output(fw_null_fname, s, &fw, prepend_label) != 0)
+        logmsg(MSG_FATAL, "fscl: cannot write %s", fw_null_fname);
+      logmsg(MSG_STATUS, "Family-wise maxima: M %d unpruned trials of %d points, maxt kernel %.3f ms, %.3f s in all, %.0f grid points x "
+                         "trials per second\n", fw.trials, fw.n, fw.kernel_ms, fw.wall_s,
+             fw.wall_s > 0 ? (double)fw.n * (double)fw.trials / fw.wall_s : 0.0);
+      fscl_amd_familywise_free(&fw);
     }
     if (bootstrap_fname) {
       /* the parametric bootstrap, last: simulate under the sweeps, rescan, summarise */

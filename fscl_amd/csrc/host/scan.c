@@ -19,6 +19,7 @@
 #include <pthread.h>
 #include <sched.h>
 #include <signal.h>
+#include <stdarg.h>
 #include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -2211,19 +2212,10 @@ static void permute_throughput(scan_t *s, int n_perm, double permute_nbp, int ev
   for (k = 0; k < FSCLG_N_SLOTS; k++) { free(rd[k].pt); free(rd[k].cells); free(rd[k].out); }
 }
 
-/* entry of a permutation test, after the caller's own refusals and prepare(): the SIGINT window
-   and handler, the chromosomes whose whole-chromosome null sums a trial reads, the permutation
-   geometry, and (g != NULL: the parity stream) the single thread's usleep() draw */
-static void permute_begin(int eval_range, double scan_width_mb, fh_rand_t *g) {
-  const char *e = getenv("FSCL_AMD_SIGINT_WINDOW_MS");
-  struct sigaction sa;
+/* what every trial's rows need (the permutation tests and the family-wise pass): the chromosomes
+   whose whole-chromosome null sums a trial reads, and the permutation geometry */
+static void trial_rows_begin(int eval_range, double scan_width_mb) {
   int i;
-  g_sigint_window = e ? atof(e) / 1e3 : 10.;
-  memset(&sa, 0, sizeof sa);
-  sa.sa_handler = on_sigint;
-  sigemptyset(&sa.sa_mask);
-  gettimeofday(&g_last_dump, NULL);
-  sigaction(SIGINT, &sa, NULL);
   /* a trial's whole-chromosome null sums are read only where the window is the whole chromosome
      (scan-chromosome.c:75-94): the other chromosomes' sums are not computed */
   D.chr_list = fh_malloc(sizeof(int) * (D.n_chr ? D.n_chr : 1), "chromosomes");
@@ -2231,6 +2223,29 @@ static void permute_begin(int eval_range, double scan_width_mb, fh_rand_t *g) {
   for (i = 0; i < D.n_chr; i++)
     if ((long long)D.chr_n[i] <= 2ll * eval_range + 1) D.chr_list[D.n_chr_list++] = i;
   perm_geom(scan_width_mb);
+}
+
+/* ... and their end: the original rows are back on every device */
+static void trial_rows_end(void) {
+  free(D.chr_list);
+  D.chr_list = NULL;
+  D.n_chr_list = 0;
+  set_original_rows();
+}
+
+/* entry of a permutation test, after the caller's own refusals and prepare(): the SIGINT window
+   and handler, the trials' rows (trial_rows_begin), and (g != NULL: the parity stream) the single
+   thread's usleep() draw */
+static void permute_begin(int eval_range, double scan_width_mb, fh_rand_t *g) {
+  const char *e = getenv("FSCL_AMD_SIGINT_WINDOW_MS");
+  struct sigaction sa;
+  g_sigint_window = e ? atof(e) / 1e3 : 10.;
+  memset(&sa, 0, sizeof sa);
+  sa.sa_handler = on_sigint;
+  sigemptyset(&sa.sa_mask);
+  gettimeofday(&g_last_dump, NULL);
+  sigaction(SIGINT, &sa, NULL);
+  trial_rows_begin(eval_range, scan_width_mb);
   if (g) (void)fh_rand(g); /* scan-chromosome.c:440 */
 }
 
@@ -2238,10 +2253,7 @@ static void permute_begin(int eval_range, double scan_width_mb, fh_rand_t *g) {
 static void permute_end(double t0) {
   cr_logmsg(MSG_STATUS, "Scanning snp block permutations... finished.\n");
   signal(SIGINT, SIG_DFL);
-  free(D.chr_list);
-  D.chr_list = NULL;
-  D.n_chr_list = 0;
-  set_original_rows();
+  trial_rows_end();
   D.st.permute_s += fh_now() - t0;
 }
 
@@ -3941,6 +3953,223 @@ int fscl_amd_tail_fit(scan_t *s, int df, int min_n, fscl_amd_tail_t *out) {
   else fscl_amd_tail_free(out);
   out->wall_s = fh_now() - t0;
   return r;
+}
+
+/* ------------------------------------------------------ family-wise adjusted p-values (--familywise-file)
+   Unpruned permutation trials (the throughput mode's permutations, every point in every trial) and
+   their reduction by fsclg_maxt_submit on the first device.  The host-only pieces are in
+   familywise.c. */
+static double g_fw_ms;
+double fscl_amd_familywise_last_ms(void) { return g_fw_ms; }
+
+static int familywise_refuse(int code, const char *fmt, ...) {
+  char msg[256];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(msg, sizeof msg, fmt, ap);
+  va_end(ap);
+  fh_familywise_set_error(msg);
+  return code;
+}
+
+/* The reduction of T, chunk by chunk, on batch 0 of the first device: a full chunk is submitted (the
+   shim copies it, so its buffer is free again) and waited for only before the next one is submitted
+   or at the end, so that the trials go on meanwhile.  The maxima land at their trials; the counts of
+   the chunks are added (integers: any chunking gives the same sums). */
+typedef struct {
+  int m, G;
+  const double *obs;
+  const int32_t *order, *group;
+  double *gmax, *grp_max;
+  int32_t *garg, *grp_arg, *c_single, *c_chr, *c_step;
+  int32_t *tmp;     /* [3 m]: one chunk's counts */
+  int pending, t0;  /* a chunk is submitted: its first trial */
+} maxt_acc_t;
+
+static int maxt_drain(maxt_acc_t *A) {
+  const size_t m = (size_t)A->m;
+  size_t i;
+  int r;
+  if (!A->pending) return FSCLG_OK;
+  A->pending = 0;
+  r = fsclg_maxt_wait(D.ctx[0], 0, A->gmax + A->t0, A->garg + A->t0, A->grp_max + (size_t)A->t0 * (size_t)A->G,
+                      A->grp_arg + (size_t)A->t0 * (size_t)A->G, A->tmp, A->tmp + m, A->tmp + 2 * m);
+  g_fw_ms += fsclg_maxt_last_ms(D.ctx[0], 0);
+  if (r != FSCLG_OK) return r;
+  for (i = 0; i < m; i++) {
+    A->c_single[i] += A->tmp[i];
+    A->c_chr[i] += A->tmp[m + i];
+    A->c_step[i] += A->tmp[2 * m + i];
+  }
+  return FSCLG_OK;
+}
+
+static int maxt_push(maxt_acc_t *A, const double *chunk, int t0, int n) {
+  int r = maxt_drain(A);
+  if (r != FSCLG_OK) return r;
+  r = fsclg_maxt_submit(D.ctx[0], 0, chunk, n, A->m, A->obs, A->order, A->group, A->G);
+  if (r == FSCLG_OK) { A->pending = 1; A->t0 = t0; }
+  return r;
+}
+
+int fscl_amd_familywise_runs(const double *clr, int n_trials, int m, const double *obs, const int32_t *order,
+                             const int32_t *group, int n_groups, double *gmax, int32_t *garg, double *grp_max,
+                             int32_t *grp_arg, int32_t *c_single, int32_t *c_chr, int32_t *c_step) {
+  maxt_acc_t A;
+  int B, t0, r = FSCLG_OK;
+  fh_familywise_set_error("");
+  g_fw_ms = 0.0;
+  if (n_trials < 0 || m < 0 || n_groups < 0 || (m && (!obs || !order || !group || !c_single || !c_chr || !c_step)) ||
+      (n_trials && (!gmax || !garg || (m && !clr))) || (n_trials && n_groups && (!grp_max || !grp_arg)))
+    return familywise_refuse(FSCLG_E_ARG, "a NULL argument or a negative size");
+  if (m) { memset(c_single, 0, sizeof(int32_t) * (size_t)m); memset(c_chr, 0, sizeof(int32_t) * (size_t)m); memset(c_step, 0, sizeof(int32_t) * (size_t)m); }
+  if (n_trials == 0) return FSCLG_OK;
+  B = fscl_amd_familywise_chunk(m, n_trials, fscl_amd_familywise_cap());
+  if (B < 1)
+    return familywise_refuse(FSCLG_E_ARG, "one trial of %d points does not fit in FSCL_AMD_FWER_CAP=%zu bytes", m, fscl_amd_familywise_cap());
+  dev_open();
+  memset(&A, 0, sizeof A);
+  A.m = m; A.G = n_groups; A.obs = obs; A.order = order; A.group = group;
+  A.gmax = gmax; A.garg = garg; A.grp_max = grp_max; A.grp_arg = grp_arg;
+  A.c_single = c_single; A.c_chr = c_chr; A.c_step = c_step;
+  A.tmp = fh_malloc(sizeof(int32_t) * 3 * (size_t)(m ? m : 1), "familywise counts");
+  for (t0 = 0; t0 < n_trials && r == FSCLG_OK; t0 += B)
+    r = maxt_push(&A, clr + (size_t)t0 * (size_t)m, t0, n_trials - t0 < B ? n_trials - t0 : B);
+  if (r == FSCLG_OK) r = maxt_drain(&A);
+  else (void)maxt_drain(&A);
+  free(A.tmp);
+  if (r != FSCLG_OK) familywise_refuse(r, "%s", fsclg_last_error());
+  return r;
+}
+
+int fscl_amd_familywise(scan_t *s, sm_ptable_t *sm, int trials, unsigned long long seed, double permute_nbp,
+                        int eval_range, int bp_resl, int large_grid_sp, double scan_width_mb, int keep_matrix,
+                        fscl_amd_familywise_t *out) {
+  const double t_begin = fh_now();
+  const unsigned long long seed_saved = g_pseed;
+  maxt_acc_t A;
+  fsclg_cell_t *cells;
+  fsclg_point_t *pts;
+  double *obs, *chunk;
+  int32_t *group;
+  long r_sub = 0, r_done = 0, R;
+  int m, G, B, nd, K, i, l, c0 = 0, rc = FSCLG_OK;
+  if (!s || !sm || !out) return FSCLG_E_ARG;
+  memset(out, 0, sizeof *out);
+  fh_familywise_set_error("");
+  g_fw_ms = 0.0;
+  if (trials < 1) return familywise_refuse(FSCLG_E_ARG, "--familywise-trials must be at least 1");
+  if (large_grid_sp < 1) return familywise_refuse(FSCLG_E_ARG, "the coarse grid spacing must be positive");
+  if (D.world > 1) return familywise_refuse(FSCLG_E_STATE, "--familywise-file runs in one process (not with %d ranks)", D.world);
+  m = s->n_scan_pts > 0 ? s->n_scan_pts : 0;
+  G = s->n_chromosomes > 0 ? s->n_chromosomes : 0;
+  if (G > FSCLG_MAXT_MAX_GROUPS)
+    return familywise_refuse(FSCLG_E_ARG, "%d chromosomes: more than the %d the family-wise maxima take", G, FSCLG_MAXT_MAX_GROUPS);
+  B = fscl_amd_familywise_chunk(m, trials, fscl_amd_familywise_cap());
+  if (B < 1)
+    return familywise_refuse(FSCLG_E_ARG, "one trial of %d points does not fit in FSCL_AMD_FWER_CAP=%zu bytes", m, fscl_amd_familywise_cap());
+  prepare(s, sm);
+  nd = D.n_dev;
+  K = env_int("FSCL_AMD_DEPTH", nd >= 4 ? 2 : FSCLG_N_SLOTS / nd, 1, FSCLG_N_SLOTS);
+  R = ((long)trials + nd - 1) / nd; /* rounds: trial r * nd + l on local device l */
+  out->n = m; out->n_groups = G; out->trials = trials; out->seed = seed;
+  out->order = fh_malloc(sizeof(int32_t) * (size_t)(m ? m : 1), "familywise order");
+  out->c_single = fh_calloc((size_t)(m ? m : 1), sizeof(int32_t), "familywise counts");
+  out->c_chr = fh_calloc((size_t)(m ? m : 1), sizeof(int32_t), "familywise counts");
+  out->c_step = fh_calloc((size_t)(m ? m : 1), sizeof(int32_t), "familywise counts");
+  out->gmax = fh_malloc(sizeof(double) * (size_t)trials, "familywise maxima");
+  out->garg = fh_malloc(sizeof(int32_t) * (size_t)trials, "familywise maxima");
+  out->chr_max = fh_malloc(sizeof(double) * (size_t)trials * (size_t)(G ? G : 1), "familywise maxima");
+  out->chr_arg = fh_malloc(sizeof(int32_t) * (size_t)trials * (size_t)(G ? G : 1), "familywise maxima");
+  if (keep_matrix) out->matrix = fh_malloc(sizeof(double) * (size_t)trials * (size_t)(m ? m : 1), "familywise matrix");
+  obs = fh_malloc(sizeof(double) * (size_t)(m ? m : 1), "familywise observed");
+  group = fh_malloc(sizeof(int32_t) * (size_t)(m ? m : 1), "familywise groups");
+  cells = fh_malloc(sizeof(fsclg_cell_t) * (size_t)(m ? m : 1), "cells");
+  chunk = fh_malloc(sizeof(double) * (size_t)B * (size_t)(m ? m : 1), "familywise chunk");
+  pts = fh_malloc(sizeof(fsclg_point_t) * (size_t)K * (size_t)nd * (size_t)(m ? m : 1), "points");
+  for (i = 0; i < m; i++) {
+    const scan_pt_t *q = s->scan_pts + i;
+    obs[i] = q->clr;
+    group[i] = q->chr;
+    trial_cell(q, large_grid_sp, cells + i); /* the same in every trial */
+  }
+  fscl_amd_familywise_order(obs, m, out->order);
+  memset(&A, 0, sizeof A);
+  A.m = m; A.G = G; A.obs = obs; A.order = out->order; A.group = group;
+  A.gmax = out->gmax; A.garg = out->garg; A.grp_max = out->chr_max; A.grp_arg = out->chr_arg;
+  A.c_single = out->c_single; A.c_chr = out->c_chr; A.c_step = out->c_step;
+  A.tmp = fh_malloc(sizeof(int32_t) * 3 * (size_t)(m ? m : 1), "familywise counts");
+  /* the throughput mode's builders under this pass's seed: trial t is its trial t */
+  g_pseed = seed;
+  trial_rows_begin(eval_range, scan_width_mb);
+  TB.n_dev = nd; TB.q = nd; TB.rank_off = 0; TB.n_perm = (long)trials - 1;
+  TB.snps = s->snps; TB.n = s->n_snps; TB.nbp = permute_nbp; TB.width_mb = scan_width_mb;
+  TB.total = R * nd; TB.next = 0; TB.negj = 0; TB.gen_s = 0.;
+  {
+    const int want = spec_threads_wanted();
+    TB.nb = (K + 1) * nd + want;
+    TB.limit = TB.nb;
+    TB.buf = fh_calloc((size_t)TB.nb, sizeof(void *), "permutation ring");
+    TB.nul = fh_calloc((size_t)TB.nb, sizeof(double *), "permutation ring");
+    TB.built = fh_malloc(sizeof(long) * (size_t)TB.nb, "permutation ring");
+    for (i = 0; i < TB.nb; i++) {
+      TB.buf[i] = fsclg_host_alloc((size_t)D.rb * (s->n_snps ? s->n_snps : 1));
+      if (!TB.buf[i]) logmsg(MSG_FATAL, "fscl_amd: row staging: %s", fsclg_last_error());
+      TB.nul[i] = fh_malloc(sizeof(double) * (D.n_chr ? D.n_chr : 1), "null sums");
+      TB.built[i] = -1;
+    }
+    for (TB.n_th = 0; TB.n_th < want; TB.n_th++)
+      if (pthread_create(&TB.th[TB.n_th], NULL, tb_worker, NULL) != 0) break;
+  }
+  while (r_done < r_sub || r_sub < R) {
+    if (r_sub < R && r_sub - r_done < K) { /* a round's trials: rows, window sums and every cell, per device */
+      const int slot = (int)(r_sub % K);
+      cr_logmsg(MSG_STATUS, "Family-wise maxima: unpruned permutation trials... %7ld of %d        ", r_sub * nd, trials);
+      for (l = 0; l < nd; l++) {
+        const long j = r_sub * nd + l;
+        int bi;
+        if (j >= trials) continue;
+        bi = tb_get(j);
+        dev_check(fsclg_slot_set_rows_packed(D.ctx[l], slot, TB.buf[bi], D.rb, TB.nul[bi]), "set rows");
+        dev_check(fsclg_slot_windows(D.ctx[l], slot, cells, m, eval_range), "window sums");
+        dev_check(fsclg_search_submit(D.ctx[l], 2 + slot, slot, cells, m, eval_range, bp_resl), "search submit");
+      }
+      r_sub++;
+    } else { /* the oldest round, its trials in order: each one's CLRs are a row of the chunk */
+      const int slot = (int)(r_done % K);
+      fsclg_point_t *o = pts + (size_t)slot * (size_t)nd * (size_t)(m ? m : 1);
+      for (l = 0; l < nd; l++)
+        if (r_done * nd + l < trials) dev_check(fsclg_search_wait(D.ctx[l], 2 + slot, o + (size_t)l * (size_t)m), "search wait");
+      tb_release((r_done + 1) * nd); /* the round's uploads ran before its searches */
+      for (l = 0; l < nd; l++) {
+        const long t = r_done * nd + l;
+        double *row;
+        if (t >= trials) continue;
+        row = chunk + (size_t)(t - c0) * (size_t)m;
+        for (i = 0; i < m; i++) row[i] = o[(size_t)l * (size_t)m + i].clr;
+        if (out->matrix && m) memcpy(out->matrix + (size_t)t * (size_t)m, row, sizeof(double) * (size_t)m);
+        if (t - c0 + 1 == B || t == trials - 1) {
+          if (rc == FSCLG_OK) rc = maxt_push(&A, chunk, c0, (int)(t - c0 + 1));
+          c0 = (int)t + 1;
+        }
+      }
+      r_done++;
+    }
+  }
+  if (rc == FSCLG_OK) rc = maxt_drain(&A);
+  else (void)maxt_drain(&A);
+  cr_logmsg(MSG_STATUS, "Family-wise maxima: unpruned permutation trials... finished.\n");
+  tb_stop();
+  g_pseed = seed_saved;
+  trial_rows_end();
+  free(A.tmp); free(obs); free(group); free(cells); free(chunk); free(pts);
+  out->kernel_ms = g_fw_ms;
+  if (rc != FSCLG_OK) {
+    familywise_refuse(rc, "%s", fsclg_last_error());
+    fscl_amd_familywise_free(out);
+  }
+  out->wall_s = fh_now() - t_begin;
+  return rc;
 }
 
 /* the points fscl_amd_scan_chromosome_grid made last: fscl_amd_scan_permute_grid tests only

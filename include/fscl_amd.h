@@ -937,6 +937,86 @@ double fscl_amd_tail_log10p(const fsclg_tail_t *row);
 void fscl_amd_tail_summary(const scan_t *scan_obj, fscl_amd_tail_t *t);
 int fscl_amd_tail_output(const char *fname, const scan_t *scan_obj, const fscl_amd_tail_t *t, const char *prepend_label);
 
+/* ---- family-wise adjusted p-values from unpruned permutation maxima (--familywise-file) ----
+   Westfall-Young maxT over the scan points.  Trial t = 0 .. trials-1 applies the block permutation
+   the throughput mode gives its trial t under `seed`, evaluates EVERY scan point on
+   its trial cell (the G-aligned, unclipped cell, Q5) -- no pruning, no prune draw -- and T[t][i] is
+   point i's CLR there.  The trials are pipelined over the row slots and the local devices (one
+   trial per device at a time); T is reduced on the first device in chunks of B trials by
+   fsclg_maxt_submit (include/fsclg.h), B the most trials whose B * n doubles fit in
+   $FSCL_AMD_FWER_CAP bytes (default 2^28), and the chunks' counts are added.  No result depends on
+   B, on the number of devices or on the depth of the pipeline.  With obs_i the point's CLR, the
+   points ranked by obs descending (ties by index ascending), M = trials:
+     p_single_i = (1 + c_single_i) / (M + 1),   c_single_i = #{t : max_k T[t][k] >= obs_i};
+     p_chr_i    = (1 + c_chr_i) / (M + 1),      the same over the points of i's chromosome;
+     p_step     the step-down value: in rank order p_step_(1) = (1 + c_step_(1)) / (M + 1) and
+                p_step_(j) = max(p_step_(j-1), (1 + c_step_(j)) / (M + 1)), c_step_(j) the trials
+                whose maximum over the ranks >= j reaches obs_(j).
+   At level a, k = floor(a (M + 1)) and the threshold is the k-th largest of the M maxima (none when
+   k = 0); a point is significant exactly when its CLR is strictly above it, which is p_single <= a.
+   maxT controls the family-wise error rate only as far as the block permutation is a valid null
+   (the per-point test's own assumption); the reference has no such test; the cost is M full scans.
+
+   fscl_amd_familywise: the pass, after a bisection scan (scan_chromosome), in one process
+   (FSCLG_E_STATE with several ranks); FSCLG_E_ARG for trials < 1, a cap below one trial or more
+   chromosomes than FSCLG_MAXT_MAX_GROUPS (fscl_amd_familywise_error names the reason).  The
+   arrays of *out are malloc'd (fscl_amd_familywise_free); matrix is T itself when keep_matrix, else
+   NULL.  The scan points, the permutation test's records and the rand() stream are not touched; the
+   original rows are back on the devices at the end.
+   fscl_amd_familywise_runs: fsclg_maxt_submit / wait of a caller's matrix clr[n_trials][m] on the
+   first device, in the same chunks, counts added; needs no scan.
+   fscl_amd_familywise_last_ms: the summed maxt_kernel milliseconds of the last of either.
+   Host only (familywise.c): fscl_amd_familywise_order (the rank order of obs[n]; a NaN ranks last),
+   fscl_amd_familywise_chunk (B for n points under cap bytes, at most trials; 0 when one trial does
+   not fit), fscl_amd_familywise_combine (rank[n] from 1, and the three p-values, from the counts),
+   fscl_amd_familywise_threshold (k, and *thr the k-th largest of maxima[M], NaN when k = 0),
+   fscl_amd_familywise_output (fname NULL: stdout; 0, or -1 if the file cannot be written) -- one
+   row per scan point in -o order, then one summary row per chromosome and one for the genome:
+     [label TAB] chromosome TAB position TAB CLR (%1.2f) TAB alpha (%1.3e) TAB rank TAB p_chr (%1.3e)
+       TAB p_single (%1.3e) TAB p_step (%1.3e) TAB -log10 p_step (%1.3f)
+     [label TAB] chromosome | "genome" TAB "summary" TAB M TAB n_points TAB max_q50 (%1.2f) TAB thr_10
+       TAB thr_05 TAB thr_01 (%1.2f) TAB n_sig_05 TAB n_sig_01
+   max_q50 the median of the row's M maxima, thr_* its thresholds at levels 0.10, 0.05 and 0.01,
+   n_sig_* counted by p_step on the genome row and by p_chr on a chromosome row; NA for a threshold
+   with k = 0 and for a figure that is not finite --
+   and fscl_amd_familywise_null_output, one row per trial:
+     [label TAB] trial TAB genome_max (%1.4f) TAB argmax_chromosome TAB argmax_position
+       then every chromosome's maximum (%1.4f); NA where there is none. */
+typedef struct {
+  int n, n_groups, trials;      /* scan points, chromosomes, M */
+  unsigned long long seed;
+  int32_t *order;               /* [n] the points by observed CLR descending */
+  int32_t *c_single, *c_chr, *c_step; /* [n] */
+  double *gmax;                 /* [trials] */
+  int32_t *garg;
+  double *chr_max;              /* [trials][n_groups] */
+  int32_t *chr_arg;
+  double *matrix;               /* [trials][n], or NULL */
+  double kernel_ms, wall_s;
+} fscl_amd_familywise_t;
+int fscl_amd_familywise(scan_t *scan_obj, sm_ptable_t *sm_p, int trials, unsigned long long seed, double permute_nbp,
+                        int eval_range, int bp_resl, int large_grid_sp, double scan_width_mb, int keep_matrix,
+                        fscl_amd_familywise_t *out);
+int fscl_amd_familywise_runs(const double *clr, int n_trials, int m, const double *obs, const int32_t *order,
+                             const int32_t *group, int n_groups, double *gmax, int32_t *garg, double *grp_max,
+                             int32_t *grp_arg, int32_t *c_single, int32_t *c_chr, int32_t *c_step);
+double fscl_amd_familywise_last_ms(void);
+const char *fscl_amd_familywise_error(void);
+size_t fscl_amd_familywise_cap(void); /* $FSCL_AMD_FWER_CAP, or 2^28 */
+/* the pass's host-only refusals before any device work: trials, the chromosomes, and one trial of
+   the scan's cells (one point each at this spacing) under the cap; 0, or -1 with the reason */
+int fscl_amd_familywise_check(const scan_t *scan_obj, int large_grid_sp, int trials);
+void fscl_amd_familywise_free(fscl_amd_familywise_t *f);
+void fscl_amd_familywise_order(const double *obs, int n, int32_t *order);
+int fscl_amd_familywise_chunk(int n, int trials, size_t cap_bytes);
+void fscl_amd_familywise_combine(const int32_t *c_single, const int32_t *c_chr, const int32_t *c_step, const int32_t *order,
+                                 int n, int trials, int32_t *rank, double *p_single, double *p_chr, double *p_step);
+int fscl_amd_familywise_threshold(const double *maxima, int trials, double level, double *thr);
+int fscl_amd_familywise_output(const char *fname, const scan_t *scan_obj, const fscl_amd_familywise_t *f,
+                               const char *prepend_label);
+int fscl_amd_familywise_null_output(const char *fname, const scan_t *scan_obj, const fscl_amd_familywise_t *f,
+                                    const char *prepend_label);
+
 /* release the device context (tables / snps) */
 void fscl_amd_shutdown(void);
 

@@ -484,6 +484,38 @@ int fsclg_tail_submit(fsclg_ctx *c, int batch, const float *samples, size_t n_sa
 int fsclg_tail_wait(fsclg_ctx *c, int batch, fsclg_tail_t *out);
 double fsclg_tail_last_ms(fsclg_ctx *c, int batch);
 
+/* Family-wise maxima of unpruned permutation trials (Westfall-Young maxT).
+   clr[n_trials][m] holds every point's CLR in every trial of a chunk, obs[m] the observed CLRs,
+   order[m] the points by observed CLR descending (ties by index ascending; any permutation of
+   0 .. m-1 is accepted and defines the ranks), group[m] each point's group (its chromosome) in
+   [0, n_groups).  A value enters a maximum as v + 0.0, so a maximum of zeros is +0.0; a NaN is never
+   a maximum and never exceeds; a maximum over no value, or over NaN alone, is -inf.
+   Per trial t:  gmax[t] the maximum over the points and garg[t] the least point index whose value
+   equals it (-1 when there is none: no point, or NaN alone);  grp_max[t][g], grp_arg[t][g] the same
+   over the points of group g.
+   Per point i, over the chunk's trials, three counts:
+     c_single[i] = #{t : gmax[t] >= obs[i]},
+     c_chr[i]    = #{t : grp_max[t][group[i]] >= obs[i]},
+     c_step[i]   = #{t : u_t(rank of i) >= obs[i]},  u_t(j) = max of clr[t][order[k]] over k >= j,
+   the successive suffix maximum of the step-down procedure (a NaN obs[i] counts nothing).
+   Everything is comparisons and integer adds: the result does not depend on the order of
+   execution, and the counts of successive chunks add up to the counts of their union.
+   One workgroup of FSCLG_MAXT_WG threads per trial; the suffix maxima run in tiles of
+   FSCLG_MAXT_TILE ranks.  Asynchronous like fsclg_tail_submit / fsclg_tail_wait on any batch, and
+   needs neither tables nor sites; the arrays are copied.  Errors: FSCLG_E_ARG for a bad batch,
+   a negative size, n_groups above FSCLG_MAXT_MAX_GROUPS, a group outside [0, n_groups), an order
+   that is no permutation, n_trials * (n_groups + 1) past an int, a NULL result (wait: the batch
+   stays submitted); FSCLG_E_STATE for a batch not waited for (submit), no maxima submitted on it
+   (wait).  fsclg_maxt_last_ms: the kernel's own time (HIP events) of the batch's last maxt call. */
+#define FSCLG_MAXT_WG 256
+#define FSCLG_MAXT_TILE 1024
+#define FSCLG_MAXT_MAX_GROUPS 4096
+int fsclg_maxt_submit(fsclg_ctx *c, int batch, const double *clr, int n_trials, int m, const double *obs,
+                      const int32_t *order, const int32_t *group, int n_groups);
+int fsclg_maxt_wait(fsclg_ctx *c, int batch, double *gmax, int32_t *garg, double *grp_max, int32_t *grp_arg,
+                    int32_t *c_single, int32_t *c_chr, int32_t *c_step);
+double fsclg_maxt_last_ms(fsclg_ctx *c, int batch);
+
 /* Expected terms of a walk under the model: what the fitted spectrum itself predicts at a sweep.
    A request is a walk of fsclg_sites_submit (chr, pos; its lalpha field is not read); request r is evaluated at each of the
    n_la log alphas la[r * n_la ..], giving the tasks (r, k) in that order.  The sites of task (r, k)

@@ -107,11 +107,6 @@ def main(argv: list[str]) -> int:
         build_native(force=force, trace=True)
     if "--rehearsal" in argv:  # the scaling-rehearsal test build (tools/scale_sim.sh)
         build_native(force=force, variant="rehearsal", defines=("-DFSCL_AMD_REHEARSAL",))
-    if "--logx" in argv:  # the computed mid-branch log distance (FSCLG_LOG_CALC): 2 in every
-        # kernel, 1 in the split kernel only; and their rehearsal builds
-        for v, lc in (("logx", "2"), ("logxs", "1")):
-            build_native(force=force, variant=v, defines=(f"-DFSCLG_LOG_CALC={lc}",))
-            build_native(force=force, variant=f"rehearsal_{v}", defines=("-DFSCL_AMD_REHEARSAL", f"-DFSCLG_LOG_CALC={lc}"))
     for a in argv:  # --variant=NAME:DEF[,DEF...]: an experiment build fscl_amd/_build_NAME with -DDEF each
         if a.startswith("--variant="):
             name, _, defs = a[len("--variant="):].partition(":")

@@ -131,19 +131,13 @@ struct Params {
   const int32_t* n_refine;     // [n_coarse + 1]
   const uint32_t* dfail;       // [n_coarse + (n_coarse + 1) * MAXREF]: per alpha, the least |d| with
                                // logt(|d|) + lalpha > LOG_AD_MAX (logt is nondecreasing in |d|)
-  const uint32_t* dband;       // [alpha row][n_iv + 1]: the least |d| with logt(|d|) + lalpha >= thr[j] (band cuts)
-  int nd;                      // n_iv + 1 (dband's row stride)
-  int band_th;                 // a band's window is staged when its pieces hold at least this many trips
-  int band_nb;                 // at most this many bands (FSCLG_BAND_NB, experiments; NBMAX by default)
-  int band_minp;               // a walk part is cut at a band only where both pieces hold this many trips
-  const int32_t* tpos;         // [ceil(n_snps / 128)]: the position of site 128 t (band cut searches)
-  int off_bd;                  // band mode: byte offset of its BandLds in the dynamic LDS (after the logt copy;
-                               // reserved only when band_th >= 0, so the walk-window path keeps the whole window)
+  unsigned long long hold0[5] = {};  // unused: the 40 bytes of band mode's fields.  They hold the kernarg offsets of
+                               // what follows: without them the search kernels reload spilled SGPRs ~230 times more
+                               // (profiles/term_loop_cleanup_device_code.txt)
   const fsclg_cell_t* cells;
   fsclg_point_t* out;
   unsigned long long* stats;   // 8 counters
   unsigned long long* ctrace;  // optional per-cell [start, end, cu id, terms, phase ticks x4] (FSCLG_CELL_TRACE)
-  unsigned long long* ivhist;  // optional [n_iv]: terms per spline interval, one sample per segment
   int n_coarse;
   int n_iv;
   int n_rows;
@@ -158,8 +152,8 @@ struct Params {
   int off_thr, off_nul;        // byte offsets in fsclg_dyn (the coefficient window at 0)
   int off_lt, lt_hi;           // LDS copy of logt3 branch 2 (|d| > 2^24) entries [256, lt_hi) at off_lt; lt_hi 0: none
   uint32_t lt_span;            // |d| is in that copy iff |d| - 2^24 < lt_span (unsigned); 0: none
-  const double* lx;            // FSCLG_LOG_CALC: the mid branch computed (logx_mid), its 256-entry table (LX_BYTES)
-  int off_lx, lx_on;           //   at off_lx in LDS; lx_on 0: the mid branch from logt3 (the device check failed)
+  unsigned long long hold1[2] = {};  // unused: the 16 bytes of the computed log's fields, kept as hold0 is (without
+                               // them profile_kernel<true> and curve_kernel<true> grow by 8 and 3 instructions)
   int eval_range;
   int bp_resl;
   int n_cells;
@@ -206,41 +200,12 @@ struct Walk {
   double la;
   double xl, xr;  // log(alpha d) at the walk's far ends (the walk's largest x is one of them)
   uint32_t dfail; // a site is outside the walk iff its |d| >= dfail (Params::dfail)
-  int kd;         // the walk's alpha row in Params::dfail / Params::dband
+  int kd;         // the walk's alpha row in Params::dfail
 };
 
-// band mode (the throughput kernel): a phase's walks are evaluated interval band by
-// band.  Band b holds the intervals [bbase[b], bbase[b] + K) (K: the LDS window), the bands tile
-// downwards from the top interval of the phase's walks, and below the last one lies the remainder.
-// A walk part's sites in band b are those with |d| in [D(bbase[b]), D(bbase[b - 1])) (Params::dband):
-// one contiguous run of sites, a "piece", found as a trip range (cut[]: the trip holding the cut,
-// relative to the part's first trip; -1: the part never reaches the band) whose boundary trips
-// are masked by the same |d| test ("lazy cuts", run_piece_seg).  Pieces are cut into segments of
-// TPS trips; sb[] numbers a walk's segments in site-index order (left part's pieces from band 0 down
-// to the remainder, then the right part's from the remainder up to band 0).
-#ifndef FSCLG_NBMAX
-#define FSCLG_NBMAX 8
-#endif
-constexpr int NBMAX = FSCLG_NBMAX;
-constexpr int NPIECE = 2 * (NBMAX + 1);  // pieces per walk
-struct BandLds {
-  alignas(16) int16_t cut[MAXWALK][2][NBMAX];  // -1: the part never reaches the band; -2: dropped (pieces merged)
-  uint32_t dv[MAXWALK][NBMAX];      // the walk's |d| bound of each band (Params::dband)
-  int8_t qof[MAXWALK][2][NBMAX + 1];  // the piece of (walk, part) that group g processes, -1: none
-  uint8_t sb[MAXWALK][NPIECE + 1];
-  int bbase[NBMAX];
-  int nb;
-  int nrun;
-  int run_g0[NBMAX + 2];            // run r: groups (= bands, nb: the remainder) [run_g0[r], run_g0[r + 1])
-  int run_stage[NBMAX + 1];         // run r stages band run_g0[r]'s window first (0: keeps the loaded one)
-  int gitems[NBMAX + 1];            // segments per group
-  int gtrips[NBMAX + 1];            // trips per group
-};
-
-template <int MW, bool BAND = false>
+template <int MW>
 struct SmemT {
   static constexpr int MAXW = MW;
-  static constexpr bool HAS_BAND = BAND;
   Pt pt[4];                       // cells: start, end, midpoint, the midpoint's predicted child
   Walk w[MW];
   unsigned long long P[MW];
@@ -266,7 +231,6 @@ struct SmemT {
   int gseg[MW + 1];
   int gk[MW + 1];                 // the group's walks: word[gk[g] .. gk[g + 1])
   int word[MW];              // walks in segment order
-  int hkey;                       // interval-histogram key of the phase: 0 coarse, 1 + c refine around coarse c
   int hitmask;                    // split cells: the points whose speculative refine walks were the right ones
   unsigned long long tph[5];      // FSCLG_PHASE_TIMING: wall-clock ticks in bounds / layout / segments / resolve,
                                   // and (slot 4) the split combine's wait for the other members' arrival
@@ -278,9 +242,6 @@ struct SmemT {
   int xnt[FSCLG_MAXSPLIT];        // split cells: each member's tie count of the instance
 };
 using Smem = SmemT<MAXWALK>;             // the throughput kernel (its LDS window takes the rest)
-using SmemBand = SmemT<MAXWALK, true>;   // the same in band mode: a kernel of its own, so that band mode's
-                                         // layout code does not raise the walk-window kernel's registers
-static_assert(sizeof(Smem) == sizeof(SmemBand), "band mode's LDS block is dynamic (Params::off_bd)");
 using SmemSplit = SmemT<MAXWALK_SPLIT>;  // split cells: room for speculative refine walks (no LDS window)
 
 
@@ -345,56 +306,6 @@ __device__ __forceinline__ double logt_lds(uint32_t ad, const Params& P) {
       return reinterpret_cast<const double*>(fsclg_dyn + P.off_lt)[i2];  // off_lt is pre-offset by -256 entries
   }
   return logt_dev(ad, P.logt3);
-}
-
-// FSCLG_LOG_CALC: the mid branch of logt (sm-search.c:43: 5.545177444479562 + log_table[|d| >> 8],
-// i = |d| >> 8 in [256, 65536)) computed instead of gathered from the 512 KB table.  i = 2^e m,
-// m = i << (15 - e) in [2^15, 2^16); c = the top 9 bits of m (256 choices, k), r = (m - c) / c
-// with |r| < 2^-8: log(i) = log(c) - (15 - e) ln2 + log1p(r), log(c) tabulated as hi + lo,
-// (15 - e) ln2_hi exact (42-bit ln2_hi), log1p(r) = r - r^2/2 + r^3 (1/3 - r/4 + r^2/5 - r^3/6).
-// The host evaluates the same operations for all 65 280 i against the reference's table
-// (logx_table: glibc's log, the same IEEE add), adjusts the lo parts of the few k whose entries
-// round the other way, and the device checks every entry once (logx_check_kernel): every
-// value is the table's, bit for bit, or the path stays off.
-constexpr int LX_BYTES = 256 * 32;  // per k: log(c) hi, lo, RN(1/c), pad
-#ifndef FSCLG_LOG_CALC
-#define FSCLG_LOG_CALC 0
-#endif
-// FSCLG_LOG_CALC=1: in the split kernel only (the latency-bound tail); 2: in every kernel
-template <class SM> constexpr bool lx_kernel() {
-  return FSCLG_LOG_CALC >= 2 || (FSCLG_LOG_CALC == 1 && std::is_same<SM, SmemSplit>::value);
-}
-constexpr double LX_LN2_HI = 0x1.62e42fefa38p-1, LX_LN2_LO = 0x1.ef35793c7673p-45;
-__host__ __device__ __forceinline__ double logx_mid(uint32_t i, const double* lx) {
-  const int e = 31 - __builtin_clz(i);
-  const int n = 15 - e;
-  const uint32_t m = i << n;
-  const uint32_t k = (m >> 7) & 255u;
-  const double lch = lx[4 * k], lcl = lx[4 * k + 1], inv = lx[4 * k + 2];
-  const double f = (double)(m & 127u), dn = (double)n;
-  const double rh = f * inv;
-  const double A = __builtin_fma(-dn, LX_LN2_HI, lch);  // exact
-  const double q = __builtin_fma(-dn, LX_LN2_LO, lcl);
-  const double sh = A + rh;
-  const double t = (A - sh) + rh;
-  const double r2 = rh * rh;
-  double p = __builtin_fma(rh, -1.0 / 6, 1.0 / 5);
-  p = __builtin_fma(rh, p, -1.0 / 4);
-  p = __builtin_fma(rh, p, 1.0 / 3);
-  const double r3 = r2 * rh;
-  p = r3 * p;
-  double lo = t + q;
-  lo = __builtin_fma(-0.5, r2, lo);
-  lo = lo + p;
-  const double L = sh + lo;
-  return 5.545177444479562 + L;
-}
-
-// every mid-branch entry computed on the device against the uploaded table: mismatches counted
-__global__ void __launch_bounds__(256) logx_check_kernel(const double* __restrict__ lx, const double* __restrict__ lt3,
-                                                         unsigned long long* __restrict__ bad) {
-  const uint32_t i = 256u + blockIdx.x * 256u + threadIdx.x;
-  if (i < 0x10000u && logx_mid(i, lx) != lt3[0x10000u + i]) atomicAdd(bad, 1ull);
 }
 
 // |pos_i - sweep| from biased positions: one v_sad_u32
@@ -475,13 +386,8 @@ __device__ __forceinline__ void coef_stage(const double (&x)[U], const uint32_t 
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const uint32_t ci = (uint32_t)(iv[u] - ivc0);
-#ifdef FSCLG_EXP_COEF_LDS  // timing ablation (wrong results): every coefficient from the LDS window
-      if (P.n_civ > 0)
-        coef_ld(fsclg_dyn, coef_off(rv[u], (int)min(ci, (uint32_t)P.civ_max), P), P, ca[u], cb[u]);
-#else
       if (ci < (uint32_t)P.n_civ)  // every row is cached
         coef_ld(fsclg_dyn, coef_off(rv[u], (int)ci, P), P, ca[u], cb[u]);
-#endif
       else
         coef_ld(reinterpret_cast<const char*>(P.coef), coef_off(rv[u], iv[u], P), P, ca[u], cb[u]);
     }
@@ -681,43 +587,29 @@ __device__ __forceinline__ double walk_sequential(const SM& S, const Walk& W, co
   return acc;
 }
 
-// FSCLG_SITE_MAJOR (default): a walk's left part is cut on the grid that ENDS at the block holding the
-// nearest site (the right part's grid starts at the block after it), so that both grids are the same
-// for every walk of a point, and the waves are dealt a phase's segments site-major: slice (j, part) is
-// the j-th segment from the nearest site of every walk that reaches it, so the waves working at once
-// read the same sites and log-table entries for different alphas (logt(|d|) does not depend on alpha)
-// and those reads hit the vector L1.  0: the left grid from the walk's far end, walk-major dealing.
-#ifndef FSCLG_FAR_FIRST
-#define FSCLG_FAR_FIRST 0  // site-major slices from the farthest inwards (1) or from the nearest SNP outwards (0)
-#endif
+// A walk's left part is cut on the grid that ENDS at the block holding the nearest site (left_anchor;
+// the right part's grid starts at the block after it), so that both grids are the same for every walk
+// of a point, and the waves are dealt a phase's segments site-major, from the nearest site outwards:
+// slice (j, part) is the j-th segment from the nearest site of every walk that reaches it, so the
+// waves working at once read the same sites and log-table entries for different alphas (logt(|d|)
+// does not depend on alpha) and those reads hit the vector L1.
 #ifndef FSCLG_GROUP_TOL
 #define FSCLG_GROUP_TOL 2  // a window group takes the following walks whose window base is at most this far below
-#endif
-#ifndef FSCLG_SITE_MAJOR
-#define FSCLG_SITE_MAJOR 1
-#endif
-#ifndef FSCLG_LEFT_ANCHOR
-#define FSCLG_LEFT_ANCHOR FSCLG_SITE_MAJOR
 #endif
 __device__ __forceinline__ int left_anchor(int near) { return (near & ~127) + 128; }
 
 // A walk covers the site indices [nearest - nl, nearest + nr]; its left part
 // [nearest - nl, nearest] (walked downwards, sm-search.c:122-128) and right part
 // [nearest + 1, nearest + nr] are cut into separate segments (left ones first), so each
-// part's walk order is monotone in the index.  Segments lie on the aligned SEGN-site grid
-// that starts at the part's first 128-site block: interior boundaries are trip-aligned, and
-// only a part's first and last trips are partial (masked).
+// part's walk order is monotone in the index.  Segments lie on the part's aligned SEGN-site
+// grid (above): interior boundaries are trip-aligned, and only a part's first and last trips
+// are partial (masked).
 template <int SEGN>
 __device__ __forceinline__ void seg_bounds(const Walk& W, const Pt& pt, int s, int& ib, int& ie) {
   const int lo = pt.nearest - W.nl, near = pt.nearest, hi = pt.nearest + W.nr;
   if (s < W.nsl) {
-#if FSCLG_LEFT_ANCHOR
     const int A = left_anchor(near), j = W.nsl - 1 - s;
     ib = max(lo, A - (j + 1) * SEGN); ie = min(A - j * SEGN, near + 1);
-#else
-    const int b0 = lo & ~127;
-    ib = max(lo, b0 + s * SEGN); ie = min(b0 + (s + 1) * SEGN, near + 1);
-#endif
   } else {
     const int b1 = (near + 1) & ~127, t = s - W.nsl;
     ib = max(near + 1, b1 + t * SEGN); ie = min(b1 + (t + 1) * SEGN, hi + 1);
@@ -727,11 +619,7 @@ __device__ __forceinline__ void seg_bounds(const Walk& W, const Pt& pt, int s, i
 // segments of a walk's two parts (layout)
 template <int SEGN>
 __device__ __forceinline__ void seg_counts(int lo, int near, int hi, int& nsl, int& nsr) {
-#if FSCLG_LEFT_ANCHOR
   nsl = (left_anchor(near) - (lo & ~127) + SEGN - 1) / SEGN;
-#else
-  nsl = (near - (lo & ~127)) / SEGN + 1;
-#endif
   nsr = hi > near ? (hi - ((near + 1) & ~127)) / SEGN + 1 : 0;
 }
 
@@ -739,13 +627,8 @@ __device__ __forceinline__ void seg_counts(int lo, int near, int hi, int& nsl, i
 // the segment of site index i of the walk
 template <int SEGN>
 __device__ __forceinline__ int seg_of(const Walk& W, const Pt& pt, int i) {
-  const int lo = pt.nearest - W.nl, near = pt.nearest;
-#if FSCLG_LEFT_ANCHOR
-  (void)lo;
+  const int near = pt.nearest;
   return i <= near ? W.nsl - 1 - (left_anchor(near) - 1 - i) / SEGN : W.nsl + (i - ((near + 1) & ~127)) / SEGN;
-#else
-  return i <= near ? (i - (lo & ~127)) / SEGN : W.nsl + (i - ((near + 1) & ~127)) / SEGN;
-#endif
 }
 
 __device__ __forceinline__ bool odd_int(double v) { return v - 2.0 * floor(0.5 * v) != 0.0; }
@@ -784,7 +667,7 @@ __device__ __forceinline__ double uniform_f64(double v) {
 // lane's x lies inside (two compares per term) the interval is civ for all of them, with no
 // per-lane interval arithmetic, and the coefficient block comes from one place (the LDS
 // window or the global table, a uniform branch).  Otherwise the trip takes the per-lane path
-// of run_segment and re-centres civ on its last site.  Only the final trip of a segment
+// (coef_stage) and re-centres civ on its last site.  Only the final trip of a segment
 // masks lanes past its end (zero sentinel row).
 template <bool LDS, int SEGN, int U, class SM>
 __device__ __forceinline__ void run_segment_idx(SM& S, int w, int s, int s1, const Params& P, int lane,
@@ -855,18 +738,9 @@ __device__ __forceinline__ void run_segment_idx(SM& S, int w, int s, int s1, con
 #pragma unroll
       for (int u = 0; u < U; u++) x[u] = lt2[ad[u] >> 16] + la;
     } else if (__builtin_amdgcn_ballot_w64(mid) == ~0ull) {
-#if FSCLG_LOG_CALC
-      if (LDS && lx_kernel<SM>() && P.lx_on) {
-        const double* lx = reinterpret_cast<const double*>(fsclg_dyn + P.off_lx);
+      const char* lt1 = reinterpret_cast<const char*>(P.logt3 + 0x10000);
 #pragma unroll
-        for (int u = 0; u < U; u++) x[u] = logx_mid(ad[u] >> 8, lx) + la;
-      } else
-#endif
-      {
-        const char* lt1 = reinterpret_cast<const char*>(P.logt3 + 0x10000);
-#pragma unroll
-        for (int u = 0; u < U; u++) x[u] = *reinterpret_cast<const double*>(lt1 + ((ad[u] >> 8) << 3)) + la;
-      }
+      for (int u = 0; u < U; u++) x[u] = *reinterpret_cast<const double*>(lt1 + ((ad[u] >> 8) << 3)) + la;
     } else {
 #pragma unroll
       for (int u = 0; u < U; u++) x[u] = logt_lds<LDS>(ad[u], P) + la;
@@ -895,17 +769,9 @@ __device__ __forceinline__ void run_segment_idx(SM& S, int w, int s, int s1, con
     TSTAMP(t_c);
     cpath = !uni ? 2 : ((LDS && (uint32_t)(civ - ivc0) < (uint32_t)P.n_civ) ? 0 : 1);
 #endif
-#ifdef FSCLG_PATHSTATS  // diagnostic: trips per path in the stats slots 4 (per-lane), 5 (LDS), 6 (global)
-    if (lane == 0) atomicAdd(&S.cnt[!uni ? 4 : ((LDS && (uint32_t)(civ - ivc0) < (uint32_t)P.n_civ) ? 5 : 6)], 1ull);
-#endif
     if (uni) {
-#ifdef FSCLG_EXP_COEF_LDS
-      const uint32_t ci = min((uint32_t)(civ - ivc0), (uint32_t)P.civ_max);
-      if (LDS && P.n_civ > 0) {
-#else
       const uint32_t ci = (uint32_t)(civ - ivc0);
       if (LDS && ci < (uint32_t)P.n_civ) {
-#endif
         const char* lb = fsclg_dyn + (__umul24(ci, (uint32_t)P.stride) << 5);
 #pragma unroll
         for (int u = 0; u < U; u++) coef_ld(lb, rv[u] << 4, P, ca[u], cb[u]);
@@ -922,12 +788,6 @@ __device__ __forceinline__ void run_segment_idx(SM& S, int w, int s, int s1, con
     double nul[U];
 #pragma unroll
     for (int u = 0; u < U; u++) nul[u] = null_of<LDS>(rv[u], S, P);
-#ifdef FSCLG_EXP_COEF_LDS  // the lanes whose interval missed the window add 0 (sane sums, the same trips)
-    bool miss[U];
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      miss[u] = (uint32_t)((uni ? civ : interval_of<LDS>(x[u], S, P)) - ivc0) >= (uint32_t)P.n_civ;
-#endif
     // after the last use of this trip's rows (so the look-ahead loads into the same
     // registers, no copy at the loop edge), unconditional (the last trip's look-ahead reads
     // the padding; a conditional load would make the waits below conservative at the join)
@@ -952,10 +812,7 @@ __device__ __forceinline__ void run_segment_idx(SM& S, int w, int s, int s1, con
 #ifdef FSCLG_TRIP_STAMPS
       const double y = yv[u];
 #else
-      double y = x[u] * (ca[u].x * x[u] * x[u] + ca[u].y * x[u] + cb[u].x) + cb[u].y;
-#endif
-#ifdef FSCLG_EXP_COEF_LDS
-      if (miss[u]) y = nul[u] + 0.0 * y;
+      const double y = x[u] * (ca[u].x * x[u] * x[u] + ca[u].y * x[u] + cb[u].x) + cb[u].y;
 #endif
       const double q = (y - nul[u]) * inv;
       const double R = rint(q);                 // the even neighbour at a tie; the resolver settles ties
@@ -1033,9 +890,9 @@ __device__ __forceinline__ void flush_walk(SM& S, int w, double acc, double accm
 // resolve walk w's exact value (thread per walk).  S.P = sum R, S.Q = sum |R| over the walk.
 // Ties are replayed in k order: fl(acc + t) rounds to even, so where t/u = F + 1/2 an odd
 // running sum takes the other neighbour of the even R (+1 if R = F, -1 if R = F + 1).
-template <int SEGN, bool BAND = false, class SM>
+template <int SEGN, class SM>
 __device__ __forceinline__ void resolve_walk(SM& S, int w) {
-  constexpr int WM = BAND ? 31 : 63;  // band mode: walk in bits 20-24, the tie's segment in bits 25-31
+  constexpr int WM = 63;  // a tie record's walk: bits 20-25
   const Walk& W = S.w[w];
   const Pt& pt = S.pt[W.p];
   if (W.len == 0) { S.exact[w] = 1; S.val[w] = pt.N; return; }
@@ -1078,7 +935,7 @@ __device__ __forceinline__ void resolve_walk(SM& S, int w) {
       // order = (left tie) the left part after it, (right tie) the left part and the
       // right part before it; R of a tie is even, so both read lpar ^ prefix-in-part
       const int jj = bestv & 0x3FFFF;
-      const int sg = BAND ? (int)((unsigned)bestv >> 25) : seg_of<SEGN>(W, pt, pt.nearest - nl + jj);
+      const int sg = seg_of<SEGN>(W, pt, pt.nearest - nl + jj);
       const int sp = segpar(jj <= nl ? 0 : nsl, sg);
       const int pre = (bestv >> 18) & 1, up = (bestv >> 19) & 1;
       const int adj = (int)(S0 & 1) ^ lpar ^ sp ^ pre ^ adjx;
@@ -1131,537 +988,6 @@ __device__ __forceinline__ void load_window(SM& S, const Params& P, int wb) {
   const double2* src = reinterpret_cast<const double2*>(P.coef) + (size_t)wb * P.stride * 2;
   for (int e = threadIdx.x; e < 2 * P.n_cache; e += WG) dst[e] = src[e];
   if (threadIdx.x == 0) S.ivc0 = wb;
-}
-
-// ------------------------------------------------------------ band mode
-constexpr int TPS = SEG / 128;           // trips per segment (band mode)
-constexpr uint32_t DNONE = 0xFFFFFFFFu;  // no lazy cut on that trip (|d| never reaches it)
-static_assert(U_MAIN == 2, "band mode: one aligned 128-site block per trip");
-static_assert(MAXWALK <= 32, "band mode: the walk in 5 bits of a tie record");
-
-// piece q of walk w (q in site-index order, BandLds): its part, trip range [ta, tb] relative to
-// the part's first trip, and its lazy cuts (the band whose |d| bound is tested on the first /
-// last trip; -1: none).  Left part (walked downwards): q = band, q = nb the remainder next to the
-// nearest site; a site of band b lies in (cut(b - 1), cut(b)] where cut(x) is the LAST site in
-// index order with |d| >= D(x).  Right part: q = nb + 1 the remainder, then bands nb - 1 .. 0; a
-// site of band b lies in [cut(b), cut(b - 1)) with cut(x) the FIRST site with |d| >= D(x).
-struct Piece { int part, ta, tb, clo, chi; bool empty; };
-// a walk part's cuts in registers (one 16-byte LDS read); element access by unrolled selects
-static_assert(NBMAX == 8, "a part's cuts are one 16-byte LDS word");
-struct Cuts { int c[NBMAX]; };
-__device__ __forceinline__ Cuts load_cuts(const BandLds& bd, int w, int part) {
-  const uint4 v = *reinterpret_cast<const uint4*>(&bd.cut[w][part][0]);
-  const uint32_t a[4] = {v.x, v.y, v.z, v.w};
-  Cuts k;
-#pragma unroll
-  for (int i = 0; i < 4; i++) { k.c[2 * i] = (int)(int16_t)(a[i] & 0xFFFFu); k.c[2 * i + 1] = (int)(int16_t)(a[i] >> 16); }
-  return k;
-}
-__device__ __forceinline__ void store_cuts(BandLds& bd, int w, int part, const Cuts& k) {
-  uint32_t a[4];
-#pragma unroll
-  for (int i = 0; i < 4; i++) a[i] = ((uint32_t)k.c[2 * i] & 0xFFFFu) | ((uint32_t)k.c[2 * i + 1] << 16);
-  *reinterpret_cast<uint4*>(&bd.cut[w][part][0]) = make_uint4(a[0], a[1], a[2], a[3]);
-}
-__device__ __forceinline__ int cut_at(const Cuts& k, int i) {  // k.c[i], i in [0, NBMAX)
-  int v = -1;
-#pragma unroll
-  for (int j = 0; j < NBMAX; j++) if (j == i) v = k.c[j];
-  return v;
-}
-__device__ __forceinline__ int kept_below(const Cuts& k, int b) {  // the largest j < b with a kept cut, -1
-  int f = -1;
-#pragma unroll
-  for (int j = 0; j < NBMAX; j++) if (j < b && k.c[j] >= 0) f = j;
-  return f;
-}
-// piece q of a walk (site-index order, BandLds) from its part's cuts k: left part (q <= nb): band q,
-// q = nb the remainder, the piece ending (inclusive) at its own kept cut and starting past the
-// nearest kept cut of a higher band; right part: q = nb + 1 the remainder, then bands nb - 1 .. 0,
-// the piece starting at its own kept cut and ending before the nearest kept cut of a higher band
-__device__ __forceinline__ Piece piece_of(const Cuts& k, int q, int nb, int ntrL, int ntrR) {
-  Piece pc;
-  pc.clo = -1; pc.chi = -1; pc.empty = false;
-  if (q <= nb) {
-    const int b = q;
-    pc.part = 0; pc.ta = 0; pc.tb = ntrL - 1;
-    const int f = kept_below(k, b);
-    if (f >= 0) { pc.ta = cut_at(k, f); pc.clo = f; }
-    if (b < nb) {
-      const int c = cut_at(k, b);
-      if (c < 0) pc.empty = true;
-      else { pc.tb = c; pc.chi = b; }
-    }
-    if (ntrL <= 0) pc.empty = true;
-  } else {
-    const int b = nb - (q - nb - 1);
-    pc.part = 1; pc.ta = 0; pc.tb = ntrR - 1;
-    if (b < nb) {
-      const int c = cut_at(k, b);
-      if (c < 0) pc.empty = true;
-      else { pc.ta = c; pc.clo = b; }
-    }
-    const int f = kept_below(k, b);
-    if (f >= 0) { pc.tb = cut_at(k, f); pc.chi = f; }
-    if (ntrR <= 0) pc.empty = true;
-  }
-  return pc;
-}
-
-// trips of the two parts of walk w (0 when the walk is empty)
-template <class SM>
-__device__ __forceinline__ void part_trips(const SM& S, int w, int& ntrL, int& ntrR) {
-  const Walk& W = S.w[w];
-  const int near = S.pt[W.p].nearest;
-  ntrL = W.len ? (near >> 7) - ((near - W.nl) >> 7) + 1 : 0;
-  ntrR = W.len && W.nr > 0 ? ((near + W.nr) >> 7) - ((near + 1) >> 7) + 1 : 0;
-}
-
-__device__ __forceinline__ int first_set128(unsigned long long b0, unsigned long long b1) {
-  return b0 ? __ffsll(b0) - 1 : (b1 ? 64 + __ffsll(b1) - 1 : 128);
-}
-__device__ __forceinline__ int last_set128(unsigned long long b0, unsigned long long b1) {
-  return b1 ? 127 - __clzll(b1) : (b0 ? 63 - __clzll(b0) : -1);
-}
-
-// one segment of one piece by one wave: nt trips from block t0 (absolute), the part's site range
-// masking its first and last trips, and the piece's lazy cuts (thresholds dlo on the first trip,
-// dhi on the last; DNONE: none) masking the boundary trips it shares with its neighbours.  A
-// lazy cut is a function of the trip's sites alone (a ballot of |d| >= D over the part's sites of
-// the trip), so the two pieces on either side of it split that trip's sites exactly between them,
-// whatever the data.  Otherwise as run_segment_idx, whose trip this is.
-template <bool LDS, class SM>
-__device__ __forceinline__ void run_piece_seg(SM& S, int w, int part, int sid, int t0, int nt, uint32_t dlo,
-                                              uint32_t dhi, const Params& P, int lane, double& acc, double& accm) {
-  constexpr int U = 2;
-  const Walk& W = S.w[w];
-  const Pt& pt = S.pt[W.p];
-  const uint32_t usweep = (uint32_t)pt.sweep ^ POS_BIAS;
-  const double la = W.la, inv = pt.inv_u;
-  const int lo = pt.nearest - W.nl;
-  const int plo = part ? pt.nearest + 1 : lo, phi = part ? pt.nearest + W.nr : pt.nearest;
-  const int ivc0 = __builtin_amdgcn_readfirstlane(S.ivc0);
-  const double* thrp = LDS ? reinterpret_cast<const double*>(fsclg_dyn + P.off_thr) : P.thr;
-  const int bs0 = t0 << 7;
-  int civ = 0;
-  double sum = 0.0, mag = 0.0;
-  uint4 nx = ld_trip(P.pr, (uint32_t)bs0, lane);
-  auto trip = [&](const int bs, const bool first, const bool lzlo, const bool lzhi, auto maskc) {
-    constexpr bool MASK = decltype(maskc)::value;
-    uint32_t pv[U], rv[U], ad[U];
-    bool valid[U];
-    pv[0] = nx.x; rv[0] = nx.y; pv[1] = nx.z; rv[1] = nx.w;
-#pragma unroll
-    for (int u = 0; u < U; u++) ad[u] = absdist(pv[u], usweep);
-    if constexpr (MASK) {
-      int kmin = max(plo - bs, 0), kmax = min(phi - bs, 127);
-      const bool in0 = lane >= kmin && lane <= kmax, in1 = lane + 64 >= kmin && lane + 64 <= kmax;
-      if (lzlo) {
-        const unsigned long long b0 = __ballot(in0 && ad[0] >= dlo), b1 = __ballot(in1 && ad[1] >= dlo);
-        kmin = max(kmin, part ? first_set128(b0, b1) : last_set128(b0, b1) + 1);
-      }
-      if (lzhi) {
-        const unsigned long long b0 = __ballot(in0 && ad[0] >= dhi), b1 = __ballot(in1 && ad[1] >= dhi);
-        kmax = min(kmax, part ? first_set128(b0, b1) - 1 : last_set128(b0, b1));
-      }
-      valid[0] = lane >= kmin && lane <= kmax;
-      valid[1] = lane + 64 >= kmin && lane + 64 <= kmax;
-#pragma unroll
-      for (int u = 0; u < U; u++) if (!valid[u]) rv[u] = 0u;  // zero sentinel row
-    } else {
-      valid[0] = valid[1] = true;
-    }
-    double x[U];
-    bool far = true, mid = true;
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      far = far && (ad[u] - 0x1000000u < (uint32_t)P.lt_span);
-      mid = mid && (ad[u] - 0x10000u < 0xFF0000u);
-    }
-    if (LDS && __builtin_amdgcn_ballot_w64(far) == ~0ull) {
-      const double* lt2 = reinterpret_cast<const double*>(fsclg_dyn + P.off_lt);
-#pragma unroll
-      for (int u = 0; u < U; u++) x[u] = lt2[ad[u] >> 16] + la;
-    } else if (__builtin_amdgcn_ballot_w64(mid) == ~0ull) {
-      const char* lt1 = reinterpret_cast<const char*>(P.logt3 + 0x10000);
-#pragma unroll
-      for (int u = 0; u < U; u++) x[u] = *reinterpret_cast<const double*>(lt1 + ((ad[u] >> 8) << 3)) + la;
-    } else {
-#pragma unroll
-      for (int u = 0; u < U; u++) x[u] = logt_lds<LDS>(ad[u], P) + la;
-    }
-    if (first) civ = __builtin_amdgcn_readfirstlane(interval_of<LDS>(readlane_f64(x[U - 1], 63), S, P));
-    const double tlo = thrp[civ], thi = thrp[civ + 1];
-    unsigned long long inm = ~0ull;
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      if constexpr (MASK) {
-        const bool ok = ((x[u] >= tlo) && (x[u] < thi)) || !valid[u];
-        inm &= __builtin_amdgcn_ballot_w64(ok);
-      } else {
-        inm &= __builtin_amdgcn_ballot_w64(x[u] >= tlo) & __builtin_amdgcn_ballot_w64(x[u] < thi);
-      }
-    }
-    const bool uni = inm == ~0ull;
-#ifdef FSCLG_PATHSTATS  // diagnostic: trips per path in the stats slots 4 (per-lane), 5 (LDS), 6 (global)
-    if (lane == 0) atomicAdd(&S.cnt[!uni ? 4 : ((LDS && (uint32_t)(civ - ivc0) < (uint32_t)P.n_civ) ? 5 : 6)], 1ull);
-#endif
-    double2 ca[U], cb[U];
-    if (uni) {
-      const uint32_t ci = (uint32_t)(civ - ivc0);
-      if (LDS && ci < (uint32_t)P.n_civ) {
-        const char* lb = fsclg_dyn + (__umul24(ci, (uint32_t)P.stride) << 5);
-#pragma unroll
-        for (int u = 0; u < U; u++) coef_ld(lb, rv[u] << 4, P, ca[u], cb[u]);
-      } else {
-        const char* gb = reinterpret_cast<const char*>(P.coef) + (__umul24((uint32_t)civ, (uint32_t)P.stride) << 5);
-#pragma unroll
-        for (int u = 0; u < U; u++) coef_ld(gb, rv[u] << 4, P, ca[u], cb[u]);
-      }
-    } else {
-      int iv[U];
-      coef_stage<LDS, U>(x, rv, S, P, ivc0, ca, cb, iv);
-      civ = __builtin_amdgcn_readlane(iv[U - 1], 63);
-    }
-    double nul[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) nul[u] = null_of<LDS>(rv[u], S, P);
-    __builtin_amdgcn_sched_barrier(0);
-    nx = ld_trip(P.pr, (uint32_t)(bs + 128), lane);  // the next trip's sites (PAD covers the last look-ahead)
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const double y = x[u] * (ca[u].x * x[u] * x[u] + ca[u].y * x[u] + cb[u].x) + cb[u].y;
-      const double q = (y - nul[u]) * inv;
-      const double R = rint(q);
-      const double fr = q - R;
-      if (__ballot(fabs(fr) == 0.5)) {
-        const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-        const unsigned long long ps = __ballot(odd_int(sum));
-        const unsigned long long pr = __ballot(odd_int(R));
-        const int pre = (__popcll(ps) + __popcll(pr & below)) & 1;
-        if (fabs(fr) == 0.5) {
-          const int ti = atomicAdd(&S.n_ties, 1);
-          if (ti < MAXTIES)
-            S.ties[ti] = (int)(((unsigned)sid << 25) | ((unsigned)w << 20) | ((fr < 0.0 ? 1u : 0u) << 19) |
-                               ((unsigned)pre << 18) | (unsigned)(bs + 64 * u + lane - lo));
-        }
-      }
-      sum += R;
-      mag += fabs(R);
-    }
-  };
-  // the masked trips (a lazy cut, or the part's own first / last block) can only be the first and
-  // the last: peeled off, so that the loop body is the unmasked trip alone (a join of both kinds in
-  // the loop makes the waits for the look-ahead load conservative: measured 1.7x per trip)
-  const bool m0 = dlo != DNONE || bs0 < plo || (nt == 1 && (dhi != DNONE || bs0 + 127 > phi));
-  const int bl = bs0 + 128 * (nt - 1);
-  const bool ml = nt > 1 && (dhi != DNONE || bl + 127 > phi);
-  int t = 0;
-  if (m0) { trip(bs0, true, dlo != DNONE, nt == 1 && dhi != DNONE, std::true_type{}); t = 1; }
-  const int tend = ml ? nt - 1 : nt;
-  for (; t < tend; t++) trip(bs0 + 128 * t, t == 0, false, false, std::false_type{});
-  if (ml) trip(bl, false, false, dhi != DNONE, std::true_type{});
-  const unsigned long long odd = __ballot(odd_int(sum));
-  if (lane == 0 && (__popcll(odd) & 1)) atomicXor(&S.segbits[w][sid >> 5], 1u << (sid & 31));
-  acc += sum;
-  accm += mag;
-}
-
-// the last t in (lo, hi) whose first position is <= key (STRICT: < key), lo if none (positions
-// ascend over (lo, hi)): an 8-ary search, seven independent probes per dependent round
-template <bool STRICT>
-__device__ __forceinline__ int tpos_search(const int32_t* __restrict__ tpos, int lo, int hi, long long key) {
-  while (hi - lo > 1) {
-    const long long span = hi - lo;
-    int m[7];
-    bool ok[7];
-#pragma unroll
-    for (int k = 0; k < 7; k++) m[k] = lo + (int)((span * (k + 1)) >> 3);
-#pragma unroll
-    for (int k = 0; k < 7; k++) { const long long v = tpos[m[k]]; ok[k] = STRICT ? v < key : v <= key; }
-    int nlo = lo, nhi = hi;
-#pragma unroll
-    for (int k = 0; k < 7; k++)
-      if (m[k] > lo && m[k] < hi) {
-        if (ok[k]) nlo = max(nlo, m[k]);
-        else nhi = min(nhi, m[k]);
-      }
-    lo = nlo; hi = nhi;
-  }
-  return lo;
-}
-
-// the |d| bound of band b for walk w (band b's sites: |d| >= it)
-__device__ __forceinline__ uint32_t band_d(const BandLds& bd, int w, int b) {
-  return bd.dv[w][b];
-}
-
-// eval_walks in band mode: bounds, the bands and their cuts, the segment numbering, then the
-// groups band by band (a "run" stages one band's window and may carry the following bands whose
-// pieces are too few to pay for their own), the remainder last; resolve as eval_walks.
-template <bool LDS, class SM>
-__device__ __forceinline__ void eval_walks_band(SM& S, const Params& P) {
-  BandLds& bd = *reinterpret_cast<BandLds*>(fsclg_dyn + P.off_bd);
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nw = __builtin_amdgcn_readfirstlane(S.nwalk);
-#ifdef FSCLG_PHASE_TIMING
-  unsigned long long t0 = 0;
-  if (tid == 0) t0 = wall_clock64();
-#define PHASE_MARK(k) do { if (tid == 0) { const unsigned long long t1 = wall_clock64(); S.tph[k] += t1 - t0; t0 = t1; } } while (0)
-#else
-#define PHASE_MARK(k) do { } while (0)
-#endif
-  walk_bounds_par(S, P, tid, nw);
-  if (tid < nw) {
-    S.P[tid] = 0; S.Q[tid] = 0; S.Pd[tid] = 0.0; S.Qd[tid] = 0.0; S.wflag[tid] = 0; S.need_slow[tid] = 0;
-    for (int j = 0; j < SEGWORDS; j++) S.segbits[tid][j] = 0;
-  }
-  if (tid <= NBMAX) { bd.gitems[tid] = 0; bd.gtrips[tid] = 0; }
-  if (tid == 0) S.n_ties = 0;
-  __syncthreads();
-  // the bands: K-interval windows from the phase's top interval T downwards (wave 0, a lane per walk)
-  if (wave == 0) {
-    const int K = P.n_civ;
-    const bool act = lane < nw;
-    int len = 0, top = -1;
-    if (act) {
-      Walk& W = S.w[lane];
-      len = W.len ? 1 + W.nl + W.nr : 0;
-      W.len = len;
-      if (len) top = interval_of<LDS>(fmax(W.xl, W.xr), S, P);
-    }
-    int T = top;
-    long long terms = len;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { T = max(T, __shfl_xor(T, o, 64)); terms += __shfl_xor(terms, o, 64); }
-    if (lane == 0) {
-      int nb = 0;
-      if (T >= 0)
-        while (nb < min(P.band_nb, NBMAX)) {
-          const int base = T - K * (nb + 1) + 1;
-          bd.bbase[nb++] = max(base, 0);
-          if (base <= 0) break;
-        }
-      bd.nb = nb;
-      S.cnt[0] += (unsigned long long)terms;
-      S.cnt[2] += nw;
-    }
-  }
-  __syncthreads();
-  const int nb = __builtin_amdgcn_readfirstlane(bd.nb);
-  // the cuts (a thread per walk, part, band): the trip holding the part's first site in walk order
-  // whose |d| reaches the band, by bisection over the trips' first positions (sorted within the
-  // part; the part's first trip counts as at or before the cut); -1 if the part's farthest site
-  // (its largest |d|) stays below the band
-  {
-    const double* thrp = LDS ? reinterpret_cast<const double*>(fsclg_dyn + P.off_thr) : P.thr;
-    for (int it = tid; it < nw * 2 * nb; it += WG) {
-      const int w = it / (2 * nb), part = (it / nb) & 1, b = it % nb;
-      const Walk& W = S.w[w];
-      const Pt& pt = S.pt[W.p];
-      const int near = pt.nearest;
-      int c = -1;
-      if (W.len && (part == 0 || W.nr > 0) && (part ? W.xr : W.xl) >= thrp[bd.bbase[b]]) {
-        const uint32_t dvb = P.dband[(size_t)W.kd * (size_t)P.nd + (size_t)bd.bbase[b]];
-        bd.dv[w][b] = dvb;
-        const long long D = (long long)dvb;
-        const long long sw = pt.sweep;
-        int t0, lo, hi;
-        if (part == 0) {  // the last trip whose first site has pos <= sweep - D
-          t0 = (near - W.nl) >> 7;
-          lo = t0; hi = (near >> 7) + 1;
-          const long long Y = sw - D;
-          lo = tpos_search<false>(P.tpos, lo, hi, Y);
-        } else {          // the last trip whose first site has pos < sweep + D
-          t0 = (near + 1) >> 7;
-          lo = t0; hi = ((near + W.nr) >> 7) + 1;
-          const long long X = sw + D;
-          lo = tpos_search<true>(P.tpos, lo, hi, X);
-        }
-        c = lo - t0;
-      }
-      bd.cut[w][part][b] = (int16_t)c;
-    }
-  }
-  __syncthreads();
-  // merging, segment numbering and groups (a lane per walk, the walk's cuts in registers).  A cut is
-  // kept only where the pieces on both sides hold at least band_minp trips (small pieces cost a
-  // segment's fixed work and a masked trip each: 4.8x the segments of the walk-window path with
-  // every cut kept); a merged piece goes to the group of its band with the most trips
-  if (wave == 0) {
-    const bool act = lane < nw && S.w[lane < nw ? lane : 0].len;
-    int ntrL = 0, ntrR = 0;
-    if (lane < nw) part_trips(S, lane, ntrL, ntrR);
-    const int minp = P.band_minp;
-    int8_t qL[NBMAX + 1], qR[NBMAX + 1];  // the piece each group processes, per part
-#pragma unroll
-    for (int g = 0; g <= NBMAX; g++) { qL[g] = -1; qR[g] = -1; }
-    Cuts cl = load_cuts(bd, lane < nw ? lane : 0, 0), cr = load_cuts(bd, lane < nw ? lane : 0, 1);
-    if (act) {
-      // left part, index order: band 0, 1, ..., nb - 1, the remainder; piece b = (cut[b - 1], cut[b]]
-      int tr[NBMAX + 1];
-      int prev = -1;
-#pragma unroll
-      for (int b = 0; b <= NBMAX; b++) {
-        tr[b] = 0;
-        if (b <= nb) {
-          const int e = b < NBMAX && b < nb ? cl.c[b < NBMAX ? b : 0] : ntrL - 1;
-          if (e >= 0) { tr[b] = e - prev; prev = e; }
-        }
-      }
-      int last = -1, best = nb, btr = -1;
-#pragma unroll
-      for (int b = 0; b <= NBMAX; b++) {
-        if (b <= nb && tr[b] > btr) { btr = tr[b]; best = b; }
-        if (b < nb && b < NBMAX) {
-          const int c = cl.c[b < NBMAX ? b : 0];
-          if (c >= 0) {
-            if (c - last >= minp && ntrL - 1 - c >= minp) {
-#pragma unroll
-              for (int g = 0; g <= NBMAX; g++) if (g == best) qL[g] = (int8_t)b;
-              last = c; best = nb; btr = -1;
-            } else {
-              cl.c[b < NBMAX ? b : 0] = -2;
-            }
-          }
-        } else if (b == nb) {
-#pragma unroll
-          for (int g = 0; g <= NBMAX; g++) if (g == best) qL[g] = (int8_t)nb;
-        }
-      }
-    }
-    if (act && ntrR > 0) {
-      // right part, index order: the remainder, band nb - 1, ..., band 0; piece b = [cut[b], cut[b - 1])
-      int tr[NBMAX];
-      int nxt = ntrR;  // the start of the nearest reached band above
-#pragma unroll
-      for (int b = 0; b < NBMAX; b++) {
-        tr[b] = 0;
-        if (b < nb && cr.c[b] >= 0) { tr[b] = nxt - cr.c[b]; nxt = cr.c[b]; }
-      }
-      int last = 0, low = nb, best = nb, btr = nxt;  // the remainder: [0, lowest reached cut)
-#pragma unroll
-      for (int k = NBMAX - 1; k >= 0; k--) {  // from the bottom band up
-        if (k < nb && cr.c[k] >= 0) {
-          const int c = cr.c[k];
-          if (c - last >= minp && ntrR - c >= minp) {
-#pragma unroll
-            for (int g = 0; g <= NBMAX; g++) if (g == best) qR[g] = (int8_t)(nb + 1 + (nb - low));
-            last = c; low = k; best = k; btr = tr[k];
-          } else {
-            cr.c[k] = -2;
-            if (tr[k] > btr) { btr = tr[k]; best = k; }
-          }
-        }
-      }
-#pragma unroll
-      for (int g = 0; g <= NBMAX; g++) if (g == best) qR[g] = (int8_t)(nb + 1 + (nb - low));
-    }
-    if (lane < nw) {
-      store_cuts(bd, lane, 0, cl);
-      store_cuts(bd, lane, 1, cr);
-#pragma unroll
-      for (int g = 0; g <= NBMAX; g++) { bd.qof[lane][0][g] = qL[g]; bd.qof[lane][1][g] = qR[g]; }
-    }
-    // segment ids in site-index order; each group's segments and trips (LDS atomics)
-    int run = 0;
-    for (int q = 0; q < 2 * (nb + 1); q++) {
-      int nseg = 0;
-      if (act) {
-        const Piece pc = piece_of(q <= nb ? cl : cr, q, nb, ntrL, ntrR);
-        if (!pc.empty && pc.tb >= pc.ta) {
-          nseg = (pc.tb - pc.ta + TPS) / TPS;
-          int g = -1;
-#pragma unroll
-          for (int j = 0; j <= NBMAX; j++) if ((q <= nb ? qL[j] : qR[j]) == q) g = j;
-          if (g >= 0) { atomicAdd(&bd.gitems[g], nseg); atomicAdd(&bd.gtrips[g], pc.tb - pc.ta + 1); }
-        }
-      }
-      if (lane < nw) bd.sb[lane][q] = (uint8_t)run;
-      run += nseg;
-    }
-    if (lane < nw) {
-      bd.sb[lane][2 * (nb + 1)] = (uint8_t)run;
-      S.w[lane].nsl = bd.sb[lane][nb + 1];
-      S.w[lane].nseg = run;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {  // runs: a band of at least band_th trips stages its window; the rest ride along
-      int nr = 0;
-      for (int g = 0; g <= nb; g++) {
-        const bool st = g < nb && bd.gtrips[g] >= P.band_th;
-        if (st || nr == 0) { bd.run_g0[nr] = g; bd.run_stage[nr] = st ? 1 : 0; nr++; }
-      }
-      bd.run_g0[nr] = nb + 1;
-      bd.nrun = nr;
-  }
-  __syncthreads();
-  PHASE_MARK(0);
-  {
-    int cw = -1;
-    double acc = 0.0, accm = 0.0;
-    const int nrun = __builtin_amdgcn_readfirstlane(bd.nrun);
-    for (int r = 0; r < nrun; r++) {
-      const int g0 = __builtin_amdgcn_readfirstlane(bd.run_g0[r]), g1 = __builtin_amdgcn_readfirstlane(bd.run_g0[r + 1]);
-      if (__builtin_amdgcn_readfirstlane(bd.run_stage[r])) {
-        const int wb = __builtin_amdgcn_readfirstlane(bd.bbase[g0]);
-        if (wb != __builtin_amdgcn_readfirstlane(S.ivc0)) {  // uniform over the workgroup
-          __syncthreads();
-          load_window(S, P, wb);
-          __syncthreads();
-        }
-      }
-      int nit = 0;
-      for (int g = g0; g < g1; g++) nit += __builtin_amdgcn_readfirstlane(bd.gitems[g]);
-      // each wave takes a contiguous run of the items (consecutive items are mostly one walk's: one
-      // flush per walk, not per item)
-      int g = g0, e = 0, ebase = 0;  // entry e = (walk e >> 1, part e & 1) of group g: items from ebase
-      const int i1 = (nit * (wave + 1)) / NWAVE;
-      for (int i = (nit * wave) / NWAVE; i < i1; i++) {
-        int q, cnt;
-        for (;;) {
-          const int w = e >> 1, part = e & 1;
-          q = bd.qof[w][part][g];
-          cnt = q >= 0 ? (int)bd.sb[w][q + 1] - (int)bd.sb[w][q] : 0;
-          if (i < ebase + cnt) break;
-          ebase += cnt;
-          if (++e == 2 * nw) { e = 0; g++; }
-        }
-        const int w = e >> 1, part = e & 1, s = i - ebase;
-        const int sid = (int)bd.sb[w][q] + s;
-        int ntrL, ntrR;
-        part_trips(S, w, ntrL, ntrR);
-        const Piece pc = piece_of(load_cuts(bd, w, part), q, nb, ntrL, ntrR);
-        const Walk& W = S.w[w];
-        const int near = S.pt[W.p].nearest;
-        const int ts = pc.ta + s * TPS, nt = min(TPS, pc.tb - ts + 1);
-        const uint32_t dlo = (s == 0 && pc.clo >= 0) ? band_d(bd, w, pc.clo) : DNONE;
-        const uint32_t dhi = (ts + nt - 1 == pc.tb && pc.chi >= 0) ? band_d(bd, w, pc.chi) : DNONE;
-        const int tp0 = part ? (near + 1) >> 7 : (near - W.nl) >> 7;
-        if (w != cw) {
-          if (cw >= 0) flush_walk(S, cw, acc, accm, lane);
-          cw = w; acc = 0.0; accm = 0.0;
-        }
-#ifdef FSCLG_SEGSTATS  // diagnostic: segments in the stats slot 6 (n_ties)
-        if (lane == 0) atomicAdd(&S.cnt[6], 1ull);
-#endif
-        run_piece_seg<LDS>(S, w, part, sid, tp0 + ts, nt, dlo, dhi, P, lane, acc, accm);
-      }
-    }
-    if (cw >= 0) flush_walk(S, cw, acc, accm, lane);
-  }
-  PHASE_MARK(1);
-  __syncthreads();
-  PHASE_MARK(2);
-  if (tid < nw) resolve_walk<SEG, true>(S, tid);
-#ifndef FSCLG_SEGSTATS
-  if (tid == 0) S.cnt[6] += (unsigned long long)S.n_ties;
-#endif
-  __syncthreads();
-  PHASE_MARK(3);
-#undef PHASE_MARK
 }
 
 // agent-scope atomics: performed at the memory side, coherent across the XCDs' L2s
@@ -1801,12 +1127,6 @@ __device__ __forceinline__ void combine_members(SM& S, const Params& P, int nw) 
 
 template <bool LDS, bool SPLIT, class SM>
 __device__ __forceinline__ void eval_walks(SM& S, const Params& P) {
-  if constexpr (SM::HAS_BAND && LDS && !SPLIT) {
-    if (P.band_th >= 0 && P.n_civ > 0) {  // band mode (FSCLG_BAND_TH=-1: the walk-window groups below)
-      eval_walks_band<LDS>(S, P);
-      return;
-    }
-  }
   constexpr int SEGN = SPLIT ? SEG_SPLIT : SEG;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nw = __builtin_amdgcn_readfirstlane(S.nwalk);
@@ -1892,7 +1212,7 @@ __device__ __forceinline__ void eval_walks(SM& S, const Params& P) {
   // miscompiled into a loop that never re-issued its atomic)
   {
     const int ngrp = __builtin_amdgcn_readfirstlane(S.ngrp);
-    int k = 0, cw = -1, nsg_run = 0;
+    int cw = -1, nsg_run = 0;
     double acc = 0.0, accm = 0.0;
     for (int gi = 0; gi < ngrp; gi++) {
      const int gwb = __builtin_amdgcn_readfirstlane(S.gwb[gi]);
@@ -1905,39 +1225,19 @@ __device__ __forceinline__ void eval_walks(SM& S, const Params& P) {
      // split cells: the members deal the segments round-robin
      const int mstride = SPLIT ? NWAVE * P.split : NWAVE;
      const int g0 = SPLIT ? __builtin_amdgcn_readfirstlane(S.member) * NWAVE + wave : wave;
-#if FSCLG_SITE_MAJOR
      // site-major: the group's ids run over the slices (j, part) = (0, left), (0, right), (1, left), ...;
      // slice (j, part) holds, in walk order, the walks whose part has more than j segments (lane l of
      // every wave holds the group's l-th walk and its part counts); id -> (walk, segment) by a ballot
      const int k0 = __builtin_amdgcn_readfirstlane(S.gk[gi]), nwg = __builtin_amdgcn_readfirstlane(S.gk[gi + 1]) - k0;
      int wl = 0, nsl_l = 0, nsr_l = 0;
      if (lane < nwg) { wl = S.word[k0 + lane]; nsl_l = S.w[wl].nsl; nsr_l = S.w[wl].nseg - nsl_l; }
-#if FSCLG_FAR_FIRST
-     // the slices from the farthest inwards: the phase ends on the dense near slices (every walk
-     // reaches them), so the waves run out of work together
-     int jmax = max(nsl_l, nsr_l) - 1;
-#pragma unroll
-     for (int o = 32; o > 0; o >>= 1) jmax = max(jmax, __shfl_xor(jmax, o, 64));
-     jmax = __builtin_amdgcn_readfirstlane(jmax);
-     int base = __builtin_amdgcn_readfirstlane(S.gseg[gi]), sj = jmax, spart = 0;
-#else
      int base = __builtin_amdgcn_readfirstlane(S.gseg[gi]), sj = 0, spart = 0;
-#endif
      unsigned long long M = __ballot(lane < nwg && (spart ? nsr_l : nsl_l) > sj);
-     (void)k;
-#endif
      for (int g = __builtin_amdgcn_readfirstlane(S.gseg[gi]) + g0; g < ge; g += mstride) {
-#if FSCLG_SITE_MAJOR
-#if FSCLG_FAR_FIRST
-      while (g >= base + (int)__popcll(M) && sj >= 0) {  // g < ge: a later slice holds it
-        base += (int)__popcll(M);
-        if (spart == 0) spart = 1; else { spart = 0; sj--; }
-#else
       while (g >= base + (int)__popcll(M) && sj < MAXSEG_W) {  // g < ge: a later slice holds it
         base += (int)__popcll(M);
         if (spart == 0) spart = 1; else { spart = 0; sj++; }
-#endif
-        M = __ballot(lane < nwg && (!FSCLG_FAR_FIRST || sj >= 0) && (spart ? nsr_l : nsl_l) > sj);
+        M = __ballot(lane < nwg && (spart ? nsr_l : nsl_l) > sj);
       }
       if (g >= base + (int)__popcll(M)) break;  // never: the slices hold exactly the group's segments
       const int rk = g - base;  // the rk-th walk of the slice
@@ -1945,18 +1245,10 @@ __device__ __forceinline__ void eval_walks(SM& S, const Params& P) {
       const int l = __ffsll(__ballot(((M >> lane) & 1ull) && below == rk)) - 1;
       const int w = __builtin_amdgcn_readlane(wl, l);
       const int sg = spart ? __builtin_amdgcn_readlane(nsl_l, l) + sj : __builtin_amdgcn_readlane(nsl_l, l) - 1 - sj;
-#else
-      while (k < nw - 1 && g >= S.w[S.word[k]].seg0 + S.w[S.word[k]].nseg) k++;  // walks own consecutive segment ranges
-      const int w = S.word[k];
-      const int sg = g - S.w[w].seg0;
-#endif
-      if (w != cw) {  // walk-major: the wave's segments of one walk are consecutive, one flush per walk
+      if (w != cw) {  // one flush per run of a walk's segments
         if (cw >= 0) flush_walk(S, cw, acc, accm, lane);
         cw = w; acc = 0.0; accm = 0.0;
       }
-#ifdef FSCLG_SEGSTATS
-      if (lane == 0) atomicAdd(&S.cnt[6], 1ull);
-#endif
       run_segment_idx<LDS, SEGN, SPLIT ? U_SPLIT : U_MAIN>(S, w, sg, sg + 1, P, lane, acc, accm);
       nsg_run++;
      }
@@ -1972,9 +1264,7 @@ __device__ __forceinline__ void eval_walks(SM& S, const Params& P) {
   IEV(5, 0, 0);  // combined
   TRACE("  segments done: ties=%d\n", S.n_ties);
   if (tid < nw) resolve_walk<SEGN>(S, tid);
-#ifndef FSCLG_SEGSTATS
   if (tid == 0) S.cnt[6] += (unsigned long long)S.n_ties;
-#endif
   __syncthreads();
   IEV(6, 0, 0);  // resolved
   PHASE_MARK(3);
@@ -2070,7 +1360,7 @@ __device__ __forceinline__ void search_maxalpha_pts(SM& S, const Params& P, int 
     S.w[tid].kd = a;
     S.w[tid].len = 0; S.w[tid].nl = S.w[tid].nr = 0;
   }
-  if (tid == 0) { S.nwalk = np * nc; S.cnt[3] += np; S.hkey = 0; }
+  if (tid == 0) { S.nwalk = np * nc; S.cnt[3] += np; }
   // refine walks for point p's list ci[p] (lane p), after the first `base` walks: wave 0, lane
   // p * MAXREF + r for walk r; returns (first << 8) | count of point p's walks in lane p and sets
   // S.nwalk (cnt[p] = 0: none for that point)
@@ -2183,7 +1473,7 @@ __device__ __forceinline__ void search_maxalpha_pts(SM& S, const Params& P, int 
       if (hit) pt.pad = pt.spad;
     }
     const unsigned hm = (unsigned)__ballot(hit) & all;
-    if (lane == 0) { S.hkey = 1 + S.pt[p0].ci; S.hitmask = (int)hm; }
+    if (lane == 0) S.hitmask = (int)hm;
   }
   __syncthreads();
   const unsigned hm = (unsigned)__builtin_amdgcn_readfirstlane(S.hitmask);
@@ -2259,12 +1549,6 @@ __device__ __forceinline__ void maxpos_body(SM& S, const Params& P) {
     load_window(S, P, P.ivc0);
     double* lt2 = reinterpret_cast<double*>(fsclg_dyn + P.off_lt);
     for (int j = 256 + tid; j < P.lt_hi; j += WG) lt2[j] = P.logt3[2 * 0x10000 + j];
-#if FSCLG_LOG_CALC
-    if (lx_kernel<SM>() && P.lx_on) {
-      double* lx = reinterpret_cast<double*>(fsclg_dyn + P.off_lx);
-      for (int j = tid; j < LX_BYTES / 8; j += WG) lx[j] = P.lx[j];
-    }
-#endif
   } else if (tid == 0) S.ivc0 = 0;
   __syncthreads();
   if (P.mode == 1) {
@@ -2383,10 +1667,10 @@ __device__ __forceinline__ void maxpos_body(SM& S, const Params& P) {
 #ifndef FSCLG_WPE_SPLIT
 #define FSCLG_WPE_SPLIT 6
 #endif
-template <bool LDS, bool BAND = false>
+template <bool LDS>
 __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(FSCLG_WPE, FSCLG_WPE)))
 search_maxpos_kernel(Params P) {
-  __shared__ SmemT<MAXWALK, BAND> S;
+  __shared__ Smem S;
   maxpos_body<LDS, false>(S, P);
 }
 
@@ -2433,12 +1717,6 @@ __device__ __forceinline__ void profile_body(SM& S, const Params& P, const ProfC
     load_window(S, P, P.ivc0);
     double* lt2 = reinterpret_cast<double*>(fsclg_dyn + P.off_lt);
     for (int j = 256 + tid; j < P.lt_hi; j += WG) lt2[j] = P.logt3[2 * 0x10000 + j];
-#if FSCLG_LOG_CALC
-    if (lx_kernel<SM>() && P.lx_on) {
-      double* lx = reinterpret_cast<double*>(fsclg_dyn + P.off_lx);
-      for (int j = tid; j < LX_BYTES / 8; j += WG) lx[j] = P.lx[j];
-    }
-#endif
   } else if (tid == 0) S.ivc0 = 0;
   __syncthreads();
   const ProfChunk c = chunks[k];
@@ -4148,7 +3426,6 @@ struct Batch {
   Buf<int2, PINNED> p_epos, p_cell_ep;
   Buf<unsigned long long, PINNED> p_ctrace;  // FSCLG_CELL_TRACE=<file>: per-cell timing appended per launch
   int trace_n = 0;                  // cells of the traced launch (the event area follows them)
-  unsigned long long* ivhist = nullptr;    // this launch measures the interval histogram (FSCLG_IVHIST)
   bool traced = false;
   std::vector<int> uidx, upos, order, sidx;
   cellorder::RangeMemo<fsclg_cell_t, int2> wr_memo;  // its cells' window ranges at the last submit
@@ -4232,8 +3509,6 @@ struct fsclg_ctx {
   hipEvent_t wev0, wev1;          // window null-sum kernel timing
   // tables
   double* d_logt = nullptr;
-  double* d_lx = nullptr;         // FSCLG_LOG_CALC: logx_mid's table (LX_BYTES)
-  int lx_on = 0;
   double* d_coef = nullptr;
   double* d_null = nullptr;
   double* d_thr = nullptr;
@@ -4283,19 +3558,12 @@ struct fsclg_ctx {
   Batch batch[NBATCH];
   // LDS coefficient cache plan (fsclg_plan_cache)
   bool plan_dirty = true;
-  bool hist_pending = false;          // the next search_maxpos launch measures the interval histogram
-  Buf<unsigned long long, DEVICE> d_ivhist;
   int c_ivc0 = 0, c_civ = 0, c_crow = 0;
   double c_cover = 0.0;
-  int c_ivc0_b = 0, c_civ_b = 0;         // the window beside band mode's BandLds (Params::off_bd)
-  double c_cover_b = 0.0;
   // alpha grid
   std::vector<double> h_coarse, h_refine;
   std::vector<int32_t> h_nref;
   uint32_t* d_dfail = nullptr;     // walk thresholds of the alpha grid (Params::dfail)
-  uint32_t* d_dband = nullptr;     // band cuts of the alpha grid (Params::dband)
-  int32_t* d_tpos = nullptr;       // position of every 128th site (Params::tpos)
-  std::vector<double> h_thr;       // the interval thresholds (Params::thr)
   double* d_la_coarse = nullptr;
   double* d_la_refine = nullptr;
   int32_t* d_n_refine = nullptr;
@@ -4333,7 +3601,6 @@ static int upload(Buf<T, DEVICE>& b, const T* src, size_t n, hipStream_t s) {
 }
 
 static int update_dfail(fsclg_ctx* c);
-static int update_dband(fsclg_ctx* c);
 
 // least double x with (int)((x - LOG_AD_MIN) / step) >= j (sm-spline.c:52), by bisection over the
 // ordered doubles; the host evaluates the reference's expression with IEEE division
@@ -4422,7 +3689,7 @@ int fsclg_close(fsclg_ctx* c) {
   hipDeviceSynchronize();
   void* ptrs[] = {c->d_logt, c->d_coef, c->d_null, c->d_thr, c->d_pr0,
                   c->d_chr_start, c->d_chr_n, c->d_la_coarse, c->d_la_refine, c->d_n_refine,
-                  c->d_stats, c->d_dfail, c->d_dband, c->d_tpos, c->d_lx,
+                  c->d_stats, c->d_dfail,
                   c->d_smp_coef, c->d_smp_prefix, c->d_smp_depth, c->d_smp_chr,
                   c->d_exp_fcoef, c->d_exp_neutral, c->d_exp_null_u, c->d_exp_null_f, c->d_exp_depth, c->d_exp_class};
   for (void* p : ptrs) if (p) hipFree(p);
@@ -4450,63 +3717,6 @@ static bool any_pending(const fsclg_ctx* c) {
   return false;
 }
 
-#if FSCLG_LOG_CALC
-// logx_mid's table: per k, log(c) as hi + lo (long double) and RN(1/c); then every entry of the
-// mid branch evaluated here with the device's operations, and the lo part of a k whose entries
-// do not all reproduce the reference's table shifted (in 2^-68 steps, up to 2^-59) until they do;
-// then the device's own evaluation checked once against the uploaded table.  Any entry still
-// off: the mid branch keeps the gather (lx_on 0).
-static int logx_setup(fsclg_ctx* c, const std::vector<double>& lt3) {
-  std::vector<double> lx(LX_BYTES / 8, 0.0);
-  for (int k = 0; k < 256; k++) {
-    const double cc = (256.0 + k) * 128.0;
-    const long double lc = logl((long double)cc);
-    lx[4 * k] = (double)lc;
-    lx[4 * k + 1] = (double)(lc - (long double)lx[4 * k]);
-    lx[4 * k + 2] = 1.0 / cc;
-  }
-  auto k_of = [](uint32_t i) { return ((i << (15 - (31 - __builtin_clz(i)))) >> 7) & 255u; };
-  auto k_ok = [&](uint32_t k) {
-    for (uint32_t i = 256; i < 0x10000u; i++)
-      if (k_of(i) == k && logx_mid(i, lx.data()) != lt3[0x10000u + i]) return false;
-    return true;
-  };
-  std::vector<char> bad_k(256, 0);
-  for (uint32_t i = 256; i < 0x10000u; i++)
-    if (logx_mid(i, lx.data()) != lt3[0x10000u + i]) bad_k[k_of(i)] = 1;
-  bool ok = true;
-  for (int k = 0; k < 256 && ok; k++) {
-    if (!bad_k[k]) continue;
-    const double base = lx[4 * k + 1];
-    bool fixed = false;
-    for (int t = 1; t <= 512 && !fixed; t++)
-      for (int sg = -1; sg <= 1 && !fixed; sg += 2) {
-        lx[4 * k + 1] = base + sg * t * 0x1p-68;
-        fixed = k_ok((uint32_t)k);
-      }
-    if (!fixed) { lx[4 * k + 1] = base; ok = false; }
-  }
-  c->lx_on = 0;
-  if (!ok) return FSCLG_OK;
-  int r;
-  if ((r = upload(&c->d_lx, lx.data(), lx.size(), c->ustream))) return r;
-  unsigned long long* d_bad = nullptr;
-  unsigned long long bad = 1;
-  HIPCHK(hipMalloc((void**)&d_bad, sizeof bad), "hipMalloc");
-  HIPCHK(hipMemsetAsync(d_bad, 0, sizeof bad, c->ustream), "hipMemsetAsync");
-  hipLaunchKernelGGL(logx_check_kernel, dim3((0x10000 - 256 + 255) / 256), dim3(256), 0, c->ustream, c->d_lx, c->d_logt,
-                     d_bad);
-  HIPCHK(hipGetLastError(), "launch logx_check_kernel");
-  HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, c->ustream), "hipMemcpyAsync");
-  HIPCHK(hipStreamSynchronize(c->ustream), "hipStreamSynchronize");
-  hipFree(d_bad);
-  c->lx_on = bad == 0 && !getenv("FSCLG_NO_LOGX");
-  if (bad) fprintf(stderr, "fsclg: the device's mid-branch log distances differ from the table in %llu entries: "
-                           "the table is gathered instead\n", bad);
-  return FSCLG_OK;
-}
-#endif
-
 int fsclg_upload_tables(fsclg_ctx* c, const double* log_table, const double* coef, int n_rows, int n_iv,
                         const double* nullrow, double log_ad_step) {
   if (!c || !log_table || !coef || !nullrow || n_rows <= 0 || n_iv <= 0) return set_err(FSCLG_E_ARG, "tables");
@@ -4525,9 +3735,6 @@ int fsclg_upload_tables(fsclg_ctx* c, const double* log_table, const double* coe
       lt3[(size_t)b * 0x10000 + i] = b ? (double)v : log_table[i];
     }
   if ((r = upload(&c->d_logt, lt3.data(), lt3.size(), c->ustream))) return r;
-#if FSCLG_LOG_CALC
-  if ((r = logx_setup(c, lt3))) return r;
-#endif
   c->h_lt3.swap(lt3);
   if ((r = update_dfail(c))) return r;
   // [row][iv][4] -> [iv][plane][1 + row][2] (coef_off): device row 0 is an all-zero sentinel
@@ -4550,9 +3757,7 @@ int fsclg_upload_tables(fsclg_ctx* c, const double* log_table, const double* coe
   thr[n_iv] = __builtin_inf();   // iv n_iv-1 never steps up (the reference clamps)
   if ((r = upload(&c->d_thr, thr.data(), thr.size(), c->ustream))) return r;
   c->n_rows = n_rows; c->n_iv = n_iv; c->step = log_ad_step;
-  c->h_thr = thr;
   c->exp_n_depths = 0;  // (fsclg_expect_tables names the rows of these tables)
-  if ((r = update_dband(c))) return r;
   c->plan_dirty = true;
   for (Slot& S : c->slot) { S.win_valid = false; S.ctab_valid = false; }
   return FSCLG_OK;
@@ -4573,11 +3778,6 @@ int fsclg_upload_snps(fsclg_ctx* c, const int32_t* pos, const uint32_t* row, int
   std::vector<uint2> pr(((size_t)n_snps + 127) / 128 * 128 + PAD, make_uint2(POS_BIAS, 0u));
   for (int i = 0; i < n_snps; i++) pr[phys((uint32_t)i)] = make_uint2((uint32_t)pos[i] ^ POS_BIAS, row[i] + 1);
   if ((r = upload(&c->d_pr0, pr.data(), pr.size(), c->ustream))) return r;
-  {  // band cut searches: the position of the first site of every 128-site block
-    std::vector<int32_t> tp(((size_t)n_snps + 127) / 128);
-    for (size_t t = 0; t < tp.size(); t++) tp[t] = pos[t * 128];
-    if ((r = upload(&c->d_tpos, tp.data(), tp.size(), c->ustream))) return r;
-  }
   for (Slot& S : c->slot) {
     if ((r = upload(S.d_pr, pr.data(), pr.size(), c->ustream))) return r;
     if ((r = upload<double>(S.d_chr_null, nullptr, (size_t)n_chr, c->ustream))) return r;
@@ -4877,45 +4077,7 @@ static int update_dfail(fsclg_ctx* c) {
     }
     df[k] = (uint32_t)lo;
   }
-  int r = upload(&c->d_dfail, df.data(), df.size(), c->ustream);
-  return r ? r : update_dband(c);
-}
-
-// Params::dband for every alpha of the grid and every interval threshold: the least |d| with
-// fl(logt(|d|) + lalpha) >= thr[j] (the device's own add; logt3 nondecreasing, checked in
-// update_dfail), so a site lies in interval j or above iff its |d| reaches dband[alpha][j].
-// thr[0] = -inf: 0; thr[n_iv] = +inf: 0xFFFFFFFF (never).  Bands are cut on these.
-static int update_dband(fsclg_ctx* c) {
-  if (c->h_lt3.empty() || c->h_coarse.empty() || c->h_thr.empty() || c->n_iv <= 0) return FSCLG_OK;
-  const std::vector<double>& T = c->h_lt3;
-  auto lt = [&](uint64_t ad) {
-    const uint32_t sh = ad > 0xFFFFFFu ? 16u : (ad > 0xFFFFu ? 8u : 0u);
-    return T[(size_t)(ad >> sh) + ((size_t)sh << 13)];
-  };
-  std::vector<double> las(c->h_coarse);
-  las.insert(las.end(), c->h_refine.begin(), c->h_refine.end());
-  const int nd = c->n_iv + 1;
-  std::vector<uint32_t> db(las.size() * (size_t)nd);
-  for (size_t k = 0; k < las.size(); k++) {
-    const double la = las[k];
-    for (int j = 0; j < nd; j++) {
-      const double th = c->h_thr[j];
-      auto reaches = [&](uint64_t d) { volatile double x = lt(d) + la; return x >= th; };
-      uint32_t v;
-      if (reaches(0)) v = 0;
-      else if (!reaches(0xFFFFFFFFull)) v = 0xFFFFFFFFu;
-      else {
-        uint64_t lo = 0, hi = 0xFFFFFFFFull;  // reaches(lo) false, reaches(hi) true
-        while (hi - lo > 1) {
-          const uint64_t m = lo + (hi - lo) / 2;
-          if (reaches(m)) hi = m; else lo = m;
-        }
-        v = (uint32_t)hi;
-      }
-      db[k * nd + j] = v;
-    }
-  }
-  return upload(&c->d_dband, db.data(), db.size(), c->ustream);
+  return upload(&c->d_dfail, df.data(), df.size(), c->ustream);
 }
 
 static int ensure_io(Batch& B, int n) {
@@ -5234,14 +4396,11 @@ static int slot_windows_impl(fsclg_ctx* c, int slot, const fsclg_cell_t* cells, 
 // Every row is held: a miss sends the whole wave's gather to the global table, so a row
 // prefix (a per-lane miss rate) would miss in nearly every wave, while an interval window
 // misses in whole waves (neighbouring sites have nearly equal log distance).
-constexpr int BAND_LDS_BYTES = (int)((sizeof(BandLds) + 15) / 16 * 16);
 constexpr int STAT_M = (int)((sizeof(Smem) + 15) / 16 * 16);  // the static LDS of the unsplit kernels
 static void choose_window(fsclg_ctx* c, const std::vector<double>& hist) {
   c->c_ivc0 = 0; c->c_civ = 0; c->c_crow = 0; c->c_cover = 0.0;
-  c->c_ivc0_b = 0; c->c_civ_b = 0; c->c_cover_b = 0.0;
   const int stat = (int)((sizeof(Smem) + 15) / 16 * 16);
-  const int room = LDS_WG - stat - (c->n_iv + 1) * 8 - (c->n_rows + 1) * 8 - (c->lt_hi ? (c->lt_hi - 256) * 8 : 0) -
-                   (c->lx_on && FSCLG_LOG_CALC >= 2 ? LX_BYTES + 16 : 0);
+  const int room = LDS_WG - stat - (c->n_iv + 1) * 8 - (c->n_rows + 1) * 8 - (c->lt_hi ? (c->lt_hi - 256) * 8 : 0);
   double htot = 0.0;
   for (double h : hist) htot += h;
   if (room < 32 || htot <= 0) return;
@@ -5261,9 +4420,6 @@ static void choose_window(fsclg_ctx* c, const std::vector<double>& hist) {
   int bj;
   c->c_cover = best_iv(K, bj);
   c->c_ivc0 = bj; c->c_civ = K; c->c_crow = R;
-  // band mode's window: the same choice in the room its BandLds leaves (16 B aligned after the rest)
-  const int Kb = std::min(c->n_iv, (room - BAND_LDS_BYTES - 16) / (R * 32));
-  if (Kb > 0) { c->c_cover_b = best_iv(Kb, bj); c->c_ivc0_b = bj; c->c_civ_b = Kb; }
 }
 
 // Choose the LDS coefficient window: intervals [ivc0, ivc0 + K) x every device row, K * rows
@@ -5274,11 +4430,9 @@ static void choose_window(fsclg_ctx* c, const std::vector<double>& hist) {
 static void plan_cache(fsclg_ctx* c) {
   c->plan_dirty = false;
   c->c_ivc0 = 0; c->c_civ = 0; c->c_crow = 0; c->c_cover = 0.0;
-  c->c_ivc0_b = 0; c->c_civ_b = 0; c->c_cover_b = 0.0;
   if (getenv("FSCLG_NO_WINDOW")) return;  // experiment: every coefficient from the global table
   const int stat = (int)((sizeof(Smem) + 15) / 16 * 16);
-  const int room = LDS_WG - stat - (c->n_iv + 1) * 8 - (c->n_rows + 1) * 8 - (c->lt_hi ? (c->lt_hi - 256) * 8 : 0) -
-                   (c->lx_on && FSCLG_LOG_CALC >= 2 ? LX_BYTES + 16 : 0);
+  const int room = LDS_WG - stat - (c->n_iv + 1) * 8 - (c->n_rows + 1) * 8 - (c->lt_hi ? (c->lt_hi - 256) * 8 : 0);
   if (room < 32 || c->n_iv <= 0 || c->h_pos.empty() || c->h_coarse.empty() || c->h_lt3.empty()) return;
   std::vector<double> hist(c->n_iv, 0.0);
   std::vector<double> las(c->h_coarse);
@@ -5305,36 +4459,23 @@ static void plan_cache(fsclg_ctx* c) {
     }
   }
   choose_window(c, hist);
-#ifdef FSCLG_IVHIST  // diagnostic builds measure the real histogram in the first launch
-  c->hist_pending = true;
-#endif
 }
 
-// band mode is off by default (-1: the walk-window path with site-major dealing, faster at C4 and C5,
-// HISTORY §R6.3); FSCLG_BAND_TH=16 turns it on
-static int band_default(const fsclg_ctx* c) { (void)c; return -1; }
-
 // Params' dynamic LDS layout: the coefficient window (intervals [ivc0, ivc0 + n_civ) of every row), the
-// thresholds, the null rows, logt3's branch-2 entries [256, lt_hi) (entry i at off_lt + 8 i), then, 16 B
-// aligned, logx_mid's table and band mode's BandLds.  The window is band mode's, the walk path's or none
-// (split launches and points); P.stride, P.lt_hi and P.lx_on are set before
-enum LdsWindow { WIN_NONE, WIN_WALK, WIN_BAND };
+// thresholds, the null rows, logt3's branch-2 entries [256, lt_hi) (entry i at off_lt + 8 i).  The window
+// is the walk path's or none (split launches and points); P.stride and P.lt_hi are set before
+enum LdsWindow { WIN_NONE, WIN_WALK };
 static int lds_lt_end(const Params& P) { return P.off_lt + 256 * 8 + (P.lt_hi ? (P.lt_hi - 256) * 8 : 0); }
 static void lds_layout(const fsclg_ctx* c, Params& P, LdsWindow w) {
-  P.ivc0 = w == WIN_BAND ? c->c_ivc0_b : (w == WIN_WALK ? c->c_ivc0 : 0);
-  P.n_civ = w == WIN_BAND ? c->c_civ_b : (w == WIN_WALK ? c->c_civ : 0);
+  P.ivc0 = w == WIN_WALK ? c->c_ivc0 : 0;
+  P.n_civ = w == WIN_WALK ? c->c_civ : 0;
   P.civ_max = std::max(P.n_civ - 1, 0);
   P.n_cache = P.n_civ * P.stride;
   P.off_thr = P.n_cache * 32; P.off_nul = P.off_thr + (c->n_iv + 1) * 8;
   P.off_lt = P.off_nul + (c->n_rows + 1) * 8 - 256 * 8;
-  P.off_lx = (lds_lt_end(P) + 15) & ~15;
-  P.off_bd = ((P.lx_on ? P.off_lx + LX_BYTES : lds_lt_end(P)) + 15) & ~15;
 }
 // the bytes of that layout a launch asks for
-static int lds_dyn_bytes(const Params& P) {
-  if (P.band_th >= 0 && P.n_civ > 0 && P.split <= 1) return P.off_bd + BAND_LDS_BYTES;
-  return P.lx_on ? P.off_lx + LX_BYTES : lds_lt_end(P);
-}
+static int lds_dyn_bytes(const Params& P) { return lds_lt_end(P); }
 
 extern "C++" {
 // a kernel's hipFuncAttributeMaxDynamicSharedMemorySize, set once per device (bit = device id; a
@@ -5358,27 +4499,13 @@ static Params make_params(fsclg_ctx* c, Batch& B, int slot, int n, int mode, int
   P.inv_step = 1.0 / c->step; P.iv_off = -LOG_AD_MIN * P.inv_step - 1e-9;
   // dynamic LDS: the planned coefficient window, thresholds and null rows
   if (c->plan_dirty) plan_cache(c);
-  {
-    // band mode (an alternative term order, off by default: HISTORY §R6.1, §R6.3): FSCLG_BAND_TH >= 0
-    // turns it on; read per launch, as FSCLG_BAND_NB / FSCLG_BAND_MINP (tests switch them within one
-    // process).  Band mode's BandLds sits in the dynamic LDS after the logt copy, so its window is c_civ_b
-    const int band_env = getenv("FSCLG_BAND_TH") ? atoi(getenv("FSCLG_BAND_TH")) : -2;
-    const int band_th = band_env != -2 ? band_env : band_default(c);
-    P.band_th = (c->d_dband && c->d_tpos && c->c_civ_b > 0) ? band_th : -1;
-    const int band_nb = getenv("FSCLG_BAND_NB") ? atoi(getenv("FSCLG_BAND_NB")) : NBMAX;
-    P.band_nb = band_nb;
-    const int band_minp = getenv("FSCLG_BAND_MINP") ? atoi(getenv("FSCLG_BAND_MINP")) : 8;
-    P.band_minp = band_minp;
-  }
   P.lt_hi = c->lt_hi;
   P.lt_span = c->lt_hi > 256 ? ((uint32_t)c->lt_hi << 16) - 0x1000000u : 0u;  // lt_hi <= 32768
-  P.lx = c->d_lx; P.lx_on = FSCLG_LOG_CALC >= 2 ? c->lx_on : 0;  // FSCLG_LOG_CALC=1: set for split launches
-  lds_layout(c, P, P.band_th >= 0 ? WIN_BAND : WIN_WALK);
+  lds_layout(c, P, WIN_WALK);
   P.chr_start = c->d_chr_start; P.chr_n = c->d_chr_n; P.chr_null = S.d_chr_null; P.win_null = S.d_win_null;
   P.la_coarse = c->d_la_coarse; P.la_refine = c->d_la_refine; P.n_refine = c->d_n_refine;
   P.dfail = c->d_dfail;
-  P.dband = c->d_dband; P.nd = c->n_iv + 1; P.tpos = c->d_tpos;
-  P.cells = B.p_cells; P.out = B.p_out; P.stats = c->d_stats; P.ctrace = nullptr; P.ivhist = nullptr;
+  P.cells = B.p_cells; P.out = B.p_out; P.stats = c->d_stats; P.ctrace = nullptr;
   P.epos = nullptr; P.n_ep = 0; P.ept = nullptr; P.cell_ep = nullptr;
   P.split = 1; P.xacc = nullptr; P.xcnt = nullptr;
   {
@@ -5439,10 +4566,8 @@ static int launch_blocks_impl(hipStream_t stream, const Params& P, int n) {
     int dev = 0, r;
     HIPCHK(hipGetDevice(&dev), "hipGetDevice");
     if ((r = allow_dyn_lds<&search_maxpos_kernel<true>>(dev, LDS_WG - STAT_M))) return r;
-    if ((r = allow_dyn_lds<&search_maxpos_kernel<true, true>>(dev, LDS_WG - STAT_M))) return r;
     if ((r = allow_dyn_lds<&search_maxpos_split_kernel<true>>(dev, LDS_WG - stat_s))) return r;
     if (P.split > 1) hipLaunchKernelGGL((search_maxpos_split_kernel<true>), dim3(grid), dim3(WG), dyn, stream, P);
-    else if (P.band_th >= 0 && P.n_civ > 0) hipLaunchKernelGGL((search_maxpos_kernel<true, true>), dim3(grid), dim3(WG), dyn, stream, P);
     else hipLaunchKernelGGL((search_maxpos_kernel<true>), dim3(grid), dim3(WG), dyn, stream, P);
   } else
     if (P.split > 1) hipLaunchKernelGGL((search_maxpos_split_kernel<false>), dim3(grid), dim3(WG), 0, stream, P);
@@ -5457,7 +4582,7 @@ static int launch_blocks_impl(hipStream_t stream, const Params& P, int n) {
 
 // a submit's first touch of the batch: nothing of an earlier call is left, the kind's time starts at zero
 static void batch_reset(Batch& B, BatchKind k, int slot, int eval_range = 0, int bp_resl = 0) {
-  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.ivhist = nullptr; B.traced = false;
+  B.n_cells = 0; B.nu = 0; B.nlaunch = 0; B.slot = slot; B.traced = false;
   B.eval_range = eval_range; B.bp_resl = bp_resl; B.n_res = 0; B.st_synced = false; B.ms[k] = 0.0;
 }
 
@@ -5737,14 +4862,6 @@ static int search_submit_impl(fsclg_ctx* c, int batch, int slot, const fsclg_cel
   // the slot's rows and null sums first
   HIPCHK(hipStreamWaitEvent(B.stream, c->slot[slot].ready, 0), "hipStreamWaitEvent");
   Params P = make_params(c, B, slot, nl, 0, eval_range, bp_resl);
-  if (c->hist_pending && P.n_civ > 0) {  // diagnostic builds (FSCLG_IVHIST): per phase key
-    const int nh = (c->n_coarse + 2) * c->n_iv;
-    if ((r = c->d_ivhist.ensure(nh))) return r;
-    HIPCHK(hipMemsetAsync(c->d_ivhist, 0, sizeof(unsigned long long) * nh, B.stream), "hipMemset ivhist");
-    P.ivhist = c->d_ivhist;
-    B.ivhist = c->d_ivhist;
-    c->hist_pending = false;
-  }
   // the events bracket the kernel launches only (one or two of search_maxpos_kernel)
   HIPCHK(hipEventRecord(B.ev0, B.stream), "hipEventRecord");
   if (use_ep) {
@@ -5759,7 +4876,6 @@ static int search_submit_impl(fsclg_ctx* c, int batch, int slot, const fsclg_cel
     P.spec_refine = spec_refine_on();
     // latency: no LDS coefficient windows (their loads, repeated by every member for every
     // phase, cost more than the global gathers of a lightly loaded device)
-    P.lx_on = FSCLG_LOG_CALC >= 1 ? c->lx_on : 0;
     lds_layout(c, P, WIN_NONE);
   }
   if ((r = launch_blocks(B.stream, P, G > 1 ? (nl + 7) / 8 * 8 * G : nl))) return r;
@@ -5792,15 +4908,6 @@ int fsclg_search_wait(fsclg_ctx* c, int batch, fsclg_point_t* out) {
   HIPCHK(hipEventSynchronize(B.ev2), "hipEventSynchronize");
   int r;
   if ((r = batch_time(c, B, B.nlaunch, BK_SEARCH))) return r;
-  if (B.ivhist) {  // re-plan the LDS window from the measured histogram
-    const int nkey = c->n_coarse + 2;
-    std::vector<unsigned long long> hk((size_t)nkey * c->n_iv), h(c->n_iv, 0);
-    HIPCHK(hipMemcpy(hk.data(), B.ivhist, sizeof(unsigned long long) * hk.size(), hipMemcpyDeviceToHost), "copy ivhist");
-    for (int k = 0; k < nkey; k++)
-      for (int j = 0; j < c->n_iv; j++) h[j] += hk[(size_t)k * c->n_iv + j];
-    choose_window(c, std::vector<double>(h.begin(), h.end()));
-    B.ivhist = nullptr;
-  }
   if (B.traced) {  // development aid: append [n, then n x (start, end, cu, terms, 4 phase times)] to the file
     std::vector<unsigned long long> h((size_t)8 * nu);
     memcpy(h.data(), B.p_ctrace, sizeof(unsigned long long) * h.size());
@@ -5968,7 +5075,7 @@ static int cover_windows(fsclg_ctx* c, Batch& B, int slot, const std::vector<fsc
 // One launch of a run-chunk kernel (profile_body's wrappers) on the batch's stream, for the slot's rows:
 // the runs' window null sums (one covering cell per run), their chunks of CH positions in p_cmchunks
 // (out0: the chunk's first position among all, or by_chunk: its index), then the kernel between ev0 and
-// ev1, on the walk-window path (band mode has its own kernel) with the tables in LDS where they fit
+// ev1, with the tables in LDS where they fit
 enum RunKernel { RUN_PROFILE, RUN_CELLMAX, RUN_CURVE };
 extern "C++" {
 template <bool LDS>
@@ -6003,8 +5110,6 @@ static int launch_runs(fsclg_ctx* c, Batch& B, const fsclg_run_t* runs, int n_ru
   });
   static const char* const what[] = {"launch profile_kernel", "launch cellmax_kernel", "launch curve_kernel"};
   return launch_bracket(c, B, nc, what[k], [&](Params& P) {
-    P.band_th = -1;
-    lds_layout(c, P, WIN_WALK);
     P.ctrace = nullptr;
     const int dyn = lds_dyn_bytes(P);
     // (tables too large for the LDS copies: every coefficient from the global table, as the cell path)
@@ -6973,8 +6078,7 @@ int fsclg_get_stats(fsclg_ctx* c, fsclg_stats_t* st) {
     st->busy_ms = busy;
   }
   if (c->plan_dirty) plan_cache(c);
-  if (band_default(c) >= 0) { st->cache_iv0 = c->c_ivc0_b; st->cache_n_iv = c->c_civ_b; st->cache_cover = c->c_cover_b; }
-  else { st->cache_iv0 = c->c_ivc0; st->cache_n_iv = c->c_civ; st->cache_cover = c->c_cover; }
+  st->cache_iv0 = c->c_ivc0; st->cache_n_iv = c->c_civ; st->cache_cover = c->c_cover;
   st->cache_n_rows = c->c_crow;
   return FSCLG_OK;
 }

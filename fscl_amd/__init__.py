@@ -163,6 +163,7 @@ class PointT(C.Structure):  # fsclg_point_t
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_void_p)
+TOP_ACCEPT_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ScanPtT))
 
 # exported symbols of include/fscl_amd.h and include/fsclg.h (checked by tests)
 EXPORTS = [
@@ -201,7 +202,7 @@ EXPORTS = [
     "fscl_amd_tail_chunk", "fscl_amd_tail_pack", "fscl_amd_tail_log10p", "fscl_amd_tail_summary", "fscl_amd_tail_output",
     "fsclg_surface_submit", "fsclg_surface_wait", "fsclg_surface_last_ms",
     "fscl_amd_surface_alphas", "fscl_amd_surface_run", "fscl_amd_scan_surface", "fscl_amd_scan_point_surfaces",
-    "fscl_amd_surfaces_free", "fscl_amd_surface_region", "fscl_amd_surface_output", "fscl_amd_surface_runs",
+    "fscl_amd_top_points", "fscl_amd_surfaces_free", "fscl_amd_surface_region", "fscl_amd_surface_output", "fscl_amd_surface_runs",
     "fscl_amd_surface_last_ms",
     "fsclg_blocks_submit", "fsclg_blocks_wait", "fsclg_blocks_last_ms",
     "fscl_amd_scan_blocks", "fscl_amd_scan_point_jackknife", "fscl_amd_blocks_free", "fscl_amd_blocks_cap",
@@ -317,6 +318,7 @@ def _load() -> C.CDLL:
         "fscl_amd_tail_output": (C.c_int, [C.c_char_p, P(ScanT), P(TailT), C.c_char_p]),
         "fscl_amd_surface_alphas": (C.c_int, [C.c_double, C.c_double, C.c_int, C.c_double, C.c_void_p]),
         "fscl_amd_surface_run": (C.c_int, [P(ScanT), C.c_void_p, P(RunT)]),
+        "fscl_amd_top_points": (C.c_int, [P(ScanT), C.c_int, C.c_int, TOP_ACCEPT_FN, C.c_void_p]),
         "fscl_amd_scan_surface": (C.c_int, [P(ScanT), P(SmPtableT), C.c_int, C.c_void_p, C.c_int, P(SurfacesT)]),
         "fscl_amd_scan_point_surfaces": (C.c_int, [P(ScanT), P(SmPtableT), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                                    C.c_double, C.c_int, P(SurfacesT)]),
@@ -1070,6 +1072,18 @@ def scan_point_surfaces(scan, tables, top: int = 3, halfwidth: int = 100000, ste
                                                         float(alphas[0]), float(alphas[1]), int(alphas[2]), C.byref(res)),
                  "fscl_amd_scan_point_surfaces")
     return _surfaces_take(res)
+
+
+def top_points(scan, top: int, spacing: int, accept=None) -> np.ndarray:
+    """The indices of at most ``top`` scan points by descending CLR (ties in scan order, a NaN never), none
+    within ``spacing`` bp of one already chosen on its chromosome; ``accept(ScanPtT) -> bool`` rejects points
+    without blocking their neighbours.  Host only."""
+    idx = np.zeros(max(int(top), 1), dtype=np.int32)
+    fn = TOP_ACCEPT_FN(lambda p: int(bool(accept(p.contents)))) if accept else TOP_ACCEPT_FN()
+    n = get_lib().fscl_amd_top_points(scan, int(top), int(spacing), fn, idx.ctypes.data)
+    if n < 0:
+        raise ValueError("fscl_amd_top_points: no scan")
+    return idx[:n].copy()
 
 
 def surface_runs(scan, tables, runs, alphas, eval_range: int = 81920, rows=None, batch: int = 0, pts=None, sm=None):

@@ -1,6 +1,6 @@
 /* conditional.c -- the host-only side of the conditional sweep scan (--conditional-file): the
    sites a candidate sweep owns, the given sweeps' terms per site, the base fold, the size limit
-   and the writer.  No device call is made here (fscl_amd_scan_conditional, scan.c, evaluates);
+   and the writer.  No device call is made here (fscl_amd_scan_conditional, analyses.c, evaluates);
    tools/conditional_host_check.c builds this file alone under the sanitizers. */
 #include <errno.h>
 #include <math.h>

@@ -1,6 +1,6 @@
 /* expect.c -- the host-only side of the expected terms under the model (--expect-file): the tables
    the sampler's lack (folded rows, null values per class), the refusals, the size limit and the
-   writer.  No device call is made here (fscl_amd_scan_expect, scan.c, evaluates);
+   writer.  No device call is made here (fscl_amd_scan_expect, analyses.c, evaluates);
    tools/expect_host_check.c builds this file alone under the sanitizers. */
 #include <errno.h>
 #include <math.h>

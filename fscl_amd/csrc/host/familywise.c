@@ -1,7 +1,7 @@
 /* familywise.c -- the host-only side of the family-wise adjusted p-values (--familywise-file,
  * include/fscl_amd.h): the rank order of the observed CLRs, the chunk of trials under a byte cap,
  * the combine of the exceedance counts into p-values, the thresholds and the two writers.  Nothing
- * here touches the device; fscl_amd_familywise and fscl_amd_familywise_runs are in scan.c;
+ * here touches the device; fscl_amd_familywise and fscl_amd_familywise_runs are in trials.c;
  * tools/familywise_host_check.c builds this file alone under the sanitizers. */
 #include <errno.h>
 #include <math.h>

@@ -66,29 +66,23 @@ static fscl_amd_sweep_t *parse_sweeps(const scan_t *s, const strlist_t *l, const
 
 /* the --bootstrap-top scan points: descending CLR (ties in scan order, a NaN never), at their fitted
    sweep_pos and alpha, skipping a point within window_bp of one already chosen on its chromosome */
+static int sampler_takes_alpha(const scan_pt_t *p) { /* (positive and finite: else the sampler refuses) */
+  const double alpha = exp(p->lalpha);
+  return alpha > 0.0 && !(alpha > 1.7976931348623157e308);
+}
+
 static fscl_amd_sweep_t *top_sweeps(const scan_t *s, int top, int window_bp, int *n_out) {
   fscl_amd_sweep_t *sw = malloc(sizeof *sw * (size_t)(top > 0 ? top : 1));
-  char *used = calloc((size_t)(s->n_scan_pts > 0 ? s->n_scan_pts : 1), 1);
-  int n = 0, i, k;
-  if (!sw || !used) logmsg(MSG_FATAL, "fscl: out of memory (sweeps)");
-  while (n < top) {
-    int best = -1;
-    for (i = 0; i < s->n_scan_pts; i++)
-      if (!used[i] && s->scan_pts[i].clr == s->scan_pts[i].clr && (best < 0 || s->scan_pts[i].clr > s->scan_pts[best].clr))
-        best = i;
-    if (best < 0) break;
-    used[best] = 1;
-    for (k = 0; k < n; k++) {
-      long long d = (long long)s->scan_pts[best].sweep_pos - sw[k].pos;
-      if (sw[k].chr == s->scan_pts[best].chr && (d < 0 ? -d : d) <= window_bp) break;
-    }
-    if (k < n) continue;
-    sw[n].chr = s->scan_pts[best].chr; sw[n].pos = s->scan_pts[best].sweep_pos; sw[n].alpha = exp(s->scan_pts[best].lalpha);
-    if (!(sw[n].alpha > 0.0) || sw[n].alpha > 1.7976931348623157e308) continue; /* (an alpha the sampler refuses) */
-    n++;
+  int *point = malloc(sizeof *point * (size_t)(top > 0 ? top : 1));
+  int n, k;
+  if (!sw || !point) logmsg(MSG_FATAL, "fscl: out of memory (sweeps)");
+  n = fscl_amd_top_points(s, top, window_bp, sampler_takes_alpha, point);
+  for (k = 0; k < n; k++) {
+    const scan_pt_t *p = s->scan_pts + point[k];
+    sw[k].chr = p->chr; sw[k].pos = p->sweep_pos; sw[k].alpha = exp(p->lalpha);
   }
-  free(used);
-  *n_out = n;
+  free(point);
+  *n_out = n > 0 ? n : 0;
   return sw;
 }
 

@@ -1,7 +1,7 @@
 /* jackknife.c -- the host-only side of the delete-one-block jackknife of sweep peaks
    (--jackknife-file): the blocks a request needs, the size limits, the combination of the block
    sums into delete-one estimates and the writer.  No device call is made here
-   (fscl_amd_scan_blocks, scan.c, evaluates); tools/jackknife_host_check.c builds this file alone
+   (fscl_amd_scan_blocks, analyses.c, evaluates); tools/jackknife_host_check.c builds this file alone
    under the sanitizers. */
 #include <errno.h>
 #include <math.h>

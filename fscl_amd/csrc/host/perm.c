@@ -217,7 +217,7 @@ void fh_plan_apply_u32(uint32_t *rows, int n, const fsclg_swap_t *ent, const int
 /* one trial's result (clr, lalpha; its cell starts at start_pos) applied to its scan point:
    scan-chromosome.c:488-502, the product's only copy.  The prune draw (31 bits, as rand()) is asked
    of the caller only when this hit takes permute_p to >= 20, so at most once: the stream, the
-   counter-based draw and the pipeline's order guard stay with the drivers (scan.c).  At most `save`
+   counter-based draw and the pipeline's order guard stay with the drivers (trials.c).  At most `save`
    null CLRs are kept */
 void fh_trial_apply(scan_pt_t *p, double clr, double lalpha, int start_pos, int save, fh_draw_fn draw, void *ctx) {
   if (clr >= p->clr) {

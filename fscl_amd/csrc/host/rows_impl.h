@@ -1,11 +1,31 @@
-/* The row-array routines of the permutation trials, for one staging width: included by scan.c
-   once per width with ROW_T (uint8_t, uint16_t or uint32_t) and ROW_SFX defined.  The trials'
+/* The row-array routines of the permutation trials, for each staging width: included once by
+   scan.c for the whole-chromosome null sums and once by trials.c (ROW_TRIALS defined) for the
+   rest; the file then includes itself per width with ROW_T (uint8_t, uint16_t or uint32_t) and
+   ROW_SFX defined, which gives chr_null_sums_8, chr_null_sums_16, ... .  The trials'
    rows are staged at the narrowest width that holds the device table's rows (D.rb bytes), so
    that a candidate permutation moves fewer bytes on the host and every device's upload reads
    fewer over PCIe; the values, and so every result, are the same at any width. */
+#ifndef ROW_T
+#define ROW_T uint8_t
+#define ROW_SFX 8
+#include "rows_impl.h"
+#undef ROW_T
+#undef ROW_SFX
+#define ROW_T uint16_t
+#define ROW_SFX 16
+#include "rows_impl.h"
+#undef ROW_T
+#undef ROW_SFX
+#define ROW_T uint32_t
+#define ROW_SFX 32
+#include "rows_impl.h"
+#undef ROW_T
+#undef ROW_SFX
+#else
 #define ROW_CAT2(a, b) a##_##b
 #define ROW_CAT(a, b) ROW_CAT2(a, b)
 
+#ifndef ROW_TRIALS
 /* init_scan_result's window sum (scan-chromosome.c:92-94): sequential from 0.0 over the
    whole chromosome for the given rows, for the chromosomes whose window is the whole
    chromosome (D.chr_list; the others' entries are never read and are set to 0) */
@@ -13,7 +33,7 @@ static void ROW_CAT(chr_null_sums, ROW_SFX)(const ROW_T *row, double *out) {
   const int nl = D.chr_list ? D.n_chr_list : D.n_chr;
   int q, i;
   if (D.chr_list) for (q = 0; q < D.n_chr; q++) out[q] = 0.;
-#pragma omp parallel for schedule(dynamic, 1) private(i) if (nl > 1) num_threads(null_threads())
+#pragma omp parallel for schedule(dynamic, 1) private(i) if (nl > 1) num_threads(fh_null_threads())
   for (q = 0; q < nl; q++) {
     const int c = D.chr_list ? D.chr_list[q] : q;
     double acc = 0.;
@@ -22,6 +42,7 @@ static void ROW_CAT(chr_null_sums, ROW_SFX)(const ROW_T *row, double *out) {
   }
 }
 
+#else
 /* scan-chromosome.c:336-389 on the row array: blocks of consecutive sites (length ~ 1 +
    Exp(nbp), extended to at least scan_width_mb on the same chromosome; fh_block_draw, shared
    with the device plan of perm.c) are swapped into place; positions never move.  Q9: a block
@@ -101,6 +122,8 @@ static int ROW_CAT(chr_null_sums_1t, ROW_SFX)(const ROW_T *row, double *out, con
   }
   return 0;
 }
+#endif
 
 #undef ROW_CAT
 #undef ROW_CAT2
+#endif

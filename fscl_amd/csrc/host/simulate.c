@@ -1,7 +1,7 @@
 /* simulate.c -- the host-only side of the sweep-model simulation and the parametric bootstrap
  * (include/fscl_amd.h): sweep parsing, the nearest-sweep rule, the sampler's table layout, the
  * replicate scan_t, the SNP-format writer and the bootstrap's quantile summary.  Nothing here
- * touches the device; fscl_amd_simulate and fscl_amd_bootstrap are in scan.c. */
+ * touches the device; fscl_amd_simulate and fscl_amd_bootstrap are in analyses.c. */
 #include <errno.h>
 #include <math.h>
 #include <stdio.h>

@@ -1,6 +1,6 @@
 /* surface.c -- the host-only side of the position-by-alpha likelihood surfaces (--surface-file):
    the alpha list of a request, its positions, the region summary and the writer.  No device call
-   is made here (fscl_amd_scan_surface, scan.c, evaluates); tools/surface_host_check.c builds this
+   is made here (fscl_amd_scan_surface, analyses.c, evaluates); tools/surface_host_check.c builds this
    file alone under the sanitizers. */
 #include <errno.h>
 #include <math.h>
@@ -46,6 +46,31 @@ int fscl_amd_surface_run(const scan_t *s, const fscl_amd_surface_req_t *q, fsclg
   run->count = k1 >= k0 ? (int)(k1 - k0 + 1) : 0;
   run->start_pos = run->count ? (int)(q->centre_pos + k0 * q->step) : q->centre_pos;
   return 0;
+}
+
+/* the peak selection of --surface-top, --jackknife-top, --expect-top and --bootstrap-top */
+int fscl_amd_top_points(const scan_t *s, int top, int spacing, int (*accept)(const scan_pt_t *), int *idx_out) {
+  char *used;
+  int n = 0, i, k;
+  if (!s || (!s->scan_pts && s->n_scan_pts > 0) || (top > 0 && !idx_out)) return -1;
+  used = fh_calloc(s->n_scan_pts > 0 ? s->n_scan_pts : 1, 1, "top points");
+  while (n < top) {
+    int best = -1;
+    for (i = 0; i < s->n_scan_pts; i++)
+      if (!used[i] && s->scan_pts[i].clr == s->scan_pts[i].clr && (best < 0 || s->scan_pts[i].clr > s->scan_pts[best].clr))
+        best = i;
+    if (best < 0) break;
+    used[best] = 1;
+    for (k = 0; k < n; k++) {
+      long long d = (long long)s->scan_pts[best].sweep_pos - s->scan_pts[idx_out[k]].sweep_pos;
+      if (s->scan_pts[idx_out[k]].chr == s->scan_pts[best].chr && (d < 0 ? -d : d) <= spacing) break;
+    }
+    if (k < n) continue;
+    if (accept && !accept(s->scan_pts + best)) continue;
+    idx_out[n++] = best;
+  }
+  free(used);
+  return n;
 }
 
 void fscl_amd_surfaces_free(fscl_amd_surfaces_t *r) {

@@ -1,7 +1,7 @@
 /* tail.c -- the host-only side of the projected p-values (include/fscl_amd.h): the used prefix of
  * every point's null record, the chunks of a launch, the packing of one chunk, the summary with its
  * calibration figure and the --tail-file writer.  Nothing here touches the device;
- * fscl_amd_tail_fit and fscl_amd_tail_runs are in scan.c. */
+ * fscl_amd_tail_fit and fscl_amd_tail_runs are in analyses.c. */
 #include <errno.h>
 #include <math.h>
 #include <stdio.h>

@@ -405,10 +405,15 @@ unsigned long long fscl_amd_curve_forced(void);
    contiguous shares of the requests balanced by window size x cells (identical results); with
    several ranks, rank 0 alone evaluates (the others return FSCLG_OK and an empty result).  Returns
    a fsclg status code (FSCLG_E_ARG: a NULL argument, n < 0, a request fscl_amd_surface_run or the
-   device refuses).  fscl_amd_scan_point_surfaces: the `top` scan points of greatest CLR (ties in
-   scan order, a NaN never; a point within halfwidth bp of one already chosen on its chromosome is
-   skipped, as --bootstrap-top does), in that order, each centred on its sweep_pos with
-   fscl_amd_surface_alphas(la_lo, la_hi, n_grid, its fitted lalpha).
+   device refuses).  fscl_amd_scan_point_surfaces: the `top` scan points of greatest CLR
+   (fscl_amd_top_points with spacing = halfwidth and no predicate), in that order, each centred on
+   its sweep_pos with fscl_amd_surface_alphas(la_lo, la_hi, n_grid, its fitted lalpha).
+
+   fscl_amd_top_points (host only): the one peak selection of the --*-top options.  The indices of
+   at most `top` scan points into idx_out[top], by descending CLR (ties in scan order, a NaN
+   never); a point within `spacing` bp of one already chosen on its chromosome is skipped; a point
+   `accept` (NULL: none) rejects is skipped too and does not block its neighbours.  Returns their
+   number; -1 for a NULL scan, or a NULL idx_out with top > 0.
 
    fscl_amd_surface_region (host only), on sm[n_pos][n_la] and the positions' null sums: V = sm -
    null_logl per cell; M its maximum, the first in position order, then alpha order (max_ipos,
@@ -458,6 +463,7 @@ typedef struct {
 } fscl_amd_surface_region_t;
 int fscl_amd_surface_alphas(double lo, double hi, int n, double fitted, double *out /* [64] */);
 int fscl_amd_surface_run(const scan_t *scan_obj, const fscl_amd_surface_req_t *req, fsclg_run_t *run);
+int fscl_amd_top_points(const scan_t *scan_obj, int top, int spacing, int (*accept)(const scan_pt_t *), int *idx_out);
 int fscl_amd_scan_surface(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, const fscl_amd_surface_req_t *req, int n,
                           fscl_amd_surfaces_t *out);
 int fscl_amd_scan_point_surfaces(scan_t *scan_obj, sm_ptable_t *sm_p, int eval_range, int top, int halfwidth, int step,

@@ -1086,6 +1086,13 @@ def top_points(scan, top: int, spacing: int, accept=None) -> np.ndarray:
     return idx[:n].copy()
 
 
+def _sampler_takes_alpha(p) -> bool:
+    """The ``accept`` rule of the bootstrap's peak selection (the CLI's sampler_takes_alpha): the point's
+    alpha = exp(lalpha) is positive and finite, else the sampler refuses it."""
+    with np.errstate(over="ignore"):
+        return bool(0.0 < float(np.exp(p.lalpha)) < np.inf)
+
+
 def surface_runs(scan, tables, runs, alphas, eval_range: int = 81920, rows=None, batch: int = 0, pts=None, sm=None):
     """fsclg_surface_submit / fsclg_surface_wait on the scan's first device (the shim-level handle, next to
     curve_runs): ``alphas`` holds one ascending list per run, all of one length.  Returns (points
@@ -1875,6 +1882,18 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         raise ValueError("scan_mode grid runs on the parity stream only")
     if int(sites_top) < 0:
         raise ValueError("sites_top must be >= 0")
+    if expect_file is None and (expect_sweeps or expect_alphas is not None or expect_top != 3 or expect_bins != 24):
+        raise ValueError("expect_sweeps, expect_top, expect_alphas and expect_bins need expect_file")
+    # the defaults that follow other options (the CLI's check pass): the -G and -g spacings, then the surface's values
+    bootstrap_window = int(large_grid_sp if bootstrap_window is None else bootstrap_window)
+    surface_halfwidth = int(large_grid_sp if surface_halfwidth is None else surface_halfwidth)
+    surface_step = int(small_grid_sp if surface_step is None else surface_step)
+    jackknife_halfwidth = surface_halfwidth if jackknife_halfwidth is None else int(jackknife_halfwidth)
+    jackknife_step = surface_step if jackknife_step is None else int(jackknife_step)
+    jackknife_block = max(int(large_grid_sp) // 2, 1) if jackknife_block is None else int(jackknife_block)
+    conditional_step = int(small_grid_sp if conditional_step is None else conditional_step)
+    jackknife_alphas, conditional_alphas, expect_alphas = (surface_alphas if a is None else a
+                                                           for a in (jackknife_alphas, conditional_alphas, expect_alphas))
     if bootstrap_file is not None and scan_mode == "grid":
         raise ValueError("the bootstrap rescans by bisection (not with scan_mode grid)")
     if bootstrap_file is not None and (int(bootstrap_reps) < 0 or int(bootstrap_top) < 0):
@@ -1882,35 +1901,24 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
     if surface_file is not None:
         if int(surface_top) < 0 or not float(surface_drop) >= 0.0:
             raise ValueError("surface_top and surface_drop must be >= 0")
-        if int(small_grid_sp if surface_step is None else surface_step) < 1:
+        if surface_step < 1:
             raise ValueError("surface_step must be at least 1")
-        if int(large_grid_sp if surface_halfwidth is None else surface_halfwidth) < 0:
+        if surface_halfwidth < 0:
             raise ValueError("surface_halfwidth must be >= 0")
         _surface_grid(*surface_alphas)  # (raises ValueError)
     if jackknife_file is not None:
-        # the jackknife's grid defaults to the surface's, given or default
-        jackknife_halfwidth = int((large_grid_sp if surface_halfwidth is None else surface_halfwidth)
-                                  if jackknife_halfwidth is None else jackknife_halfwidth)
-        jackknife_step = int((small_grid_sp if surface_step is None else surface_step) if jackknife_step is None else jackknife_step)
-        jackknife_block = int(max(int(large_grid_sp) // 2, 1) if jackknife_block is None else jackknife_block)
-        jackknife_alphas = surface_alphas if jackknife_alphas is None else jackknife_alphas
         if int(jackknife_top) < 0 or jackknife_halfwidth < 0:
             raise ValueError("jackknife_top and jackknife_halfwidth must be >= 0")
         if jackknife_step < 1 or jackknife_block < 1:
             raise ValueError("jackknife_step and jackknife_block must be at least 1")
         _surface_grid(*jackknife_alphas)  # (raises ValueError)
     if conditional_file is not None:
-        conditional_step = int(small_grid_sp if conditional_step is None else conditional_step)
-        conditional_alphas = surface_alphas if conditional_alphas is None else conditional_alphas
         if conditional_step < 1:
             raise ValueError("conditional_step must be at least 1")
         if int(conditional_halfwidth) < 0 or not 1 <= int(conditional_rounds) <= COND_MAX_ROUNDS:
             raise ValueError("conditional_halfwidth must be >= 0 and conditional_rounds 1 .. 8")
         _surface_grid(*conditional_alphas)  # (raises ValueError)
-    if expect_file is None and (expect_sweeps or expect_alphas is not None or expect_top != 3 or expect_bins != 24):
-        raise ValueError("expect_sweeps, expect_top, expect_alphas and expect_bins need expect_file")
     if expect_file is not None:
-        expect_alphas = surface_alphas if expect_alphas is None else expect_alphas
         if int(expect_top) < 0 or not 1 <= int(expect_bins) <= 64:
             raise ValueError("expect_top must be >= 0 and expect_bins 1 .. 64")
         _surface_grid(*expect_alphas)  # (raises ValueError)
@@ -1959,9 +1967,8 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         sites_output(sites_file, scan, *scan_point_sites(scan, tab, sites_top, eval_range), label)
     if surface_file is not None:  # the CLI's --surface-file: the surfaces around the points of greatest CLR
         surface_output(surface_file, scan,
-                       scan_point_surfaces(scan, tab, surface_top, int(large_grid_sp if surface_halfwidth is None else surface_halfwidth),
-                                           int(small_grid_sp if surface_step is None else surface_step), surface_alphas,
-                                           eval_range), surface_drop, label)
+                       scan_point_surfaces(scan, tab, surface_top, surface_halfwidth, surface_step, surface_alphas, eval_range),
+                       surface_drop, label)
     if jackknife_file is not None:  # the CLI's --jackknife-file: the delete-one-block jackknife of the same points
         jackknife_output(jackknife_file, scan,
                          scan_point_jackknife(scan, tab, jackknife_top, jackknife_halfwidth, jackknife_step, jackknife_alphas,
@@ -1970,10 +1977,7 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         given = [as_sweep(w) for w in given_sweeps]
         if not given:  # the scan point of greatest CLR (the first on a tie, never a NaN) at its fitted alpha
             p = points(scan)
-            ok = [i for i in range(len(p)) if p["clr"][i] == p["clr"][i]]
-            if ok:
-                i = max(ok, key=lambda i: (p["clr"][i], -i))
-                given = [(int(p["chr"][i]), int(p["sweep_pos"][i]), math.exp(float(p["lalpha"][i])))]
+            given = [(int(p["chr"][i]), int(p["sweep_pos"][i]), math.exp(float(p["lalpha"][i]))) for i in top_points(scan, 1, 0)]
         conditional_output(conditional_file, scan,
                            scan_conditional(scan, tab, given, conditional_halfwidth, conditional_step,
                                             _surface_grid(*conditional_alphas), conditional_rounds, conditional_min_clr,
@@ -1999,17 +2003,11 @@ def run(snp_file=None, output=None, *, ms_file=None, ms_segment_length=0, ms_fol
         if familywise_null_file is not None:
             familywise_null_output(familywise_null_file, scan, fw, label)
     if bootstrap_file is not None:  # the CLI's --bootstrap-file, last
-        win = int(large_grid_sp if bootstrap_window is None else bootstrap_window)
         if not boot_sw:  # the scan points of greatest CLR, none within the window of one already chosen
             p = points(scan)
-            for i in sorted((i for i in range(len(p)) if p["clr"][i] == p["clr"][i]), key=lambda i: -p["clr"][i]):
-                if len(boot_sw) >= int(bootstrap_top):
-                    break
-                a = float(np.exp(p["lalpha"][i]))
-                if any(c == p["chr"][i] and abs(int(p["sweep_pos"][i]) - q) <= win for c, q, _ in boot_sw) or \
-                        not (0.0 < a < np.inf):
-                    continue
-                boot_sw.append((int(p["chr"][i]), int(p["sweep_pos"][i]), a))
-        rows = bootstrap(scan, tab, fsp, boot_sw, bootstrap_reps, simulate_seed, win, eval_range, bp_resl, large_grid_sp)
+            boot_sw = [(int(p["chr"][i]), int(p["sweep_pos"][i]), float(np.exp(p["lalpha"][i])))
+                       for i in top_points(scan, bootstrap_top, bootstrap_window, accept=_sampler_takes_alpha)]
+        rows = bootstrap(scan, tab, fsp, boot_sw, bootstrap_reps, simulate_seed, bootstrap_window, eval_range, bp_resl,
+                         large_grid_sp)
         bootstrap_output(bootstrap_file, scan, boot_sw, bootstrap_reps, rows, label)
     return scan

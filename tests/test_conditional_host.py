@@ -6,8 +6,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,7 +14,7 @@ import cond_ref as cr
 import fscl_amd
 import walk_ref as wr
 from fscl_amd import synth
-from util import CLI, GOLD, ROOT
+from util import GOLD, run_cli, run_host_check
 
 NAN = float("nan")
 
@@ -222,15 +220,7 @@ def test_refusals_before_any_device_call(scan, monkeypatch):
 def test_host_check_under_sanitizers(built, tmp_path):
     """tools/conditional_host_check.c: the clip, the given terms, the base fold and the writer under ASan and UBSan, as
     a stand-alone program (no device library, nothing loaded into Python)."""
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc not found"
-    exe = tmp_path / "conditional_host_check"
-    host = ROOT / "fscl_amd" / "csrc" / "host"
-    subprocess.run([gcc, "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fopenmp", "-std=gnu11",
-                    str(ROOT / "tools" / "conditional_host_check.c"), str(host / "conditional.c"), str(host / "util.c"), "-lm",
-                    "-o", str(exe)], check=True, capture_output=True, text=True, timeout=300)
-    r = subprocess.run([str(exe), str(tmp_path)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-400:], r.stderr[-2000:])
+    run_host_check("conditional_host_check", ["conditional.c", "util.c"], tmp_path, [tmp_path])
 
 
 @pytest.mark.parametrize("args, msg", [
@@ -254,8 +244,7 @@ def test_cli_refusals(built, tmp_path, args, msg):
     """Refused before the data is loaded: no device is touched and no file is written."""
     first = (GOLD / "g1.snp").read_text().split(None, 1)[0]  # (the first chromosome's name)
     args = [a.replace("@CHR@", first) for a in args]
-    r = subprocess.run([str(CLI), "-f", str(GOLD / "g1.snp"), "-o", str(tmp_path / "o.txt"),
-                        f"--conditional-file={tmp_path / 'c.txt'}"] + args, capture_output=True, text=True, timeout=120)
+    r = run_cli([f"--conditional-file={tmp_path / 'c.txt'}"] + args, tmp_path, snp="g1.snp")
     assert r.returncode != 0 and msg in r.stderr + r.stdout, (r.returncode, r.stderr[-500:])
     assert not (tmp_path / "c.txt").exists() and not (tmp_path / "o.txt").exists()
 
@@ -263,8 +252,7 @@ def test_cli_refusals(built, tmp_path, args, msg):
 def test_cli_cap_refused_before_the_scan(built, tmp_path, monkeypatch):
     monkeypatch.setenv("FSCL_AMD_COND_CAP", "100")
     first = (GOLD / "g1.snp").read_text().split(None, 1)[0]
-    r = subprocess.run([str(CLI), "-f", str(GOLD / "g1.snp"), "-o", str(tmp_path / "o.txt"), f"--conditional-file={tmp_path / 'c.txt'}",
-                        f"--given-sweep={first}:1000:1e-3"], capture_output=True, text=True, timeout=120)
+    r = run_cli([f"--conditional-file={tmp_path / 'c.txt'}", f"--given-sweep={first}:1000:1e-3"], tmp_path, snp="g1.snp")
     assert r.returncode != 0 and "FSCL_AMD_COND_CAP" in r.stderr + r.stdout, (r.returncode, r.stderr[-500:])
     assert not (tmp_path / "c.txt").exists() and not (tmp_path / "o.txt").exists()
 
@@ -272,8 +260,7 @@ def test_cli_cap_refused_before_the_scan(built, tmp_path, monkeypatch):
 @pytest.mark.parametrize("opt", ["--given-sweep=chr1:1000:1e-3", "--conditional-step=500", "--conditional-halfwidth=0",
                                  "--conditional-rounds=1", "--conditional-min-clr=0", "--conditional-alphas=-20:4:7"])
 def test_cli_options_need_the_file(built, tmp_path, opt):
-    r = subprocess.run([str(CLI), "-f", str(GOLD / "g1.snp"), "-o", str(tmp_path / "o.txt"), opt], capture_output=True, text=True,
-                       timeout=120)
+    r = run_cli([opt], tmp_path, snp="g1.snp")
     assert r.returncode != 0 and "need --conditional-file" in r.stderr + r.stdout, (r.returncode, r.stderr[-500:])
     assert not (tmp_path / "o.txt").exists()
 

@@ -4,8 +4,6 @@ NumPy restatement the GPU tests compare with (tests/expect_ref.py): no GPU is to
 from __future__ import annotations
 
 import math
-import shutil
-import subprocess
 
 import mpmath  # noqa: F401  (test_reference_against_mpmath pins E_M1 and E_M2 with it: without it this file fails, never skips)
 import numpy as np
@@ -14,7 +12,7 @@ import pytest
 import expect_ref as er
 import fscl_amd
 import sample_ref as sr
-from util import CLI, GOLD, ROOT
+from util import GOLD, run_cli, run_host_check
 
 
 def swept_sites(name):
@@ -151,15 +149,7 @@ def test_refusals_before_any_device_work(built, monkeypatch):
 def test_host_check_under_sanitizers(built, tmp_path):
     """tools/expect_host_check.c: the table building, the bins, the refusals and the writer under ASan and UBSan, as
     a stand-alone program (no device library, nothing loaded into Python)."""
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc not found"
-    exe = tmp_path / "expect_host_check"
-    host = ROOT / "fscl_amd" / "csrc" / "host"
-    subprocess.run([gcc, "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fopenmp", "-std=gnu11",
-                    str(ROOT / "tools" / "expect_host_check.c"), str(host / "expect.c"), str(host / "util.c"), "-lm", "-o",
-                    str(exe)], check=True, capture_output=True, text=True, timeout=300)
-    r = subprocess.run([str(exe), str(tmp_path)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-400:], r.stderr[-2000:])
+    run_host_check("expect_host_check", ["expect.c", "util.c"], tmp_path, [tmp_path])
 
 
 # ------------------------------------------------------------------ the CLI's refusals
@@ -188,8 +178,7 @@ def test_host_check_under_sanitizers(built, tmp_path):
 def test_cli_refusals(built, tmp_path, args, msg):
     """Refused before any device work (this test runs without a device): no file is written."""
     args = [a.replace("=E", f"={tmp_path / 'e.txt'}") if a.startswith("--expect-file") else a for a in args]
-    r = subprocess.run([str(CLI), "-f", str(GOLD / "g1.snp"), "-o", str(tmp_path / "o.txt")] + args, capture_output=True,
-                       text=True, timeout=120)
+    r = run_cli(args, tmp_path, snp="g1.snp")
     assert r.returncode != 0 and msg in r.stderr + r.stdout, (r.returncode, r.stderr[-500:])
     assert not (tmp_path / "e.txt").exists() and not (tmp_path / "o.txt").exists()
 

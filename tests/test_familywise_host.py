@@ -6,16 +6,13 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import fscl_amd
 import maxt_ref as mr
-from util import CLI, GOLD, ROOT
+from util import GOLD, ROOT, run_cli, run_host_check
 
 
 def test_exports(built):
@@ -186,22 +183,7 @@ def test_chunk_and_cap_refusal(built, monkeypatch):
 def test_host_check_under_sanitizers(built, tmp_path):
     """tools/familywise_host_check.c: the order, the chunk, the refusals, the combine, the thresholds and the writers
     under ASan and UBSan, as a stand-alone program (no device library, nothing loaded into Python)."""
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc not found"
-    exe = tmp_path / "familywise_host_check"
-    host = ROOT / "fscl_amd" / "csrc" / "host"
-    subprocess.run([gcc, "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fopenmp", "-std=gnu11",
-                    str(ROOT / "tools" / "familywise_host_check.c"), str(host / "familywise.c"), str(host / "util.c"), "-lm",
-                    "-o", str(exe)], check=True, capture_output=True, text=True, timeout=300)
-    r = subprocess.run([str(exe), str(tmp_path)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-400:], r.stderr[-2000:])
-
-
-def run_cli(args, tmp_path, env=None):
-    base = [str(CLI), "-f", str(GOLD / "g1.snp"), "-o", str(tmp_path / "o.txt")]
-    e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "FSCL_AMD_FWER_CAP")}
-    e.update(env or {})
-    return subprocess.run(base + args, capture_output=True, text=True, timeout=120, env=e)
+    run_host_check("familywise_host_check", ["familywise.c", "util.c"], tmp_path, [tmp_path])
 
 
 def test_cli_refusals(built, tmp_path):
@@ -218,7 +200,7 @@ def test_cli_refusals(built, tmp_path):
             ([f"--familywise-file={t}", "--familywise-trials=2.5"], None, "--familywise-trials must be an integer >= 1"),
             # g1 has 30 cells: one trial needs 240 bytes; refused once the data is loaded, before any device work
             ([f"--familywise-file={t}"], {"FSCL_AMD_FWER_CAP": "239"}, "FSCL_AMD_FWER_CAP=239")):
-        r = run_cli(args, tmp_path, env)
+        r = run_cli(args, tmp_path, env, snp="g1.snp")
         assert r.returncode != 0 and msg in r.stderr + r.stdout, (args, r.returncode, r.stderr[-400:])
         assert not t.exists() and not (tmp_path / "o.txt").exists()
     scan = fscl_amd.load_snp_input(GOLD / "g1.snp")

@@ -5,15 +5,13 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import blocks_ref as br
 import fscl_amd
-from util import CLI, GOLD, ROOT
+from util import GOLD, run_cli, run_host_check
 
 NAN = math.nan
 POS = [2000, 3000, 4000]
@@ -222,15 +220,7 @@ def test_scan_blocks_refusals_before_any_device_call(scan, monkeypatch, capfd):
 def test_host_check_under_sanitizers(built, tmp_path):
     """tools/jackknife_host_check.c: the block bound, the combination and the writer under ASan and UBSan, as a
     stand-alone program (no device library, nothing loaded into Python)."""
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc not found"
-    exe = tmp_path / "jackknife_host_check"
-    host = ROOT / "fscl_amd" / "csrc" / "host"
-    subprocess.run([gcc, "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fopenmp", "-std=gnu11",
-                    str(ROOT / "tools" / "jackknife_host_check.c"), str(host / "jackknife.c"), str(host / "util.c"), "-lm", "-o",
-                    str(exe)], check=True, capture_output=True, text=True, timeout=300)
-    r = subprocess.run([str(exe), str(tmp_path)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-400:], r.stderr[-2000:])
+    run_host_check("jackknife_host_check", ["jackknife.c", "util.c"], tmp_path, [tmp_path])
 
 
 # ------------------------------------------------------------------ the CLI's refusals
@@ -245,8 +235,7 @@ def test_host_check_under_sanitizers(built, tmp_path):
 ])
 def test_cli_refusals(built, tmp_path, args, msg):
     """Refused before the data is loaded: no device is touched and no file is written."""
-    r = subprocess.run([str(CLI), "-f", str(GOLD / "g1.snp"), "-o", str(tmp_path / "o.txt"),
-                        f"--jackknife-file={tmp_path / 'j.txt'}"] + args, capture_output=True, text=True, timeout=120)
+    r = run_cli([f"--jackknife-file={tmp_path / 'j.txt'}"] + args, tmp_path, snp="g1.snp")
     assert r.returncode != 0 and msg in r.stderr + r.stdout, (r.returncode, r.stderr[-500:])
     assert not (tmp_path / "j.txt").exists() and not (tmp_path / "o.txt").exists()
 

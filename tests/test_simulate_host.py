@@ -5,15 +5,13 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import fscl_amd
 import sample_ref as sr
-from util import CLI, GOLD
+from util import GOLD, run_cli
 
 NAN = math.nan
 
@@ -198,13 +196,6 @@ def test_bootstrap_output_and_quantiles(built, tmp_path):
     with pytest.raises(ValueError):
         fscl_amd.bootstrap_output(out, scan, sweeps, reps, rows)
     del keep
-
-
-def run_cli(args, tmp_path, env=None):
-    base = [str(CLI), "-f", str(GOLD / "g2.snp"), "-o", str(tmp_path / "o.txt")]
-    e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK")}
-    e.update(env or {})
-    return subprocess.run(base + args, capture_output=True, text=True, timeout=120, env=e)
 
 
 def test_cli_refusals(built, tmp_path):

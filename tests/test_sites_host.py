@@ -4,13 +4,12 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import subprocess
 
 import numpy as np
 import pytest
 
 import fscl_amd
-from util import CLI, GOLD
+from util import GOLD, run_cli
 
 NAN = math.nan
 POS = [100 * (i + 1) for i in range(10)]           # ten sites of chromosome "chrA" ...
@@ -151,13 +150,10 @@ def test_sites_cap_env(built, monkeypatch):
 
 
 def test_cli_refusals(built, tmp_path):
-    base = [str(CLI), "-f", str(GOLD / "g2.snp"), "-o", str(tmp_path / "o.txt")]
-    r = subprocess.run(base + [f"--sites-file={tmp_path / 's.txt'}", "--no-scan"], capture_output=True, text=True,
-                       timeout=120)
+    r = run_cli([f"--sites-file={tmp_path / 's.txt'}", "--no-scan"], tmp_path)
     assert r.returncode != 0 and "--sites-file needs the scan" in r.stderr + r.stdout
     assert not (tmp_path / "s.txt").exists()
-    r = subprocess.run(base + [f"--sites-file={tmp_path / 's.txt'}", "--sites-top=-1"], capture_output=True, text=True,
-                       timeout=120)
+    r = run_cli([f"--sites-file={tmp_path / 's.txt'}", "--sites-top=-1"], tmp_path)
     assert r.returncode != 0 and "--sites-top must be >= 0" in r.stderr + r.stdout
     assert not (tmp_path / "s.txt").exists()
     with pytest.raises(ValueError):

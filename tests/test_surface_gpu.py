@@ -503,6 +503,28 @@ def test_cli_end_to_end(built, tmp):
         assert summ == want
 
 
+def test_cli_six_files_at_once_equal_each_alone(built, tmp):
+    """One invocation writing the alpha, sites, surface, jackknife, conditional and expect files together, the
+    surface's step, half-width and alpha grid given and the others' left to follow them, against six invocations
+    that each write one file with the inherited values spelled out: the same bytes, file by file."""
+    g, step, hw, grid_s = 2000, 5000, 20000, "-12:0:5"
+    base = [str(CLI), "-f", str(GOLD / "g1.snp"), "-g", str(g), "-G", "100000"]
+    alone = {"alpha": [], "sites": [],
+             "surface": [f"--surface-step={step}", f"--surface-halfwidth={hw}", f"--surface-alphas={grid_s}"],
+             "jackknife": [f"--jackknife-step={step}", f"--jackknife-halfwidth={hw}", f"--jackknife-alphas={grid_s}"],
+             "conditional": [f"--conditional-step={g}", f"--conditional-alphas={grid_s}"],
+             "expect": [f"--expect-alphas={grid_s}"]}
+    runs = [("all", [f"--{k}-file={tmp / f'all_{k}.txt'}" for k in alone] + alone["surface"])]
+    runs += [(k, [f"--{k}-file={tmp / f'one_{k}.txt'}"] + extra) for k, extra in alone.items()]
+    for tag, extra in runs:
+        r = subprocess.run(base + ["-o", str(tmp / f"o_{tag}.txt")] + extra, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, (tag, r.stderr[-2000:])
+    for k in alone:
+        got, want = (tmp / f"all_{k}.txt").read_bytes(), (tmp / f"one_{k}.txt").read_bytes()
+        assert len(want) > 0 and got == want, f"--{k}-file: written with the other five it differs from the file written alone"
+        assert (tmp / f"o_{k}.txt").read_bytes() == (tmp / "o_all.txt").read_bytes()
+
+
 # ------------------------------------------------------------------ 8. argument errors
 def test_submit_argument_errors(shim):
     E_ARG, E_STATE = -1, -3

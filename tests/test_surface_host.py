@@ -3,14 +3,12 @@ alpha list, a request's positions, the argument errors reached without a device 
 from __future__ import annotations
 
 import math
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import fscl_amd
-from util import CLI, GOLD, ROOT
+from util import GOLD, run_cli, run_host_check
 
 NAN = math.nan
 
@@ -192,15 +190,7 @@ def test_output_bytes(scan, tmp_path):
 def test_host_check_under_sanitizers(built, tmp_path):
     """tools/surface_host_check.c: the alpha list, the positions, the region and the writer under ASan and
     UBSan, as a stand-alone program (no device library, nothing loaded into Python)."""
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc not found"
-    exe = tmp_path / "surface_host_check"
-    host = ROOT / "fscl_amd" / "csrc" / "host"
-    subprocess.run([gcc, "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fopenmp", "-std=gnu11",
-                    str(ROOT / "tools" / "surface_host_check.c"), str(host / "surface.c"), str(host / "util.c"), "-lm", "-o",
-                    str(exe)], check=True, capture_output=True, text=True, timeout=300)
-    r = subprocess.run([str(exe), str(tmp_path)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-400:], r.stderr[-2000:])
+    run_host_check("surface_host_check", ["surface.c", "util.c"], tmp_path, [tmp_path])
 
 
 # ------------------------------------------------------------------ the CLI's refusals
@@ -221,8 +211,7 @@ def test_host_check_under_sanitizers(built, tmp_path):
 ])
 def test_cli_refusals(built, tmp_path, args, msg):
     """Refused before the data is loaded: no device is touched and no file is written."""
-    r = subprocess.run([str(CLI), "-f", str(GOLD / "g1.snp"), "-o", str(tmp_path / "o.txt"),
-                        f"--surface-file={tmp_path / 's.txt'}"] + args, capture_output=True, text=True, timeout=120)
+    r = run_cli([f"--surface-file={tmp_path / 's.txt'}"] + args, tmp_path, snp="g1.snp")
     assert r.returncode != 0 and msg in r.stderr + r.stdout, (r.returncode, r.stderr[-500:])
     assert not (tmp_path / "s.txt").exists() and not (tmp_path / "o.txt").exists()
 

@@ -5,9 +5,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
-import shutil
-import subprocess
 
 import mpmath as mp
 import numpy as np
@@ -16,7 +13,7 @@ import scipy.stats as st
 
 import fscl_amd
 import tail_ref as tr
-from util import CLI, GOLD, ROOT
+from util import GOLD, run_cli, run_host_check
 
 
 def mp_logpdf(x: float, k: int, lam: float):
@@ -211,22 +208,7 @@ def test_exports_and_layout(built):
 def test_host_check_under_sanitizers(built, tmp_path):
     """tools/tail_host_check.c: the packing, chunking, summary and writer under ASan and UBSan, as a
     stand-alone program (no device library, nothing loaded into Python)."""
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc not found"
-    exe = tmp_path / "tail_host_check"
-    host = ROOT / "fscl_amd" / "csrc" / "host"
-    subprocess.run([gcc, "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fopenmp", "-std=gnu11",
-                    str(ROOT / "tools" / "tail_host_check.c"), str(host / "tail.c"), str(host / "util.c"), "-lm", "-o", str(exe)],
-                   check=True, capture_output=True, text=True, timeout=300)
-    r = subprocess.run([str(exe), str(tmp_path)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-400:], r.stderr[-2000:])
-
-
-def run_cli(args, tmp_path, env=None):
-    base = [str(CLI), "-f", str(GOLD / "g2.snp"), "-o", str(tmp_path / "o.txt")]
-    e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK")}
-    e.update(env or {})
-    return subprocess.run(base + args, capture_output=True, text=True, timeout=120, env=e)
+    run_host_check("tail_host_check", ["tail.c", "util.c"], tmp_path, [tmp_path])
 
 
 def test_cli_refusals(built, tmp_path):

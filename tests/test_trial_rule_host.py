@@ -5,13 +5,11 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from util import ROOT
+from util import run_host_check
 import fscl_amd
 
 RAND_MAX = 2147483647
@@ -142,12 +140,4 @@ def test_a_mixed_sequence(L):
 def test_host_check_under_sanitizers(built, tmp_path):
     """tools/trial_rule_check.c: the same crafted sequences under ASan and UBSan, as a stand-alone program
     built from perm.c and util.c alone (no device library, nothing loaded into Python)."""
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc not found"
-    exe = tmp_path / "trial_rule_check"
-    host = ROOT / "fscl_amd" / "csrc" / "host"
-    subprocess.run([gcc, "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fopenmp", "-std=gnu11",
-                    str(ROOT / "tools" / "trial_rule_check.c"), str(host / "perm.c"), str(host / "util.c"), "-lm", "-o", str(exe)],
-                   check=True, capture_output=True, text=True, timeout=300)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-400:], r.stderr[-2000:])
+    run_host_check("trial_rule_check", ["perm.c", "util.c"], tmp_path)

@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import json
 import os
+import shutil
 import subprocess
 from pathlib import Path
 
@@ -54,6 +55,41 @@ def run_oracle(snp, out, opts, dump=None, threads: int | None = None) -> subproc
     if dump:
         cmd.append(f"--dump-points={dump}")
     return subprocess.run(cmd, capture_output=True, text=True, check=True)
+
+
+def run_cli(args, tmp_path, env=None, snp="g2.snp") -> subprocess.CompletedProcess:
+    """The `fscl` CLI on a golden input with its output at tmp_path/o.txt (snp=None: ``args`` alone), outside any
+    launcher's ranks; ``env`` is added to the environment."""
+    base = [str(CLI)] + (["-f", str(GOLD / snp), "-o", str(tmp_path / "o.txt")] if snp else [])
+    e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "FSCL_AMD_FWER_CAP")}
+    e.update(env or {})
+    return subprocess.run(base + list(args), capture_output=True, text=True, timeout=120, env=e)
+
+
+CLI_KEPT = ("Error:", "Warning:", "fscl:", "Fatal", "Specify", "Unrecognized", "Option ", "fscl (MI355X)")
+
+
+def cli_answer(case, tmp_path) -> tuple[int, list[str]]:
+    """(exit code, message lines in order) of one tests/golden/cli_refusals.json case: the output lines that begin
+    with one of CLI_KEPT (no status or timing line does); @TMP@ and @GOLD@ stand for the two directories."""
+    real = lambda a: a.replace("@TMP@", str(tmp_path)).replace("@GOLD@", str(GOLD))  # noqa: E731
+    r = run_cli([real(a) for a in case["args"]], tmp_path, case["env"], snp=None)
+    text = (r.stderr + r.stdout).replace(str(tmp_path), "@TMP@").replace(str(GOLD), "@GOLD@")
+    return r.returncode, [ln for ln in text.splitlines() if ln.startswith(CLI_KEPT)]
+
+
+def run_host_check(name, sources, tmp_path, args=()) -> None:
+    """Build tools/<name>.c with the host ``sources`` as a stand-alone program under ASan and UBSan (no device
+    library, nothing loaded into Python), run it and expect exit status 0 and a last line "ok"."""
+    gcc = shutil.which("gcc")
+    assert gcc, "gcc not found"
+    exe = tmp_path / name
+    host = ROOT / "fscl_amd" / "csrc" / "host"
+    subprocess.run([gcc, "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fopenmp", "-std=gnu11",
+                    str(ROOT / "tools" / f"{name}.c"), *(str(host / s) for s in sources), "-lm", "-o", str(exe)],
+                   check=True, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([str(exe), *(str(a) for a in args)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-400:], r.stderr[-2000:])
 
 
 def same_bits(a: float, b: float) -> bool:
